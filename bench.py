@@ -5,18 +5,23 @@ A "step" is one pass of the hot path over one batch: QUERIES_PER_STEP fp32 query
 HBM) -> exact cosine top-K over this rank's fp32 corpus shard -> [N > 1 only] the path's one exchange step, an
 RCCL all-gather of the per-shard top-k + the on-GPU merge.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
+A plain run does only what the headline figure needs: set up, warm up, time EXACTLY K steps (one round), write the
+last step's outputs if --dump-outputs is given, print the one JSON line.  --full adds everything else below (the
+secondary legs, CPU baselines, fp64-oracle checks, the roofline's live kernel samples, the DETAIL line).
+
 Workloads (BASELINE.json):
-  N = 1   configs[1]: 100 000 x 1024 corpus, 64 queries per step, top-10.  The same line carries `target_1m`
-          (1M x 1024 on one GPU, 32 and 64 queries per step: the north-star >= 70 % HBM target) and `encode`
-          (configs[3] shape).
+  N = 1   configs[1]: 100 000 x 1024 corpus, 64 queries per step, top-10.  With --full the same line carries
+          `target_1m` (1M x 1024 on one GPU, 32 and 64 queries per step: the north-star >= 70 % HBM target) and
+          `encode` (configs[3] shape).
   N > 1   configs[2]: ONE 1M x 1024 corpus sharded over the N ranks (contiguous row shards), every rank searches
           the same 64 queries, one all-gather, merge.  Total work is fixed: "scaling": "strong"; the 1-GPU point
           of that curve is `target_1m.q64` of the N = 1 line.  `--mode weak` instead keeps 100 000 rows per rank.
 `value` is always DISTINCT queries answered per second by the whole job (never multiplied by the rank count).
-Rank 0 prints a `DETAIL {...}` line with every leg, then LAST the ONE compact JSON line (< 4 KB) the driver parses.
+With --full, rank 0 prints a `DETAIL {...}` line with every leg, then LAST the ONE compact JSON line (< 4 KB) the
+driver parses; a plain run prints the one line only.
 """
 from __future__ import annotations
 
@@ -79,12 +84,16 @@ def timed_rounds(step, fence, steps: int, rounds: int):
 
 
 def search_leg(index, queries, k, steps, warmup, rounds, step_extra=None, fence_extra=None, outs=None,
-               prewarm_s=0.3, pipelined=False):
+               prewarm_s=0.3, pipelined=False, sample=True, keep_last=False, result=None):
     """Warm up, then time `rounds` x `steps` searches of `queries` (device tensor) on torch's current stream.
     Returns timing + live HIP-event kernel times + the prefilter path's candidate statistics.
     pipelined: the steps go through crag_index_search_pipelined (the throughput form for a run of independent
     searches from one stream: consecutive searches rotate over three streams of the index's own) with ONE
-    crag_index_join in front of every fence -- the queries are resident and the outputs are read behind the fence."""
+    crag_index_join in front of every fence -- the queries are resident and the outputs are read behind the fence.
+    sample=False: no live kernel samples (no event packets in the timed steps, no untimed steps after them); the
+    result then carries the times and outputs only.  keep_last: `last` = a copy, taken behind the final fence, of
+    what the last timed step handed its caller -- the search's outputs, or the tensors `result()` names (N > 1: the
+    merge's)."""
     dev = queries.device
     nq = int(queries.shape[0])
     if outs is None:
@@ -129,6 +138,18 @@ def search_leg(index, queries, k, steps, warmup, rounds, step_extra=None, fence_
     for _ in range(warmup):
         step()
     fence()
+
+    def last_step_result():
+        if not keep_last:
+            return None
+        got = result() if result is not None else (alts[flip[0]] if pipelined else (oi, osc, oc))
+        return tuple(t.clone() for t in got)
+
+    if not sample:
+        times = timed_rounds(step, fence, steps, rounds)
+        return {"times": times, "last": last_step_result(), "kernel": index.last_scan_kernel(),
+                "row_bytes": (index.prefilter_row_bytes() if "prefilter" in index.last_scan_kernel() else DIM * 4),
+                "out": (oi, osc, oc)}
     index.prefilter_stats()
     # Live HIP-event samples on the launch stream, SPARSE: a sampled search carries five extra event packets = 19 us
     # (scripts/probes/round_fixed_cost.py: a round of 20 searches takes 976 us without sampling, 1024 us with every
@@ -140,6 +161,7 @@ def search_leg(index, queries, k, steps, warmup, rounds, step_extra=None, fence_
     every = max(20, total // want)
     index.profile_enable(every)
     times = timed_rounds(step, fence, steps, rounds)
+    last = last_step_result()
     in_region = (total - every // 2 - 1) // every + 1 if total > every // 2 else 0
     for _ in range(max(0, want - in_region) * every):
         step()
@@ -161,7 +183,7 @@ def search_leg(index, queries, k, steps, warmup, rounds, step_extra=None, fence_
             "outputs_identical_on_both_streams": (bool(torch.equal(oi, alt[0]) and torch.equal(oc, alt[2]))
                                                   if pipelined else None),
             "row_bytes": (index.prefilter_row_bytes() if "prefilter" in index.last_scan_kernel() else DIM * 4),
-            "out": (oi, osc, oc)}
+            "out": (oi, osc, oc), "last": last}
 
 
 def overlap_leg(index, queries, k, n_streams, steps):
@@ -702,14 +724,49 @@ def emit(full: dict) -> None:
     print(json.dumps(compact_line(full)), flush=True)
 
 
-def main() -> None:
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_outputs(out_dir: str, result) -> None:
+    """--dump-outputs: what the timed path handed its caller in its last step, as out_dir/<name>.npy -- `ids` (int64
+    row ids, exact in float64), `scores` (float32), `counts` (float64).  The inputs are seeded, so two builds run with
+    the same arguments can be compared file for file.  Past DUMP_LIMIT_BYTES in all, a fixed seeded sample of the
+    query rows is written instead, their row numbers in `sample_rows`."""
+    ids, scores, counts = (t.cpu().numpy() for t in result)
+    arrays = {"ids": ids.astype(np.float64), "scores": scores.astype(np.float32), "counts": counts.astype(np.float64)}
+    nq = int(ids.shape[0])
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:   # per kept row: its share of the three arrays + its 8-byte entry in sample_rows
+        keep = int(DUMP_LIMIT_BYTES // (total / nq + 8))
+        rows = np.sort(np.random.default_rng(0).choice(nq, size=keep, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
+SECONDARY_LEGS = ("no_other_api", "no_cpu_baseline", "no_encode", "no_target_1m", "no_overlap_leg", "no_large_k",
+                  "no_hybrid", "no_query_path", "no_fp32_rows_leg")
+
+
+def parse_args(argv=None) -> argparse.Namespace:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--steps", type=int, default=2000, help="K: the number of timed steps")
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--rounds", type=int, default=5,
-                    help="the K timed steps are repeated this many times; `value` comes from the FIRST round "
-                         "(exactly K steps, the contract), median and min over the rounds are reported beside it")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the other API form, the multi-stream and fp32-rows "
+                         "repeats, top-50 / top-100, the 1M-row target, hybrid, query-path and encode legs, the CPU "
+                         "baselines, the fp64-oracle recall checks, the roofline's live kernel samples, the N > 1 "
+                         "per-rank breakdown and the DETAIL line (the --no-* options below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path handed its caller in its last step "
+                         "(ids, scores, counts of the search; N > 1: of the merge) as DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--rounds", type=int, default=None,
+                    help="the K timed steps are repeated this many times (default: 1; 5 with --full); `value` comes "
+                         "from the FIRST round (exactly K steps, the contract), median and min over the rounds are "
+                         "reported beside it")
     ap.add_argument("--rows-per-gpu", type=int, default=0, help="override the corpus rows held by each rank")
     ap.add_argument("--mode", choices=("auto", "strong", "weak"), default="auto",
                     help="N > 1: strong = one 1M-row corpus sharded over the ranks (BASELINE configs[2], default); "
@@ -736,7 +793,17 @@ def main() -> None:
     ap.add_argument("--encode-steps", type=int, default=20)
     ap.add_argument("--no-fp32-rows-leg", action="store_true",
                     help="skip the legs that repeat the search on an index without the fp16 mirror")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.rounds is None:
+        args.rounds = 5 if args.full else 1
+    if not args.full:   # a plain run: the headline leg alone
+        for name in SECONDARY_LEGS:
+            setattr(args, name, True)
+    return args
+
+
+def main() -> None:
+    args = parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -815,8 +882,12 @@ def main() -> None:
     # (crag_index_search_pipelined: consecutive searches rotate over three streams of the index's own, one join in
     # front of every fence) is timed beside it.  N > 1: a step's collective consumes the search's output -> in order.
     pipelined = world == 1 and args.api == "pipelined"
+    # a plain run's timed steps carry no live kernel samples (the roofline is --full's)
     leg = search_leg(index, queries, k, args.steps, args.warmup, args.rounds, step_extra, fence_extra, outs,
-                     pipelined=pipelined)
+                     pipelined=pipelined, sample=args.full, keep_last=bool(args.dump_outputs),
+                     result=(lambda: (f_ids, f_sc, f_ct)) if world > 1 else None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, leg["last"])
     large_k = {}
 
     def large_k_leg(ix, q, rows_, kk):
@@ -836,8 +907,8 @@ def main() -> None:
                                pipelined=not pipelined, prewarm_s=0.05)
         leg["identical_to_other_api"] = all(bool(torch.equal(a, b)) for a, b in zip(leg["out"], leg_other["out"]))
     times = leg["times"]
-    per_rank = None
-    if world > 1:
+    per_rank = sharded_recall = None
+    if world > 1 and args.full:
         # where a rank's step goes: local search, the one exchange (all-gather), the merge — torch events on the
         # launch stream around each part of 40 untimed steps (the all-gather's completion is ordered into the
         # stream by ProcessGroupNCCL before the next event is recorded)
@@ -863,7 +934,6 @@ def main() -> None:
         # the merged answer against the fp64 oracle (the checker, outside every timed region): every rank scores a sample of
         # the queries against ITS shard on its host cores, rank 0 merges the per-shard oracle lists (score descending,
         # id ascending -- the search's order) and compares them with what the exchange + merge left on the GPU
-        sharded_recall = None
         if not args.no_cpu_baseline:
             import oracle
             oracle.set_threads(max(1, min(os.cpu_count() or 1, 64) // world))
@@ -890,7 +960,7 @@ def main() -> None:
 
     traffic_doc = None
     tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath):
+    if args.full and os.path.exists(tpath):
         try:
             traffic_doc = json.load(open(tpath))
         except Exception:
@@ -963,7 +1033,7 @@ def main() -> None:
         encode = encode_leg(dev, rank, world, dist, args.encode_steps, enc=shared_enc)
 
     same_job_1gpu = None
-    if world > 1 and rank == 0 and mode == "strong":
+    if world > 1 and rank == 0 and mode == "strong" and args.full:
         # the 1-GPU point of THIS job, measured in this run on rank 0's GPU while the other ranks wait at the final
         # barrier: the driver's N = 1 line times configs[1] (100 000 rows), not the 1M-row job that is sharded here
         try:
@@ -981,7 +1051,6 @@ def main() -> None:
             same_job_1gpu = {"error": f"{type(exc).__name__}: {exc}"}
 
     if rank == 0:
-        roof = roofline(rows, nq, k, leg, traffic_doc)
         line = {
             "metric": "queries/sec @ recall@10=1.0 (exact cosine top-10, 1024-d fp32 corpus)",
             "value": round(nq * args.steps / elapsed, 2),
@@ -1009,8 +1078,9 @@ def main() -> None:
                         "crag_index_search_async (in stream order)"),
                 "hbm_bytes_per_corpus_row": DIM * 4 + (leg.get("row_bytes") if leg.get("row_bytes") != DIM * 4 else 0) + 12,
             },
-            "roofline": roof,
         }
+        if args.full:   # from the live kernel samples of the timed steps
+            line["roofline"] = roofline(rows, nq, k, leg, traffic_doc)
         if world > 1:
             line["config"]["per_rank_step_breakdown"] = per_rank
             if sharded_recall is not None:   # (the sharded job's answer against the per-shard fp64 oracle lists, merged)
@@ -1061,7 +1131,10 @@ def main() -> None:
             line["cpu_baseline"] = base
             line["config"]["recall_at_10_vs_fp64_oracle"] = recall
             line["config"]["topk_order_identical_to_oracle"] = same_order
-        emit(line)
+        if args.full:
+            emit(line)
+        else:   # a plain run: the one line
+            print(json.dumps(line), flush=True)
 
     if world > 1:
         dist.barrier()

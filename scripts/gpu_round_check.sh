@@ -11,17 +11,17 @@ mkdir -p $O
 ( while true; do sleep 45; echo "[gpu_round_check] $(date +%T) still running"; done ) &
 HB=$!
 trap "kill $HB 2>/dev/null" EXIT
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 # the driver's own invocation (few steps between synchronisations)
-python bench.py --steps 20 --warmup 5 > $O/bench_steps20.json 2>> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_steps20.json 2>> $O/bench.err
 # two ranks folded onto the one GPU of this box over gloo: the N > 1 code path (shards, exchange, merge, per-rank
 # breakdown) end to end; its times say nothing about xGMI
-CRAG_BENCH_BACKEND=gloo timeout -k 10 240 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 100 --warmup 10 --rounds 2 --no-encode > $O/bench_n2_gloo_rehearsal.json 2> $O/bench_n2.err || true
+CRAG_BENCH_BACKEND=gloo timeout -k 10 240 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 100 --warmup 10 --rounds 2 --no-encode > $O/bench_n2_gloo_rehearsal.json 2> $O/bench_n2.err || true
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --no-cpu-baseline > $O/stats_bench.json 2> $O/stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --no-cpu-baseline > $O/stats_bench.json 2> $O/stats.err
 # the headline leg alone (in the full command above the 1M legs launch the same kernel template)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_headline -- python3 $R/bench.py --no-cpu-baseline --no-encode --no-target-1m --no-fp32-rows-leg --no-overlap-leg --no-other-api --no-large-k > /dev/null 2> $O/stats_headline.err
-B="--steps 200 --warmup 20 --rounds 1 --no-cpu-baseline --no-encode --no-target-1m --no-fp32-rows-leg --no-overlap-leg --no-other-api --no-large-k"
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_headline -- python3 $R/bench.py --full --no-cpu-baseline --no-encode --no-target-1m --no-fp32-rows-leg --no-overlap-leg --no-other-api --no-large-k > /dev/null 2> $O/stats_headline.err
+B="--full --steps 200 --warmup 20 --rounds 1 --no-cpu-baseline --no-encode --no-target-1m --no-fp32-rows-leg --no-overlap-leg --no-other-api --no-large-k"
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_${c}_100k64 -- python3 $R/bench.py $B > /dev/null 2>&1
   rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_${c}_1m32 -- python3 $R/bench.py $B --rows-per-gpu 1000000 --queries 32 --steps 60 > /dev/null 2>&1

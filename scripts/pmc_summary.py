@@ -67,7 +67,7 @@ def traffic(fetch_csv: str, write_csv: str, workload: str, out_json: str) -> Non
     _, write_kb = _scan_mean(write_csv, "WRITE_SIZE")
     doc = json.load(open(out_json)) if os.path.exists(out_json) else {}
     doc["method"] = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over "
-                     "`python bench.py --steps .. --no-cpu-baseline --no-encode --no-target-1m [--rows-per-gpu 1000000 "
+                     "`python bench.py --full --steps .. --no-cpu-baseline --no-encode --no-target-1m [--rows-per-gpu 1000000 "
                      "--queries 32|64]` (scripts/gpu_round_check.sh); per-kernel means over launches 10.. "
                      "(scripts/pmc_summary.py); KB -> bytes x1024; FETCH_SIZE doubled (gfx950 reports half of a wide "
                      "coalesced streaming read, MI355X_MICROARCH.md HBM section); WRITE_SIZE taken as is.")

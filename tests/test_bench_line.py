@@ -11,6 +11,8 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
 import bench  # noqa: E402
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 CONTRACT_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                  "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline")
@@ -66,3 +68,49 @@ def test_emit_prints_the_compact_line_last(tmp_path, monkeypatch):
     last = json.loads(lines[-1])
     assert len(lines[-1]) < bench.COMPACT_LIMIT and "roofline" in last and "cpu_baseline" in last
     assert json.loads((tmp_path / "gpurun_out" / "bench_detail.json").read_text())["value"] == last["value"]
+
+
+def test_plain_run_is_the_headline_leg_alone():
+    """A plain run times exactly --steps steps once and runs none of the secondary legs; --full runs them all."""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert not plain.full and plain.steps == 7 and plain.warmup == 3 and plain.rounds == 1
+    assert plain.dump_outputs is None
+    assert all(getattr(plain, name) for name in bench.SECONDARY_LEGS)
+    full = bench.parse_args(["--steps", "7", "--full"])
+    assert full.rounds == 5 and not any(getattr(full, name) for name in bench.SECONDARY_LEGS)
+    assert bench.parse_args(["--full", "--no-encode"]).no_encode
+    assert bench.parse_args(["--dump-outputs", "d", "--rounds", "2"]).rounds == 2
+
+
+def _outputs(nq, k):
+    g = torch.Generator().manual_seed(3)
+    ids = torch.randint(0, 1 << 40, (nq, k), generator=g, dtype=torch.int64)
+    ids[-1, -2:] = -1                                      # short lists pad with -1
+    scores = torch.rand(nq, k, generator=g, dtype=torch.float32)
+    counts = torch.randint(0, k + 1, (nq,), generator=g, dtype=torch.int32)
+    return ids, scores, counts
+
+
+def test_dump_outputs_writes_the_result_exactly_as_floats(tmp_path):
+    ids, scores, counts = _outputs(64, 10)
+    bench.dump_outputs(str(tmp_path / "out"), (ids, scores, counts))
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["counts.npy", "ids.npy", "scores.npy"]
+    got = {name: np.load(tmp_path / "out" / f"{name}.npy") for name in ("ids", "scores", "counts")}
+    assert got["ids"].dtype == np.float64 and np.array_equal(got["ids"].astype(np.int64), ids.numpy())
+    assert got["scores"].dtype == np.float32 and np.array_equal(got["scores"], scores.numpy())
+    assert got["counts"].dtype == np.float64 and np.array_equal(got["counts"].astype(np.int32), counts.numpy())
+
+
+def test_dump_outputs_keeps_a_fixed_sample_under_the_limit(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 40_000)
+    ids, scores, counts = _outputs(2000, 10)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), (ids, scores, counts))
+    got = {name: np.load(tmp_path / "a" / f"{name}.npy") for name in ("ids", "scores", "counts", "sample_rows")}
+    assert sum(a.nbytes for a in got.values()) <= 40_000
+    rows = got["sample_rows"].astype(np.int64)
+    assert 0 < len(rows) < 2000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got["ids"].astype(np.int64), ids.numpy()[rows])
+    assert np.array_equal(got["scores"], scores.numpy()[rows])
+    assert np.array_equal(got["counts"].astype(np.int32), counts.numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "b" / "sample_rows.npy"), got["sample_rows"])
