@@ -1750,6 +1750,8 @@ __device__ __forceinline__ void pf_stage(PfLds<NQB> &L, const PfOwner<NQB> &o, c
 template <int NQB, bool LAST>
 __device__ __forceinline__ void pf_sift(const PfParams &p, PfLds<NQB> &L, int64_t window_row0) {
     __syncthreads();   // every append and threshold update of the tile is visible
+    // (every wave is in here -- the sift is entered on a uniform decision -- and nobody writes L.n_stage before the
+    // next barrier: the same n everywhere)
     const uint32_t n = L.n_stage < (uint32_t)PF_STAGE ? L.n_stage : (uint32_t)PF_STAGE;
     const int tid = threadIdx.x;
     if (LAST && n == 0u) return;  // (uniform)
@@ -1778,7 +1780,17 @@ __device__ __forceinline__ void pf_sift(const PfParams &p, PfLds<NQB> &L, int64_
             if (!LAST) L.stage[atomicAdd(&L.n_stage, 1u)] = ent[i];
         }
     __syncthreads();
-    if (!LAST && L.n_stage <= (uint32_t)(PF_FLUSH_ABOVE / 2)) return;  // (uniform) the survivors stay staged
+    if constexpr (!LAST) {
+        // The survivors stay staged unless the buffer is still more than half full.  Every wave reads the count
+        // between two barriers and decides on its register copy: a wave that returns goes on to the next tile and
+        // appends to L.n_stage (pf_stage) with no barrier in front of that, so a slower wave reading L.n_stage
+        // after it would see a larger count, take the flush branch alone and pair its barriers with the others'
+        // per-tile barrier (candidates flushed and still staged = duplicates, or appends zeroed away = losses).
+        // A sift is rare (a few per workgroup and search at most): the extra barrier costs nothing on the tile path.
+        const uint32_t kept = L.n_stage;
+        __syncthreads();
+        if (kept <= (uint32_t)(PF_FLUSH_ABOVE / 2)) return;   // (uniform)
+    }
     if (tid < 32 * NQB) {
         const uint32_t cnt = L.qcount[tid];
         const int qg = (int)blockIdx.y * (32 * NQB) + tid;
@@ -2103,7 +2115,11 @@ __global__ __launch_bounds__(SCAN_THREADS) void prefilter_kernel(PfParams p) {
         // One barrier per tile.  It also carries the (uniform) decision to flush the staging buffer: every wave
         // posts what it saw after its own appends of the previous tile -- the wave whose append came last saw the
         // final count -- and all waves OR the same eight words behind the barrier.  [__syncthreads_or is a
-        // workgroup reduction with three barriers of its own.]
+        // workgroup reduction with three barriers of its own.]  Why this read of L.n_stage may race and the decision
+        // is still uniform: the count only picks the wave's OWN word, and nobody decides on it; the words of buffer
+        // `buf` are read behind this barrier and written again two tiles later, i.e. only after every wave has
+        // passed the next tile's barrier (a sift in between adds barriers, never removes one).  A stale count can
+        // only be lower than the final one in a wave that is not the last to append; the last one sees them all.
         if (lane == 0) L.want_flush[buf][w] = L.n_stage > (uint32_t)PF_FLUSH_ABOVE ? 1u : 0u;
         __syncthreads();
         {
@@ -2257,7 +2273,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void prefilter_kernel(PfParams p) {
         // handful of candidates and are staged back to back.  Without a bound a tile can add 2048 entries: a check
         // (a barrier) in front of each.
         const bool unbounded = any_without_bound();
-        auto sift_if_full = [&](bool post_unbounded) -> bool {
+        auto sift_if_full = [&](bool post_unbounded) -> bool {   // (uniform for the reasons given in the tile loop)
             if (lane == 0) L.want_flush[buf][w] = (L.n_stage > (uint32_t)PF_FLUSH_ABOVE ? 1u : 0u) | (post_unbounded ? 2u : 0u);
             __syncthreads();
             const u32x4 f0 = *reinterpret_cast<const u32x4 *>(&L.want_flush[buf][0]);

@@ -156,7 +156,7 @@ class TechTokenIndex:
         except Exception:   # interpreter shutdown: the library may be gone already
             pass
 
-    _E2BIG = -4   # crag_dense.h CRAG_E2BIG: a query with more than 32 distinct tokens, nothing was enqueued
+    _E2BIG = -5   # crag_dense.h CRAG_E2BIG: a query with more than 32 distinct tokens, nothing was enqueued
 
     def _pass(self, token_lists, k: int, row_mask, mask_stride: int, stream: int, borrow: bool = True):
         """One launch of the lane (crag_tech_lane_host: the hashes are packed, uploaded and matched behind ONE call).

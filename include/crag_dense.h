@@ -33,7 +33,7 @@ extern "C" {
 #define CRAG_EINVAL (-1)   /* bad argument */
 #define CRAG_EHIP (-2)     /* HIP runtime error (message has hipGetErrorString) */
 #define CRAG_ENOMEM (-3)   /* capacity exceeded / allocation failed */
-#define CRAG_E2BIG (-4)    /* an input exceeds what one call takes; the caller splits it (crag_tech_lane_host) */
+#define CRAG_E2BIG (-5)    /* an input exceeds what one call takes; the caller splits it (crag_tech_lane_host) */
 #define CRAG_ENODEV (-4)   /* no usable gfx950 device */
 
 #define CRAG_MAX_K 128     /* reference uses k = 50 / 10 (retrieve.py:18-19); BASELINE asks 10..100 */

@@ -37,6 +37,17 @@ def test_header_constants_match_python_binding():
     assert int(re.search(r"#define CRAG_DIM (\d+)", text).group(1)) == _native.CRAG_DIM
 
 
+def test_error_codes_are_distinct():
+    """A caller tells the errors apart by value only (fusion.py splits a query into passes on CRAG_E2BIG): every
+    CRAG_E* the header defines is negative and none shares its value with another."""
+    codes = dict(re.findall(r"#define (CRAG_E\w+) \((-\d+)\)", HEADER.read_text()))
+    assert {"CRAG_EINVAL", "CRAG_EHIP", "CRAG_ENOMEM", "CRAG_E2BIG", "CRAG_ENODEV"} <= set(codes), codes
+    values = [int(v) for v in codes.values()]
+    assert all(v < 0 for v in values) and len(set(values)) == len(values), codes
+    from cadence_rag_amd.fusion import TechTokenIndex
+    assert TechTokenIndex._E2BIG == int(codes["CRAG_E2BIG"])
+
+
 def test_argument_errors_are_codes_not_crashes(native_lib):
     h = ctypes.c_void_p()
     assert native_lib.crag_index_create(0, 0, 10, ctypes.byref(h)) == -1  # CRAG_EINVAL: dim

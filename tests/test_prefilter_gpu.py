@@ -323,8 +323,11 @@ def test_selection_shared_by_several_blocks_per_query_equals_one_block(gpu, monk
         ix = _index(corpus, monkeypatch)
         try:
             ix.prefilter_stats()
-            res = [ix.search(q, k), ix.search(q, k), ix.search(q, k, row_mask=packed), ix.search(q[: max(1, nq // 2)], k)]
-            out[split] = (res, ix.prefilter_stats())
+            res, stats = [], []
+            for qq, m in ((q, None), (q, None), (q, packed), (q[: max(1, nq // 2)], None)):
+                res.append(ix.search(qq, k, row_mask=m))
+                stats.append(ix.prefilter_stats())   # per search (it synchronises and resets the sums)
+            out[split] = (res, stats)
         finally:
             ix.close()
     monkeypatch.delenv("CRAG_NO_RSPLIT", raising=False)
@@ -335,9 +338,13 @@ def test_selection_shared_by_several_blocks_per_query_equals_one_block(gpu, monk
     # the scan's workgroups saw each other's bounds: it varies from run to run, the survivors do not)
     # (a search whose candidate list overflows -- k = 128 on 45 000 rows can, depending on that timing -- is answered
     # by the fallback blocks and not counted: the results above are the same bits either way)
-    assert out[True][1]["searches"] <= 4 and out[False][1]["searches"] <= 4
-    if out[True][1]["searches"] == out[False][1]["searches"] == 4:
-        assert out[True][1]["rescored_rows"] == out[False][1]["rescored_rows"]
+    may_overflow = (n, k) == (45_000, 128)
+    for i, (a, b) in enumerate(zip(out[True][1], out[False][1])):
+        assert a["searches"] <= 1 and b["searches"] <= 1
+        if a["searches"] == b["searches"] == 1:
+            assert a["rescored_rows"] == b["rescored_rows"], (i, a, b)
+        elif not may_overflow:
+            pytest.fail(f"search {i} went to the overflow fallback (R split: {a}, one block: {b})")
     s = min(nq, 3)
     want = oracle.exact_topk(q[:s], corpus, k, mode=oracle.F64, fast=True)
     got = out[True][0][0]
