@@ -86,6 +86,9 @@ SIGNATURES = {
                                                  _c.c_int, _c.c_float, _c.c_float, _P]),
     "crag_enc_small_attention_seqs_parts": (_c.c_int, [_P, _c.c_int, _c.c_int, _P, _P, _P, _c.c_int, _P, _P, _c.c_int,
                                                        _c.c_int, _P, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _P]),
+    "crag_enc_attention_prefixed": (_c.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int64, _c.c_int, _c.c_int,
+                                               _c.c_float, _P]),
+    "crag_enc_rerank_head": (_c.c_int, [_P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_float, _P]),
 }
 
 

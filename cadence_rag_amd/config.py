@@ -3,6 +3,8 @@
 (case-insensitive, no prefix).  Plain dataclass: the reference's pydantic-settings object is
 mutated by its tests with monkeypatch.setattr(settings, ...), and so is this one.
 
+The RERANK_* knobs are the reference's Phase-4 plan (PHASED_PLAN.md:291-297), same names and spelling.
+
 New knob: EMBEDDINGS_BASE_URL keeps its meaning ("" disables the dense lane); the value
 "native" (or "native://...") selects the in-process MI355X encoder instead of an HTTP gateway.
 """
@@ -35,6 +37,19 @@ class Settings:
     # native lane only
     embeddings_device: int = 0
     embeddings_max_length: int = 1024  # gateway truncation (RUNBOOK:484,748)
+    # reranker (PHASED_PLAN.md:291-297): "" = off, "native" = the in-process Qwen3Reranker, http(s) = a /rerank service
+    rerank_base_url: str = ""
+    rerank_model_id: str = "Qwen/Qwen3-Reranker-4B"
+    rerank_timeout_s: float = 180.0
+    rerank_max_chars_per_doc: int = 0   # 0: no character cut (the model truncates to rerank_max_length tokens)
+    rerank_topn_in: int = 40            # fused rows scored per side
+    rerank_topm_out: int = 12           # rows kept per side after reranking
+    rerank_max_length: int = 1024
+    rerank_device: int = -1             # -1: embeddings_device
+
+    def __post_init__(self) -> None:
+        if self.rerank_device < 0:
+            self.rerank_device = self.embeddings_device
 
     @classmethod
     def from_env(cls) -> "Settings":

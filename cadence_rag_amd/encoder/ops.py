@@ -274,3 +274,36 @@ def rmsnorm_partials(partial_rows: torch.Tensor, splitk: int, m_pad: int, weight
                                                            _p(out), _p(residual_out), int(rows), int(hidden), float(eps),
                                                            _stream()), "crag_enc_rmsnorm_partials")
     return out
+
+
+# -- the reranker's forward (csrc/crag_rerank.hip) --------------------------------------------------------------------
+def attention_prefixed(qkv, vt, out, cu, cu_pad, blk_seq, blk_q0, parent, hq: int, hkv: int, scale: float):
+    """attention() where a sequence may name a parent segment (parent int32 [B], -1 = root): a child's queries see all
+    of the parent's keys, then their own causally (crag_enc_attention_prefixed)."""
+    _req(qkv, torch.bfloat16, "qkv"); _req(vt, torch.bfloat16, "vt"); _req(out, torch.bfloat16, "out")
+    _req(parent, torch.int32, "parent")
+    if parent.numel() != cu.numel() - 1:
+        raise ValueError("parent needs one entry per sequence")
+    _native.check(_native.load().crag_enc_attention_prefixed(_p(qkv), _p(vt), _p(out), _p(cu), _p(cu_pad), _p(blk_seq),
+                                                             _p(blk_q0), _p(parent), blk_seq.numel(), vt.shape[-1], hq,
+                                                             hkv, float(scale), _stream()),
+                  "crag_enc_attention_prefixed")
+    return out
+
+
+def rerank_head(hidden_states, final_norm_w, rows, lm_rows, out, eps: float, delta=None):
+    """Per pair b: final RMSNorm of hidden_states[rows[b]] (+ delta), fp32 dots with lm_rows[0] ("yes") and lm_rows[1]
+    ("no"); out [n, 3] fp32 = (logit_yes, logit_no, score) (crag_enc_rerank_head)."""
+    _req(hidden_states, torch.bfloat16, "hidden_states"); _req(final_norm_w, torch.bfloat16, "final_norm_w")
+    _req(rows, torch.int64, "rows"); _req(lm_rows, torch.bfloat16, "lm_rows"); _req(out, torch.float32, "out")
+    hidden = hidden_states.shape[1]
+    if lm_rows.shape != (2, hidden) or out.shape != (rows.numel(), 3):
+        raise ValueError("lm_rows must be [2, hidden] and out [n, 3]")
+    if delta is not None:
+        _req(delta, torch.bfloat16, "delta")
+        if delta.shape != hidden_states.shape:
+            raise ValueError("delta must have the shape of hidden_states")
+    _native.check(_native.load().crag_enc_rerank_head(_p(hidden_states), _p(delta), _p(final_norm_w), _p(rows),
+                                                      _p(lm_rows), _p(out), rows.numel(), hidden, float(eps), _stream()),
+                  "crag_enc_rerank_head")
+    return out

@@ -85,6 +85,7 @@ class PackedBatch:
     max_len: int = 0          # longest sequence (host side: picks the attention kernel)
     cs_tok: Optional[torch.Tensor] = None   # the RoPE table's rows of `positions`, [T, 64, 2] fp32: set by a caller that
                                             # reuses the batch (the graph path: positions are a constant of the shape)
+    parent: Optional[torch.Tensor] = None   # int32 [B]: prefix segment of every sequence, -1 for a root (build_prefixed)
 
     @staticmethod
     def build(lengths: Sequence[int], device) -> "PackedBatch":
@@ -114,6 +115,48 @@ class PackedBatch:
         return PackedBatch(t, int(lens.size), t_pad, dev(cu), dev(cu_pad), dev(positions), dev(tok_of_pad),
                            dev(blk_seq[order]), dev(blk_q0[order]), last_tok, dev(np.arange(lens.size + 1)),
                            int(lens.max()))
+
+
+    @staticmethod
+    def build_prefixed(lengths: Sequence[int], parent: Sequence[int], device) -> "PackedBatch":
+        """The parent-aware layout of a rerank forward: segment b attends to ALL tokens of segment parent[b] (a root,
+        -1 for none) and then causally to its own.  A child's token j sits at position len(parent) + j; `last_tok` holds
+        the last rows of the segments no other segment names as its parent (the rows the head scores), in batch order.
+        q blocks are ordered longest first counting the parent's key tiles."""
+        lens = np.asarray(lengths, dtype=np.int64)
+        par = np.asarray(parent, dtype=np.int64)
+        if lens.size == 0 or (lens <= 0).any():
+            raise ValueError("every sequence needs at least one token")
+        if par.shape != lens.shape or (par < -1).any() or (par >= lens.size).any():
+            raise ValueError("parent needs one entry per sequence, each -1 or a sequence index")
+        if (par[par >= 0] == np.nonzero(par >= 0)[0]).any() or (par[par[par >= 0]] != -1).any():
+            raise ValueError("a parent must be another sequence, and a root")
+        cu = np.zeros(lens.size + 1, dtype=np.int64)
+        np.cumsum(lens, out=cu[1:])
+        padded = (lens + 31) // 32 * 32
+        cu_pad = np.zeros(lens.size + 1, dtype=np.int64)
+        np.cumsum(padded, out=cu_pad[1:])
+        t, t_pad = int(cu[-1]), int(cu_pad[-1])
+        plen = np.where(par >= 0, lens[np.maximum(par, 0)], 0)
+        seq_of_tok = np.repeat(np.arange(lens.size), lens)
+        local = np.arange(t) - cu[seq_of_tok]
+        positions = local + plen[seq_of_tok]
+        tok_of_pad = np.full(t_pad, -1, dtype=np.int64)
+        tok_of_pad[cu_pad[seq_of_tok] + local] = np.arange(t)
+        nblk = padded // 32
+        blk_seq = np.repeat(np.arange(lens.size), nblk)
+        blk_q0 = (np.arange(int(nblk.sum())) - np.repeat(np.cumsum(nblk) - nblk, nblk)) * 32
+        walk = blk_q0 + ((plen + 31) // 32 * 32)[blk_seq]   # keys walked before the diagonal tile
+        order = np.argsort(-walk, kind="stable")
+        pooled = np.setdiff1d(np.arange(lens.size), par[par >= 0])
+
+        def dev(a):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device, non_blocking=True)
+
+        last_tok = torch.from_numpy(np.ascontiguousarray(cu[1:][pooled] - 1)).to(device, non_blocking=True)
+        return PackedBatch(t, int(lens.size), t_pad, dev(cu), dev(cu_pad), dev(positions), dev(tok_of_pad),
+                           dev(blk_seq[order]), dev(blk_q0[order]), last_tok, dev(np.arange(lens.size + 1)),
+                           int(lens.max()), parent=dev(par))
 
 
 QKV_ROW_CHUNK = 32768
@@ -339,11 +382,17 @@ class Qwen3Encoder:
 
     # -- forward --------------------------------------------------------------------------------
     @torch.no_grad()
-    def forward_packed(self, ids: torch.Tensor, batch: PackedBatch) -> torch.Tensor:
-        """ids: int32 [T] on the device.  Returns unit-norm embeddings [B, out_dim] fp32."""
+    def forward_packed(self, ids: torch.Tensor, batch: PackedBatch, head: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ids: int32 [T] on the device.  Returns unit-norm embeddings [B, out_dim] fp32.
+        head (the reranker's forward): the "yes" / "no" rows of lm_head, [2, hidden] bf16, and `batch` a
+        PackedBatch.build_prefixed layout.  The forward then takes the general path (library GEMMs, qk_rope_vt, the
+        prefix-aware attention), runs the last layer on the pooled rows (batch.last_tok) only and returns
+        [len(last_tok), 3] fp32 = (logit_yes, logit_no, score) (crag_enc_rerank_head) instead of embeddings."""
         c = self.cfg
         if c.head_dim != 128:
             raise ValueError("the HIP attention / rope kernels are specialised for head_dim 128")
+        if head is not None:
+            return self._forward_rerank(ids, batch, head)
         t, dev = batch.n_tokens, self.device
         bf = torch.bfloat16
         x = torch.empty(t, c.hidden_size, dtype=bf, device=dev)
@@ -478,6 +527,59 @@ class Qwen3Encoder:
         else:
             raise ValueError(f"unknown pooling {c.pooling!r}")
         return out
+
+    @torch.no_grad()
+    def _forward_rerank(self, ids: torch.Tensor, batch: PackedBatch, head: torch.Tensor) -> torch.Tensor:
+        """forward_packed's general path for a parent-aware batch: the 16/32-row, wide and graph paths know nothing of
+        parents, so none of them (nor their weight copies) is used here."""
+        c, dev, bf = self.cfg, self.device, torch.bfloat16
+        if batch.parent is None:
+            raise ValueError("a rerank forward needs a PackedBatch.build_prefixed batch")
+        t = batch.n_tokens
+        x = torch.empty(t, c.hidden_size, dtype=bf, device=dev)
+        ops.embed_gather(ids, self.embed, x)
+        resid = torch.empty_like(x)
+        normed = torch.empty_like(x)
+        width = c.q_size + 2 * c.kv_size
+        qkv_buf = torch.zeros(t + 32, width, dtype=bf, device=dev)  # attention reads up to 31 rows past T
+        qkv = qkv_buf[:t]
+        vt = torch.empty(c.num_kv_heads, c.head_dim, batch.t_pad, dtype=bf, device=dev)
+        attn = torch.empty(t, c.q_size, dtype=bf, device=dev)
+        act = torch.empty(t, c.intermediate_size, dtype=bf, device=dev)
+        scale = 1.0 / math.sqrt(c.head_dim)
+        delta: Optional[torch.Tensor] = None
+        for i, L in enumerate(self.layers):
+            if i == 0:
+                ops.rmsnorm(x, L["ln1"], normed, c.rms_norm_eps, residual_in=None, residual_out=None)
+                resid.copy_(x)
+            else:
+                ops.rmsnorm(delta, L["ln1"], normed, c.rms_norm_eps, residual_in=resid, residual_out=resid)
+            for lo in range(0, t, QKV_ROW_CHUNK):
+                hi = min(t, lo + QKV_ROW_CHUNK)
+                torch.matmul(normed[lo:hi], L["qkv"].t(), out=qkv[lo:hi])
+            ops.qk_rope_vt(qkv_buf, L["q_norm"], L["k_norm"], self._cos_sin, batch.positions,
+                           c.num_heads, c.num_kv_heads, c.rms_norm_eps, vt, batch.tok_of_pad)
+            ops.attention_prefixed(qkv_buf, vt, attn, batch.cu, batch.cu_pad, batch.blk_seq, batch.blk_q0, batch.parent,
+                                   c.num_heads, c.num_kv_heads, scale)
+            if i == len(self.layers) - 1:
+                # last layer: only the scored rows matter behind the attention (forward_packed's pooled-rows path)
+                n = batch.last_tok.numel()
+                attn_l = attn.index_select(0, batch.last_tok)
+                resid_l = resid.index_select(0, batch.last_tok)
+                delta_l = F.linear(attn_l, L["o"])
+                normed_l = torch.empty_like(resid_l)
+                ops.rmsnorm(delta_l, L["ln2"], normed_l, c.rms_norm_eps, residual_in=resid_l, residual_out=resid_l)
+                act_l = torch.empty(n, c.intermediate_size, dtype=bf, device=dev)
+                ops.swiglu(F.linear(normed_l, L["gate_up"]), act_l)
+                delta_l = F.linear(act_l, L["down"])
+                out = torch.empty(n, 3, dtype=torch.float32, device=dev)
+                rows = torch.arange(n, dtype=torch.int64, device=dev)
+                return ops.rerank_head(resid_l, self.final_norm, rows, head, out, c.rms_norm_eps, delta=delta_l)
+            delta = F.linear(attn, L["o"])
+            ops.rmsnorm(delta, L["ln2"], normed, c.rms_norm_eps, residual_in=resid, residual_out=resid)
+            ops.swiglu(F.linear(normed, L["gate_up"]), act)
+            delta = F.linear(act, L["down"])
+        raise ValueError("a rerank forward needs at least one layer")
 
     # -- small batches: one hipGraph replay per forward ---------------------------------------------------
     # A /retrieve request embeds ONE query (/root/reference/app/retrieve.py:427).  At 16 tokens the eager forward is

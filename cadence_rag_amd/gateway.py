@@ -2,6 +2,8 @@
 EMBEDDINGS_BASE_URL at the MI355X box: `POST /embed {texts, model?} -> {embeddings, model}` and
 `GET /health` (/root/reference/P620_TRITON_QWEN3_4B_EMBEDDING_RUNBOOK.md:489-497,669-716).
 The body is served by the in-process encoder registered with embeddings.set_encoder().
+`POST /rerank {query, documents, model?} -> {scores, order, model}` is the reranker's contract
+(the reference's NVIDIA_IMMERSION_PLAN.md:93-97), served by the reranker registered with reranker.set_reranker().
 `POST /retrieve` is the reference's own route (/root/reference/app/main.py:184-186) over
 retrieve.retrieve_evidence and the backend registered with retrieve.set_backend().
 
@@ -17,6 +19,7 @@ from fastapi import FastAPI, HTTPException
 from pydantic import BaseModel, Field
 
 from . import embeddings
+from . import reranker
 from . import retrieve as _retrieve
 from .config import settings
 
@@ -60,6 +63,36 @@ def embed(req: EmbedRequest) -> EmbedResponse:
         raise HTTPException(status_code=502, detail=f"encoder returned vectors of the wrong size "
                                                     f"(expected {settings.embeddings_dim})")
     return EmbedResponse(embeddings=vectors, model=req.model or model)
+
+
+class RerankRequest(BaseModel):
+    query: str = ""
+    documents: List[str] = Field(default_factory=list)
+    model: Optional[str] = None
+
+
+class RerankResponse(BaseModel):
+    scores: List[float]
+    order: List[int]
+    model: str
+
+
+@app.post("/rerank", response_model=RerankResponse)
+def rerank(req: RerankRequest) -> RerankResponse:
+    if not req.query.strip():
+        raise HTTPException(status_code=400, detail="query must be a non-empty string")
+    if not req.documents:
+        raise HTTPException(status_code=400, detail="documents must contain at least one string")
+    rr = reranker.get_reranker()
+    if rr is None:
+        raise HTTPException(status_code=502, detail="native reranker is not loaded")
+    try:
+        with reranker._reranker_lock:
+            scores, order, model = rr.rerank(req.query.strip(), list(req.documents))
+        res = reranker._validate_result(scores, order, model, len(req.documents))
+    except Exception as exc:  # noqa: BLE001
+        raise HTTPException(status_code=502, detail=f"reranker failed: {exc}") from exc
+    return RerankResponse(scores=res.scores, order=res.order, model=req.model or res.model)
 
 
 # ---- POST /retrieve: request models field-for-field app/schemas.py:71-93 -------------------------

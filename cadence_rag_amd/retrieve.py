@@ -664,6 +664,46 @@ class _DenseState:
         return side.dense_topk if self.on else 0
 
 
+class _RerankState:
+    """What the reranker did to one request (echoed in notes when reranking is configured)."""
+
+    def __init__(self) -> None:
+        self.on = False
+        self.model_id: Optional[str] = None
+        self.error: Optional[str] = None
+        self.scored: Optional[int] = None
+
+    def apply(self, query: str, fused: Dict[str, List[Tuple[Dict[str, Any], Any, float]]]):
+        """RRF -> rerank top N -> top M, per side: the first rerank_topn_in fused rows of each side are scored in ONE
+        call (their full body column, both sides behind one shared query prefix), reordered by score (ties keep the
+        RRF order) and cut to rerank_topm_out; the score replaces the RRF score.  Fail-open like the dense lane: on
+        RerankClientError the fused lists come back as they are and the error is reported."""
+        from . import reranker as _rr
+        self.on = _rr.rerank_enabled()
+        if not self.on:
+            return fused
+        n_in, m_out = max(settings.rerank_topn_in, 0), max(settings.rerank_topm_out, 0)
+        heads = {s.table: list(fused[s.table][:n_in]) for s in _SIDES}
+        docs = [str(row[s.body] or "") for s in _SIDES for row, _, _ in heads[s.table]]
+        if not docs:
+            return fused
+        try:
+            res = _rr.rerank_texts(query, docs)
+        except _rr.RerankClientError as exc:
+            self.error = str(exc)
+            return fused
+        self.model_id, self.scored = res.model, len(docs)
+        out = dict(fused)
+        at = 0
+        for s in _SIDES:
+            rows = heads[s.table]
+            scores = res.scores[at:at + len(rows)]
+            at += len(rows)
+            keep = sorted(range(len(rows)), key=lambda i: (-scores[i], i))[:m_out]
+            out[s.table] = [(rows[i][0], rows[i][1], scores[i]) for i in keep]
+        return out
+
+
 def _gather_lanes(be: "RetrieveBackend", query: str, tokens: List[str], filters, dense: _DenseState
                   ) -> Dict[str, Dict[str, Sequence[Dict[str, Any]]]]:
     """table -> {lane name -> rows}, lanes in fusion order (bm25, tech_tokens, dense)."""
@@ -700,9 +740,9 @@ def _debug_section(lanes, dense: _DenseState) -> Dict[str, Any]:
     }
 
 
-def _retrieval_notes(tokens: List[str], dense: _DenseState) -> Dict[str, Any]:
+def _retrieval_notes(tokens: List[str], dense: _DenseState, rerank: Optional[_RerankState] = None) -> Dict[str, Any]:
     chunks, artifacts = _BY_TABLE["chunks"], _BY_TABLE["artifact_chunks"]
-    return {
+    notes = {
         "planner": dense.planner,
         "dense_topk": max(dense.topk(chunks), dense.topk(artifacts)),
         "lex_topk": chunks.bm25_topk,
@@ -719,6 +759,11 @@ def _retrieval_notes(tokens: List[str], dense: _DenseState) -> Dict[str, Any]:
         "dense_candidate_rows": dict(dense.candidates),
         "hnsw_ef_search": settings.embeddings_hnsw_ef_search if dense.on else None,
     }
+    if rerank is not None and rerank.on:   # keys of the rerank stage only when it is configured
+        notes["reranked_from"] = rerank.scored
+        notes["rerank_model_id"] = rerank.model_id
+        notes["rerank_error"] = rerank.error
+    return notes
 
 
 def retrieve_evidence(payload: RetrieveRequest, backend: Optional[RetrieveBackend] = None) -> Dict[str, Any]:
@@ -747,6 +792,8 @@ def retrieve_evidence(payload: RetrieveRequest, backend: Optional[RetrieveBacken
     dense.embed(query)
     lanes = _gather_lanes(be, query, tokens, payload.filters, dense)
     fused = {s.table: _rrf_merge(lanes[s.table], s.id_field) for s in _SIDES}
+    rerank = _RerankState()
+    fused = rerank.apply(query, fused)
 
     if ids_only:
         flat = [(-score, s.rank, row[s.id_field], s.tag) for s in _SIDES for row, _, score in fused[s.table]]
@@ -759,7 +806,7 @@ def retrieve_evidence(payload: RetrieveRequest, backend: Optional[RetrieveBacken
             cap = None if s.list_cap is None else min(s.list_cap, budget.max_evidence_items)
             packed[s.out] = _pack(fused[s.table], s, purse, cap)
         response = {**head, "intent": payload.intent, "budget": budget.model_dump(), **packed,
-                    "notes": {"retrieval": _retrieval_notes(tokens, dense)}}
+                    "notes": {"retrieval": _retrieval_notes(tokens, dense, rerank)}}
     if payload.debug:
         response["debug"] = _debug_section(lanes, dense)
     return response

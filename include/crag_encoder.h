@@ -176,6 +176,25 @@ int crag_enc_rmsnorm_partials(const float *partial_rows, int splitk, int m_pad, 
                               const uint16_t *weight, uint16_t *out, uint16_t *residual_out, int rows, int hidden,
                               float eps, void *stream);
 
+/* ---- the Qwen3-Reranker forward: csrc/crag_rerank.hip ----
+ *
+ * crag_enc_attention_prefixed: crag_enc_attention with a per-sequence parent[B] int32 (-1: a root; otherwise the index
+ *   of a ROOT sequence of the same batch, the shared prefix segment).  A child's queries attend to every key of its
+ *   parent, then causally to their own keys, under one softmax; a root is attended exactly as by crag_enc_attention.
+ *   The caller gives a child's tokens the positions plen(parent) + j.  hq / hkv = 2 or 4.  Every other input as
+ *   crag_enc_attention (blk_seq / blk_q0: the q blocks of every sequence, parents included).
+ * crag_enc_rerank_head: per pair b: x = bf16(hidden_states[rows[b]] + delta[rows[b]]) (delta nullable), the final
+ *   RMSNorm with crag_enc_pool_normalize's roundings, then fp32 dot products with lm_rows[0] ("yes") and lm_rows[1]
+ *   ("no"), lm_rows [2, hidden] bf16.  out[n_pairs, 3] fp32 = (logit_yes, logit_no, exp(log_softmax([no, yes])[1])).
+ *   hidden <= 8192. */
+int crag_enc_attention_prefixed(const uint16_t *qkv, const uint16_t *vt, uint16_t *out, const int32_t *cu_seqlens,
+                                const int32_t *cu_pad, const int32_t *blk_seq, const int32_t *blk_q0,
+                                const int32_t *parent, int n_blocks, int64_t t_pad, int hq, int hkv, float scale,
+                                void *stream);
+int crag_enc_rerank_head(const uint16_t *hidden_states, const uint16_t *delta, const uint16_t *final_norm_w,
+                         const int64_t *rows, const uint16_t *lm_rows, float *out, int n_pairs, int hidden, float eps,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif
