@@ -1,58 +1,17 @@
 // crag_encoder.hip — hand-written HIP operators of the Qwen3-Embedding encoder lane for gfx950.
 // C ABI: include/crag_encoder.h.  Everything of the decoder forward except the plain linear layers
 // (library GEMMs issued by the Python host) lives here: embedding gather, RMSNorm (+ residual),
-// per-head q/k RMSNorm + RoPE, V transpose, causal GQA flash attention (bf16 MFMA), SwiGLU, and the
-// gateway's pooling / slice / L2 normalisation.
+// per-head q/k RMSNorm + RoPE, V transpose, SwiGLU, the gateway's pooling / slice / L2 normalisation and the
+// skinny GEMM; causal GQA flash attention (bf16 MFMA) is crag_attention.hip.
 //
 // Reference math (not code): P620_TRITON_QWEN3_4B_EMBEDDING_RUNBOOK.md:683-716 for the
 // post-processing; the model family's public architecture for the layer (checked against
 // transformers' Qwen3Model in tests/test_encoder_gpu.py).
 
-#include "crag_arch.h"
-#include <hip/hip_runtime.h>
-#include <stdlib.h>
-#include <type_traits>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-
 #include "../../include/crag_encoder.h"
-
-extern "C" const char *crag_last_error(void);
-extern "C" void crag_set_error_(const char *msg);  // defined in crag_api.hip
+#include "crag_enc_common.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint16_t u16;
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-int efail(const char *fmt, ...) {
-    char buf[384];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    crag_set_error_(buf);
-    return -1;
-}
-
-int hip_ok(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[256];
-        snprintf(buf, sizeof(buf), "%s launch failed: %s", what, hipGetErrorString(e));
-        crag_set_error_(buf);
-        return -2;
-    }
-    return 0;
-}
-
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ u16 f2bf(float f) {  // round-to-nearest-even, NaN stays NaN (v_cvt_pk_bf16_f32)
-    return __builtin_bit_cast(u16, (__bf16)f);
-}
 
 struct alignas(16) Pack8 {
     u16 v[8];
@@ -79,18 +38,6 @@ __global__ __launch_bounds__(256) void embed_gather_kernel(const int32_t *ids, c
 // ---------------------------------------------------------------------------------------------
 constexpr int NORM_THREADS = 256;
 constexpr int NORM_MAX_CHUNKS = 4;  // hidden <= 8 * 256 * 4 = 8192
-
-__device__ __forceinline__ float block_sum(float v, float *sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sh[wv] = v;
-    __syncthreads();
-    float t = 0.f;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
-    __syncthreads();
-    return t;
-}
 
 __global__ __launch_bounds__(NORM_THREADS) void rmsnorm_kernel(const u16 *x, const u16 *res_in, const u16 *w,
                                                                u16 *out, u16 *res_out, int64_t rows, int hidden,
@@ -230,7 +177,7 @@ __device__ __forceinline__ void v_transpose_body(const u16 *qkv, u16 *vt, const 
     __syncthreads();
     {
         // each thread writes 16 slots (32 B) of one d row: 128 d rows x 2 halves = 256 threads.
-        // Inside a 32-slot block the slots are stored in PV-fragment order (see attention_kernel): stored
+        // Inside a 32-slot block the slots are stored in PV-fragment order (see attention_kernel, crag_attention.hip): stored
         // index 16 s2 + 8 h + 4 g + r holds slot 16 s2 + 8 g + 4 h + r, so that the 8 keys one lane feeds
         // to one PV MFMA are 16 contiguous bytes.
         const int d = threadIdx.x >> 1, half = threadIdx.x & 1;
@@ -265,420 +212,6 @@ __global__ __launch_bounds__(256) void qk_rope_vt_kernel(u16 *qkv, const u16 *qw
     } else {
         const int b = (int)blockIdx.x - rope_blocks;
         v_transpose_body(qkv, vt, tok_of_pad, t_pad, hq, hkv, b / hkv, b % hkv, tile);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// causal GQA flash attention, head_dim 128, one wave = 32 query rows of one query head.
-//   S^T = K . Q^T   (A = K tile rows, B = Q^T)   -> lane holds 16 of the 32 keys of ONE query row
-//   O^T += V^T . P^T (A = V^T tile from the transposed copy, B = P^T taken straight from the S^T
-//                     accumulator registers, bf16-packed; k order as the 32x32 C/D map gives it)
-// ---------------------------------------------------------------------------------------------
-struct AttnParams {
-    const u16 *qkv;
-    const u16 *vt;
-    u16 *out;
-    const int32_t *cu, *cu_pad, *blk_seq, *blk_q0;
-    int64_t t_pad;
-    int hq, hkv;
-    float scale_log2;
-};
-
-__device__ __forceinline__ bf16x8 ld_frag(const u16 *p) { return *reinterpret_cast<const bf16x8 *>(p); }
-
-// The 4 (hq/hkv) waves of a workgroup are the query heads of one GQA group: they need the SAME K and V
-// tiles.  Loading fragments straight from global memory uses 32 B of every 128-B line per instruction
-// and repeats the traffic per wave, which makes the kernel L1-bound; instead the workgroup stages each
-// 32-key tile once, fully coalesced, in LDS (double-buffered, one barrier per tile) and the waves read
-// their MFMA fragments from there (rows padded to 272 / 80 bytes: conflict-free ds_read_b128).
-constexpr int ATT_KROW = 136;   // u16 per staged K row (128 + 8 pad)
-constexpr int ATT_VROW = 40;    // u16 per staged V^T row (32 + 8 pad)
-
-template <int GROUP>
-__global__ __launch_bounds__(64 * GROUP) __attribute__((amdgpu_waves_per_eu(GROUP >= 2 ? 2 : 1, 8)))
-void attention_kernel(AttnParams p) {
-    // one pool: K buffers, then V^T buffers; the epilogue reuses its start for the per-wave output tiles
-    constexpr int K_BUF = 32 * ATT_KROW, V_BUF = CRAG_HEAD_DIM * ATT_VROW;
-    static_assert(GROUP * 32 * ATT_KROW <= 2 * (K_BUF + V_BUF) || GROUP > 4, "output tiles must fit the staging pool");
-    __shared__ __attribute__((aligned(16))) u16 s_pool[2 * (K_BUF + V_BUF)];
-    u16(*s_k)[K_BUF] = reinterpret_cast<u16(*)[K_BUF]>(s_pool);
-    u16(*s_v)[V_BUF] = reinterpret_cast<u16(*)[V_BUF]>(s_pool + 2 * K_BUF);
-    constexpr int nthr = 64 * GROUP;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(tid >> 6));
-    // kv head on the fast grid axis: workgroups go to the 8 XCDs round-robin by linear id, so with 8 kv heads
-    // every XCD serves ONE kv head and the q blocks that re-read a sequence's K/V tiles share that XCD's L2
-    const int kvh = blockIdx.x;
-    const int head = kvh * GROUP + wave;  // GROUP = query heads per kv head = waves per workgroup
-    const int seq = p.blk_seq[blockIdx.y];
-    const int q0 = p.blk_q0[blockIdx.y];
-    const int s_begin = p.cu[seq];
-    const int len = p.cu[seq + 1] - s_begin;
-    const int64_t pad_base = p.cu_pad[seq];
-    const int c = lane & 31, h = lane >> 5;
-    const int64_t row_stride = (int64_t)(p.hq + 2 * p.hkv) * CRAG_HEAD_DIM;
-
-    // Q^T fragments (B operand): B[k = 8h + j][col c] = Q[q0 + c][16 s + 8h + j]
-    bf16x8 qf[8];
-    {
-        const u16 *qp = p.qkv + (int64_t)(s_begin + q0 + c) * row_stride + (int64_t)head * CRAG_HEAD_DIM + 8 * h;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) qf[s] = ld_frag(qp + 16 * s);
-    }
-    const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    f32x16 oacc[4] = {zero, zero, zero, zero};
-    float m = -INFINITY, l = 0.f;
-    const int n_kt = q0 / 32 + 1;
-    const u16 *kglob = p.qkv + (int64_t)s_begin * row_stride + (int64_t)(p.hq + kvh) * CRAG_HEAD_DIM;
-    const u16 *vglob = p.vt + (int64_t)kvh * CRAG_HEAD_DIM * p.t_pad + pad_base;
-
-    // cooperative staging: the K tile is 32 rows x 16 chunks of 16 B, the V^T tile 128 rows x 4 chunks; with
-    // `nthr` threads every thread moves 512 / nthr chunks of each (nthr = 64 * group, group in {1, 2, 4, 8})
-    constexpr int per = 512 / nthr;
-    struct Stage {
-        bf16x8 k[per], v[per];
-    };
-    auto fetch = [&](int kt, Stage &st) {
-        const int k0 = kt * 32;
-#pragma unroll
-        for (int i = 0; i < per; ++i) {
-            const int ch = tid + i * nthr;
-            st.k[i] = ld_frag(kglob + (int64_t)(k0 + (ch >> 4)) * row_stride + 8 * (ch & 15));
-            st.v[i] = ld_frag(vglob + (int64_t)(ch >> 2) * p.t_pad + k0 + 8 * (ch & 3));
-        }
-    };
-    auto stash = [&](int buf, const Stage &st) {
-#pragma unroll
-        for (int i = 0; i < per; ++i) {
-            const int ch = tid + i * nthr;
-            *reinterpret_cast<bf16x8 *>(&s_k[buf][(ch >> 4) * ATT_KROW + 8 * (ch & 15)]) = st.k[i];
-            *reinterpret_cast<bf16x8 *>(&s_v[buf][(ch >> 2) * ATT_VROW + 8 * (ch & 3)]) = st.v[i];
-        }
-    };
-    Stage st;
-    fetch(0, st);
-    stash(0, st);
-    __syncthreads();
-    // empty the compiler's vmcnt scoreboard: otherwise the loop keeps conservative waits on the Q fragment
-    // loads above in every iteration and drains the prefetch issued at the top of each tile
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-
-    for (int kt = 0; kt < n_kt; ++kt) {
-        const int k0 = kt * 32, buf = kt & 1;
-        if (kt + 1 < n_kt) fetch(kt + 1, st);  // in flight during this tile's MFMAs and softmax
-        // all 8 K fragments first, then the MFMA chain: LDS latency is paid once, not per MFMA
-        bf16x8 fr[8];
-        {
-            const u16 *kp = &s_k[buf][c * ATT_KROW + 8 * h];  // A[row = key c][k = 8h + j]
-#pragma unroll
-            for (int s = 0; s < 8; ++s) fr[s] = *reinterpret_cast<const bf16x8 *>(kp + 16 * s);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        f32x16 sacc = zero;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[s], qf[s], sacc, 0, 0, 0);
-        // V^T fragments into the same registers while the softmax runs:
-        // A operand V^T[d = 32 dt + c][8 keys of (s2, h)], contiguous in the staged (PV-fragment) order
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-                fr[2 * dt + s2] = *reinterpret_cast<const bf16x8 *>(&s_v[buf][(32 * dt + c) * ATT_VROW + 8 * h + 16 * s2]);
-        __builtin_amdgcn_sched_barrier(0);
-        // lane: query row q0 + c; register i: key k0 + (i&3) + 8*(i>>2) + 4h
-        float sv[16];
-        float mloc = -INFINITY;
-        const bool diag = (kt == n_kt - 1);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int key = k0 + (i & 3) + 8 * (i >> 2) + 4 * h;
-            float v = sacc[i] * p.scale_log2;
-            if (diag && key > q0 + c) v = -INFINITY;
-            sv[i] = v;
-            mloc = fmaxf(mloc, v);
-        }
-        {  // combine the two half-waves (keys 4h..): v_permlane32_swap instead of an LDS-crossbar shuffle
-            const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(mloc), __float_as_uint(mloc), false, false);
-            mloc = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-        }
-        const float mnew = fmaxf(m, mloc);  // finite: key k0 (<= q0 + c) is never masked
-        const float alpha = __builtin_amdgcn_exp2f(m - mnew);
-        float lsum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            sv[i] = __builtin_amdgcn_exp2f(sv[i] - mnew);
-            lsum += sv[i];
-        }
-        {
-            const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(lsum), __float_as_uint(lsum), false, false);
-            lsum = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-        }
-        l = l * alpha + lsum;
-        if (__any(mnew != m)) {  // wave-uniform: once the running maxima have settled no rescale is needed
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) oacc[dt][i] *= alpha;
-        }
-        m = mnew;
-        // P^T fragments (B operand of k-step s2): element j = register 8*s2 + j
-        bf16x8 pf[2];
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) pf[s2][jj] = (short)f2bf(sv[8 * s2 + jj]);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)  // 4 independent accumulator chains
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-                oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[2 * dt + s2], pf[s2], oacc[dt], 0, 0, 0);
-        if (kt + 1 < n_kt) stash(buf ^ 1, st);  // that buffer was last read in tile kt-1, before the previous barrier
-        __syncthreads();
-    }
-    // O[q0 + c][32 dt + (i&3) + 8 (i>>2) + 4h] = oacc[dt][i] / l : 4 consecutive d per register quad
-    // O[q0 + c][32 dt + (i&3) + 8 (i>>2) + 4h] = oacc[dt][i] / l.  Stored straight from these registers a wave
-    // instruction would write 16 bytes into each of 32 rows (partial lines: 40 % of the kernel's time at
-    // 256-token chunks); instead the wave transposes its 32 x 128 tile through LDS (the K staging buffer is free
-    // after the last barrier) and writes whole 256-byte rows, 16 bytes per lane.
-    {
-        u16 *ot = s_pool + wave * (32 * ATT_KROW);
-        const float inv = 1.f / l;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                uint2 w;
-                w.x = (uint32_t)f2bf(oacc[dt][4 * g4] * inv) | ((uint32_t)f2bf(oacc[dt][4 * g4 + 1] * inv) << 16);
-                w.y = (uint32_t)f2bf(oacc[dt][4 * g4 + 2] * inv) | ((uint32_t)f2bf(oacc[dt][4 * g4 + 3] * inv) << 16);
-                *reinterpret_cast<uint2 *>(ot + c * ATT_KROW + 32 * dt + 8 * g4 + 4 * h) = w;
-            }
-        // same wave, LDS operations complete in order: no barrier between these writes and the reads below
-        u16 *obase = p.out + (int64_t)(s_begin + q0) * ((int64_t)p.hq * CRAG_HEAD_DIM) + (int64_t)head * CRAG_HEAD_DIM;
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int row = (lane >> 4) + 4 * it, chunk = lane & 15;
-            const bf16x8 v = *reinterpret_cast<const bf16x8 *>(ot + row * ATT_KROW + 8 * chunk);
-            if (q0 + row < len)
-                *reinterpret_cast<bf16x8 *>(obase + (int64_t)row * ((int64_t)p.hq * CRAG_HEAD_DIM) + 8 * chunk) = v;
-        }
-    }
-}
-
-// ---- 64 keys per iteration (GROUP >= 4): two 32-key tiles share one softmax update, one barrier and one
-// staging round, and their QK chains interleave.  A q block with an odd number of key tiles ends with a
-// half pair (HALF): only its first tile exists (its second would lie entirely above the diagonal). ----
-constexpr int ATT_VROW2 = 72;  // u16 per staged V^T row of a pair (64 + 8 pad: conflict-free b128 reads)
-
-template <int GROUP>
-__global__ __launch_bounds__(64 * GROUP) __attribute__((amdgpu_waves_per_eu(2, 8)))
-void attention_pair_kernel(AttnParams p) {
-    static_assert(GROUP >= 4, "staging is sized for at least 256 threads");
-    // one pool: K buffers, then V^T buffers; the epilogue reuses its start for the per-wave output tiles
-    constexpr int K_BUF = 64 * ATT_KROW, V_BUF = CRAG_HEAD_DIM * ATT_VROW2;
-    static_assert(GROUP * 32 * ATT_KROW <= 2 * (K_BUF + V_BUF), "output tiles must fit the staging pool");
-    __shared__ __attribute__((aligned(16))) u16 s_pool[2 * (K_BUF + V_BUF)];
-    u16(*s_k)[K_BUF] = reinterpret_cast<u16(*)[K_BUF]>(s_pool);
-    u16(*s_v)[V_BUF] = reinterpret_cast<u16(*)[V_BUF]>(s_pool + 2 * K_BUF);
-    constexpr int nthr = 64 * GROUP;
-    constexpr int per = 1024 / nthr;  // 16-byte chunks of K and of V^T per thread and pair
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(tid >> 6));
-    // kv head on the fast grid axis: workgroups go to the 8 XCDs round-robin by linear id, so with 8 kv heads
-    // every XCD serves ONE kv head and the q blocks that re-read a sequence's K/V tiles share that XCD's L2
-    const int kvh = blockIdx.x;
-    const int head = kvh * GROUP + wave;
-    const int seq = p.blk_seq[blockIdx.y];
-    const int q0 = p.blk_q0[blockIdx.y];
-    const int s_begin = p.cu[seq];
-    const int len = p.cu[seq + 1] - s_begin;
-    const int64_t pad_base = p.cu_pad[seq];
-    const int c = lane & 31, h = lane >> 5;
-    const int64_t row_stride = (int64_t)(p.hq + 2 * p.hkv) * CRAG_HEAD_DIM;
-
-    bf16x8 qf[8];
-    {
-        const u16 *qp = p.qkv + (int64_t)(s_begin + q0 + c) * row_stride + (int64_t)head * CRAG_HEAD_DIM + 8 * h;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) qf[s] = ld_frag(qp + 16 * s);
-    }
-    const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    f32x16 oacc[4] = {zero, zero, zero, zero};
-    float m = -INFINITY, l = 0.f;
-    const int n_kt = q0 / 32 + 1;          // 32-key tiles up to and including the diagonal one
-    const int n_pairs = (n_kt + 1) >> 1;
-    const bool last_half = (n_kt & 1) != 0;
-    const u16 *kglob = p.qkv + (int64_t)s_begin * row_stride + (int64_t)(p.hq + kvh) * CRAG_HEAD_DIM;
-    const u16 *vglob = p.vt + (int64_t)kvh * CRAG_HEAD_DIM * p.t_pad + pad_base;
-
-    struct Stage {
-        bf16x8 k[per], v[per];
-    };
-    // K pair: 64 rows x 16 chunks; V^T pair: 128 rows x 8 chunks.  A half pair moves only the first tile.
-    // per-thread bases computed once; chunk i and pair pr only add wave-uniform offsets
-    const u16 *kthr = kglob + (int64_t)(tid >> 4) * row_stride + 8 * (tid & 15);
-    const u16 *vthr = vglob + (int64_t)(tid >> 3) * p.t_pad + 8 * (tid & 7);
-    const int64_t kstep = (int64_t)(nthr >> 4) * row_stride, vstep = (int64_t)(nthr >> 3) * p.t_pad;
-    auto fetch = [&](int pr, bool half, Stage &st) {
-        const u16 *kp = kthr + (int64_t)(pr * 64) * row_stride;
-        const u16 *vp = vthr + pr * 64;
-#pragma unroll
-        for (int i = 0; i < per; ++i) {
-            // K rows (tid >> 4) + i * nthr / 16: the second tile's rows are i >= per / 2; V^T columns 8 * (tid & 7)
-            if (!(half && i >= per / 2)) st.k[i] = ld_frag(kp + i * kstep);
-            if (!(half && (tid & 7) >= 4)) st.v[i] = ld_frag(vp + i * vstep);
-        }
-    };
-    auto stash = [&](int buf, const Stage &st) {
-#pragma unroll
-        for (int i = 0; i < per; ++i) {
-            const int ch = tid + i * nthr;
-            *reinterpret_cast<bf16x8 *>(&s_k[buf][(ch >> 4) * ATT_KROW + 8 * (ch & 15)]) = st.k[i];
-            *reinterpret_cast<bf16x8 *>(&s_v[buf][(ch >> 3) * ATT_VROW2 + 8 * (ch & 7)]) = st.v[i];
-        }
-    };
-    Stage st;
-#pragma unroll
-    for (int i = 0; i < per; ++i) st.k[i] = st.v[i] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    fetch(0, n_pairs == 1 && last_half, st);
-    stash(0, st);
-    __syncthreads();
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // clean vmcnt scoreboard at the loop head (see attention_kernel)
-
-    // one pair of key tiles; HALF: only the first tile; DIAG: the pair's last existing tile is the diagonal one
-    auto pair = [&](int pr, auto HALF_, auto DIAG_) {
-        constexpr bool HALF = decltype(HALF_)::value, DIAG = decltype(DIAG_)::value;
-        const int k0 = pr * 64, buf = pr & 1;
-        if (pr + 1 < n_pairs) fetch(pr + 1, (pr + 2 == n_pairs) && last_half, st);
-        f32x16 sa = zero, sb = zero;
-        {
-            const u16 *kp = &s_k[buf][c * ATT_KROW + 8 * h];
-#pragma unroll
-            for (int half4 = 0; half4 < 2; ++half4) {  // 4 k-steps of both tiles per round: 8 fragments in flight
-                bf16x8 fa[4], fb[4];
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    fa[s] = *reinterpret_cast<const bf16x8 *>(kp + 16 * (4 * half4 + s));
-                    if constexpr (!HALF) fb[s] = *reinterpret_cast<const bf16x8 *>(kp + 32 * ATT_KROW + 16 * (4 * half4 + s));
-                }
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s], qf[4 * half4 + s], sa, 0, 0, 0);
-                    if constexpr (!HALF) sb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[s], qf[4 * half4 + s], sb, 0, 0, 0);
-                }
-            }
-        }
-        // V^T fragments of the first tile are requested now and arrive during the softmax
-        bf16x8 fv[8];
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-                fv[2 * dt + s2] = *reinterpret_cast<const bf16x8 *>(&s_v[buf][(32 * dt + c) * ATT_VROW2 + 8 * h + 16 * s2]);
-        __builtin_amdgcn_sched_barrier(0);
-        // lane: query row q0 + c; register i of tile t: key k0 + 32 t + (i&3) + 8*(i>>2) + 4h
-        // the softmax scale is positive, so the row maximum is taken on the raw scores and the scale is folded
-        // into the exponent's fma: p = exp2(s * scale - m), m = scale * max(s)
-        float mloc = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int key = k0 + (i & 3) + 8 * (i >> 2) + 4 * h;
-            if (DIAG && HALF && key > q0 + c) sa[i] = -INFINITY;
-            mloc = fmaxf(mloc, sa[i]);
-            if constexpr (!HALF) {
-                if (DIAG && key + 32 > q0 + c) sb[i] = -INFINITY;
-                mloc = fmaxf(mloc, sb[i]);
-            }
-        }
-        {
-            const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(mloc), __float_as_uint(mloc), false, false);
-            mloc = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-        }
-        const float mnew = fmaxf(m, mloc * p.scale_log2);  // finite: key k0 (<= q0 + c) is never masked
-        const float alpha = __builtin_amdgcn_exp2f(m - mnew);
-        float lsum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            sa[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(sa[i], p.scale_log2, -mnew));
-            lsum += sa[i];
-            if constexpr (!HALF) {
-                sb[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(sb[i], p.scale_log2, -mnew));
-                lsum += sb[i];
-            }
-        }
-        {
-            const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(lsum), __float_as_uint(lsum), false, false);
-            lsum = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-        }
-        l = l * alpha + lsum;
-        if (__any(mnew != m)) {  // wave-uniform: once the running maxima have settled no rescale is needed
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) oacc[dt][i] *= alpha;
-        }
-        m = mnew;
-        bf16x8 pa[2], pb[2];
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) {
-                pa[s2][jj] = (short)f2bf(sa[8 * s2 + jj]);
-                if constexpr (!HALF) pb[s2][jj] = (short)f2bf(sb[8 * s2 + jj]);
-            }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)  // 4 independent accumulator chains
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-                oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fv[2 * dt + s2], pa[s2], oacc[dt], 0, 0, 0);
-        if constexpr (!HALF) {
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2)
-                    fv[2 * dt + s2] = *reinterpret_cast<const bf16x8 *>(&s_v[buf][(32 * dt + c) * ATT_VROW2 + 8 * h + 32 + 16 * s2]);
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt)
-                    oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fv[2 * dt + s2], pb[s2], oacc[dt], 0, 0, 0);
-        }
-        if (pr + 1 < n_pairs) stash(buf ^ 1, st);  // that buffer was last read one barrier ago
-        __syncthreads();
-    };
-
-    for (int pr = 0; pr + 1 < n_pairs; ++pr) pair(pr, std::false_type{}, std::false_type{});
-    if (last_half) pair(n_pairs - 1, std::true_type{}, std::true_type{});
-    else pair(n_pairs - 1, std::false_type{}, std::true_type{});
-
-    // O[q0 + c][32 dt + (i&3) + 8 (i>>2) + 4h] = oacc[dt][i] / l.  Stored straight from these registers a wave
-    // instruction would write 16 bytes into each of 32 rows (partial lines: 40 % of the kernel's time at
-    // 256-token chunks); instead the wave transposes its 32 x 128 tile through LDS (the K staging buffer is free
-    // after the last barrier) and writes whole 256-byte rows, 16 bytes per lane.
-    {
-        u16 *ot = s_pool + wave * (32 * ATT_KROW);
-        const float inv = 1.f / l;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                uint2 w;
-                w.x = (uint32_t)f2bf(oacc[dt][4 * g4] * inv) | ((uint32_t)f2bf(oacc[dt][4 * g4 + 1] * inv) << 16);
-                w.y = (uint32_t)f2bf(oacc[dt][4 * g4 + 2] * inv) | ((uint32_t)f2bf(oacc[dt][4 * g4 + 3] * inv) << 16);
-                *reinterpret_cast<uint2 *>(ot + c * ATT_KROW + 32 * dt + 8 * g4 + 4 * h) = w;
-            }
-        // same wave, LDS operations complete in order: no barrier between these writes and the reads below
-        u16 *obase = p.out + (int64_t)(s_begin + q0) * ((int64_t)p.hq * CRAG_HEAD_DIM) + (int64_t)head * CRAG_HEAD_DIM;
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int row = (lane >> 4) + 4 * it, chunk = lane & 15;
-            const bf16x8 v = *reinterpret_cast<const bf16x8 *>(ot + row * ATT_KROW + 8 * chunk);
-            if (q0 + row < len)
-                *reinterpret_cast<bf16x8 *>(obase + (int64_t)row * ((int64_t)p.hq * CRAG_HEAD_DIM) + 8 * chunk) = v;
-        }
     }
 }
 
@@ -927,39 +460,6 @@ int crag_enc_qk_rope_vt(uint16_t *qkv, const uint16_t *q_norm_w, const uint16_t 
     hipLaunchKernelGGL(qk_rope_vt_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, qkv, q_norm_w, k_norm_w,
                        cos_sin, positions, n_tokens, hq, hkv, eps, vt, tok_of_pad, t_pad, rope_blocks);
     return hip_ok("qk_rope_vt");
-}
-
-int crag_enc_attention(const uint16_t *qkv, const uint16_t *vt, uint16_t *out, const int32_t *cu_seqlens,
-                       const int32_t *cu_pad, const int32_t *blk_seq, const int32_t *blk_q0, int n_blocks,
-                       int64_t t_pad, int hq, int hkv, float scale, void *stream) {
-    if (!qkv || !vt || !out || !cu_seqlens || !cu_pad || !blk_seq || !blk_q0) return efail("attention: NULL pointer");
-    if (hkv <= 0 || hq % hkv != 0 || (hq / hkv != 1 && hq / hkv != 2 && hq / hkv != 4 && hq / hkv != 8))
-        return efail("attention: hq/hkv must be 1, 2, 4 or 8");
-    if (n_blocks <= 0) return 0;
-    AttnParams p;
-    p.qkv = qkv;
-    p.vt = vt;
-    p.out = out;
-    p.cu = cu_seqlens;
-    p.cu_pad = cu_pad;
-    p.blk_seq = blk_seq;
-    p.blk_q0 = blk_q0;
-    p.t_pad = t_pad;
-    p.hq = hq;
-    p.hkv = hkv;
-    p.scale_log2 = scale * 1.4426950408889634f;
-    if (n_blocks > 65535 * 64) return efail("attention: too many q blocks (%d)", n_blocks);
-    const dim3 grid((unsigned)hkv, (unsigned)n_blocks);
-    switch (hq / hkv) {
-        case 1: hipLaunchKernelGGL(attention_kernel<1>, grid, dim3(64), 0, (hipStream_t)stream, p); break;
-        case 2: hipLaunchKernelGGL(attention_kernel<2>, grid, dim3(128), 0, (hipStream_t)stream, p); break;
-        case 4:
-            if (getenv("CRAG_ATTN_SINGLE")) hipLaunchKernelGGL(attention_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, p);
-            else hipLaunchKernelGGL(attention_pair_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, p);
-            break;
-        default: hipLaunchKernelGGL(attention_pair_kernel<8>, grid, dim3(512), 0, (hipStream_t)stream, p); break;
-    }
-    return hip_ok("attention");
 }
 
 int crag_enc_swiglu(const uint16_t *gate_up, uint16_t *out, int64_t rows, int inter, void *stream) {

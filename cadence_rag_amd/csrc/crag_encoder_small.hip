@@ -36,46 +36,12 @@
 // then * w rounded to bf16; cos/sin cast to bf16; P rounded to bf16 after an fp32 softmax) -- tests compare the
 // fused path with the unfused kernels and with transformers' Qwen3Model.
 
-#include "crag_arch.h"
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
 #include <type_traits>
 
 #include "../../include/crag_encoder.h"
-
-extern "C" void crag_set_error_(const char *msg);  // crag_api.hip
+#include "crag_enc_common.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef uint16_t u16;
-
-int efail(const char *fmt, ...) {
-    char buf[384];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    crag_set_error_(buf);
-    return -1;
-}
-
-int hip_ok(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[256];
-        snprintf(buf, sizeof(buf), "%s launch failed: %s", what, hipGetErrorString(e));
-        crag_set_error_(buf);
-        return -2;
-    }
-    return 0;
-}
-
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }
 
 struct SmallGemmParams {
     const u16 *x;       // [16 * MG, K] bf16 activations (PRO: the residual stream)

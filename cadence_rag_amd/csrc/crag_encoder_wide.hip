@@ -42,47 +42,12 @@
 // Arithmetic: bf16 operands, fp32 accumulation (MFMA), the K splits added in split order in fp32, one rounding to
 // bf16; SwiGLU with crag_enc_swiglu's roundings (bf16 gate -> silu in fp32 -> bf16 -> x bf16 up -> bf16).
 
-#include "crag_arch.h"
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 
 #include "../../include/crag_encoder.h"
-
-extern "C" void crag_set_error_(const char *msg);  // crag_api.hip
+#include "crag_enc_common.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef uint16_t u16;
-
-int wfail(const char *fmt, ...) {
-    char buf[384];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    crag_set_error_(buf);
-    return -1;
-}
-
-int whip_ok(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[256];
-        snprintf(buf, sizeof(buf), "%s launch failed: %s", what, hipGetErrorString(e));
-        crag_set_error_(buf);
-        return -2;
-    }
-    return 0;
-}
-
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }
 
 constexpr int WIDE_BK = 128;            // K granularity of the interface (chunks are 128 or 64 columns inside)
 constexpr int WIDE_THREADS = 256;       // (the reduce kernel's block)
@@ -406,12 +371,12 @@ int64_t crag_enc_wide_partial_bytes(int m_pad, int n, int splitk) {
 
 int crag_enc_wide_gemm(const uint16_t *x, const uint16_t *ww, float *partial, int m_pad, int n, int k, int splitk,
                        void *stream) {
-    if (!x || !ww || !partial) return wfail("wide_gemm: NULL pointer");
-    if (m_pad != 32 && m_pad != 64 && m_pad != 96 && m_pad != 128) return wfail("wide_gemm: m_pad must be 32, 64, 96 or 128 (got %d)", m_pad);
-    if (n <= 0 || n % 128) return wfail("wide_gemm: n must be a multiple of 128 (got %d)", n);
-    if (k <= 0 || k % WIDE_BK) return wfail("wide_gemm: k must be a multiple of %d (got %d)", WIDE_BK, k);
-    if (splitk <= 0 || splitk > k / WIDE_BK) return wfail("wide_gemm: splitk must be in [1, k / %d] (got %d)", WIDE_BK, splitk);
-    if (n % 64) return wfail("wide_gemm: n must be a multiple of 64");
+    if (!x || !ww || !partial) return efail("wide_gemm: NULL pointer");
+    if (m_pad != 32 && m_pad != 64 && m_pad != 96 && m_pad != 128) return efail("wide_gemm: m_pad must be 32, 64, 96 or 128 (got %d)", m_pad);
+    if (n <= 0 || n % 128) return efail("wide_gemm: n must be a multiple of 128 (got %d)", n);
+    if (k <= 0 || k % WIDE_BK) return efail("wide_gemm: k must be a multiple of %d (got %d)", WIDE_BK, k);
+    if (splitk <= 0 || splitk > k / WIDE_BK) return efail("wide_gemm: splitk must be in [1, k / %d] (got %d)", WIDE_BK, splitk);
+    if (n % 64) return efail("wide_gemm: n must be a multiple of 64");
     WideParams p;
     p.x = x;
     p.ww = ww;
@@ -423,16 +388,16 @@ int crag_enc_wide_gemm(const uint16_t *x, const uint16_t *ww, float *partial, in
     p.splitk = splitk;
     p.token_major = 0;
     wide_launch(p, m_pad, n, (hipStream_t)stream);
-    return whip_ok("wide_gemm");
+    return hip_ok("wide_gemm");
 }
 
 int crag_enc_wide_gemm_rows(const uint16_t *x, const uint16_t *ww, float *partial, int m_pad, int n, int k, int splitk,
                             void *stream) {
-    if (!x || !ww || !partial) return wfail("wide_gemm_rows: NULL pointer");
-    if (m_pad != 32 && m_pad != 64 && m_pad != 96 && m_pad != 128) return wfail("wide_gemm_rows: m_pad must be 32, 64, 96 or 128 (got %d)", m_pad);
-    if (n <= 0 || n % 128) return wfail("wide_gemm_rows: n must be a multiple of 128 (got %d)", n);
-    if (k <= 0 || k % WIDE_BK) return wfail("wide_gemm_rows: k must be a multiple of %d (got %d)", WIDE_BK, k);
-    if (splitk <= 0 || splitk > k / WIDE_BK) return wfail("wide_gemm_rows: splitk must be in [1, k / %d] (got %d)", WIDE_BK, splitk);
+    if (!x || !ww || !partial) return efail("wide_gemm_rows: NULL pointer");
+    if (m_pad != 32 && m_pad != 64 && m_pad != 96 && m_pad != 128) return efail("wide_gemm_rows: m_pad must be 32, 64, 96 or 128 (got %d)", m_pad);
+    if (n <= 0 || n % 128) return efail("wide_gemm_rows: n must be a multiple of 128 (got %d)", n);
+    if (k <= 0 || k % WIDE_BK) return efail("wide_gemm_rows: k must be a multiple of %d (got %d)", WIDE_BK, k);
+    if (splitk <= 0 || splitk > k / WIDE_BK) return efail("wide_gemm_rows: splitk must be in [1, k / %d] (got %d)", WIDE_BK, splitk);
     WideParams p;
     p.x = x;
     p.ww = ww;
@@ -444,15 +409,15 @@ int crag_enc_wide_gemm_rows(const uint16_t *x, const uint16_t *ww, float *partia
     p.splitk = splitk;
     p.token_major = 1;
     wide_launch(p, m_pad, n, (hipStream_t)stream);
-    return whip_ok("wide_gemm_rows");
+    return hip_ok("wide_gemm_rows");
 }
 
 int crag_enc_rmsnorm_partials(const float *partial_rows, int splitk, int m_pad, const uint16_t *residual_in,
                               const uint16_t *weight, uint16_t *out, uint16_t *residual_out, int rows, int hidden,
                               float eps, void *stream) {
-    if (!partial_rows || !residual_in || !weight || !out) return wfail("rmsnorm_partials: NULL pointer");
-    if (splitk <= 0 || rows <= 0 || rows > m_pad) return wfail("rmsnorm_partials: need splitk > 0 and 0 < rows <= m_pad");
-    if (hidden <= 0 || hidden % 4 || hidden > 4096) return wfail("rmsnorm_partials: hidden must be a multiple of 4, at most 4096");
+    if (!partial_rows || !residual_in || !weight || !out) return efail("rmsnorm_partials: NULL pointer");
+    if (splitk <= 0 || rows <= 0 || rows > m_pad) return efail("rmsnorm_partials: need splitk > 0 and 0 < rows <= m_pad");
+    if (hidden <= 0 || hidden % 4 || hidden > 4096) return efail("rmsnorm_partials: hidden must be a multiple of 4, at most 4096");
     NormPartialsParams p;
     p.partial = partial_rows;
     p.res_in = residual_in;
@@ -465,17 +430,17 @@ int crag_enc_rmsnorm_partials(const float *partial_rows, int splitk, int m_pad, 
     p.rows = rows;
     p.eps = eps;
     hipLaunchKernelGGL(rmsnorm_partials_kernel, dim3((unsigned)rows), dim3(WIDE_THREADS), 0, (hipStream_t)stream, p);
-    return whip_ok("rmsnorm_partials");
+    return hip_ok("rmsnorm_partials");
 }
 
 int crag_enc_wide_gemm_direct(const uint16_t *x, const uint16_t *ww, uint16_t *out, int m_rows, int m_pad, int n, int k,
                               int epilogue, void *stream) {
-    if (!x || !ww || !out) return wfail("wide_gemm_direct: NULL pointer");
-    if (m_pad != 32 && m_pad != 64 && m_pad != 96 && m_pad != 128) return wfail("wide_gemm_direct: m_pad must be 32, 64, 96 or 128 (got %d)", m_pad);
-    if (m_rows <= 0 || m_rows > m_pad) return wfail("wide_gemm_direct: 0 < m_rows <= m_pad");
-    if (n <= 0 || n % 128) return wfail("wide_gemm_direct: n must be a multiple of 128 (got %d)", n);
-    if (k <= 0 || k % WIDE_BK) return wfail("wide_gemm_direct: k must be a multiple of %d (got %d)", WIDE_BK, k);
-    if (epilogue != 0 && epilogue != 1) return wfail("wide_gemm_direct: epilogue must be 0 or 1");
+    if (!x || !ww || !out) return efail("wide_gemm_direct: NULL pointer");
+    if (m_pad != 32 && m_pad != 64 && m_pad != 96 && m_pad != 128) return efail("wide_gemm_direct: m_pad must be 32, 64, 96 or 128 (got %d)", m_pad);
+    if (m_rows <= 0 || m_rows > m_pad) return efail("wide_gemm_direct: 0 < m_rows <= m_pad");
+    if (n <= 0 || n % 128) return efail("wide_gemm_direct: n must be a multiple of 128 (got %d)", n);
+    if (k <= 0 || k % WIDE_BK) return efail("wide_gemm_direct: k must be a multiple of %d (got %d)", WIDE_BK, k);
+    if (epilogue != 0 && epilogue != 1) return efail("wide_gemm_direct: epilogue must be 0 or 1");
     WideParams p;
     p.x = x;
     p.ww = ww;
@@ -489,16 +454,16 @@ int crag_enc_wide_gemm_direct(const uint16_t *x, const uint16_t *ww, uint16_t *o
     p.splitk = 1;
     p.token_major = 0;
     wide_launch(p, m_pad, n, (hipStream_t)stream);
-    return whip_ok("wide_gemm_direct");
+    return hip_ok("wide_gemm_direct");
 }
 
 int crag_enc_wide_reduce(const float *partial, uint16_t *out, int m_rows, int m_pad, int n, int splitk, int epilogue,
                          void *stream) {
-    if (!partial || !out) return wfail("wide_reduce: NULL pointer");
-    if (m_pad != 32 && m_pad != 64 && m_pad != 96 && m_pad != 128) return wfail("wide_reduce: m_pad must be 32, 64, 96 or 128 (got %d)", m_pad);
-    if (m_rows <= 0 || m_rows > m_pad) return wfail("wide_reduce: 0 < m_rows <= m_pad");
-    if (n <= 0 || n % 128 || splitk <= 0) return wfail("wide_reduce: bad sizes n=%d splitk=%d", n, splitk);
-    if (epilogue != 0 && epilogue != 1) return wfail("wide_reduce: epilogue must be 0 or 1");
+    if (!partial || !out) return efail("wide_reduce: NULL pointer");
+    if (m_pad != 32 && m_pad != 64 && m_pad != 96 && m_pad != 128) return efail("wide_reduce: m_pad must be 32, 64, 96 or 128 (got %d)", m_pad);
+    if (m_rows <= 0 || m_rows > m_pad) return efail("wide_reduce: 0 < m_rows <= m_pad");
+    if (n <= 0 || n % 128 || splitk <= 0) return efail("wide_reduce: bad sizes n=%d splitk=%d", n, splitk);
+    if (epilogue != 0 && epilogue != 1) return efail("wide_reduce: epilogue must be 0 or 1");
     WideReduceParams p;
     p.partial = partial;
     p.out = out;
@@ -510,7 +475,7 @@ int crag_enc_wide_reduce(const float *partial, uint16_t *out, int m_rows, int m_
     p.epilogue = epilogue;
     const int items = p.n32 * p.mg_count;
     hipLaunchKernelGGL(wide_reduce_kernel, dim3((unsigned)((items + 3) / 4)), dim3(WIDE_THREADS), 0, (hipStream_t)stream, p);
-    return whip_ok("wide_reduce");
+    return hip_ok("wide_reduce");
 }
 
 }  // extern "C"

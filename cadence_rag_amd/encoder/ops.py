@@ -276,7 +276,7 @@ def rmsnorm_partials(partial_rows: torch.Tensor, splitk: int, m_pad: int, weight
     return out
 
 
-# -- the reranker's forward (csrc/crag_rerank.hip) --------------------------------------------------------------------
+# -- the reranker's forward (csrc/crag_attention.hip, csrc/crag_rerank.hip) ------------------------------------------
 def attention_prefixed(qkv, vt, out, cu, cu_pad, blk_seq, blk_q0, parent, hq: int, hkv: int, scale: float):
     """attention() where a sequence may name a parent segment (parent int32 [B], -1 = root): a child's queries see all
     of the parent's keys, then their own causally (crag_enc_attention_prefixed)."""

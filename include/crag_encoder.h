@@ -176,7 +176,7 @@ int crag_enc_rmsnorm_partials(const float *partial_rows, int splitk, int m_pad, 
                               const uint16_t *weight, uint16_t *out, uint16_t *residual_out, int rows, int hidden,
                               float eps, void *stream);
 
-/* ---- the Qwen3-Reranker forward: csrc/crag_rerank.hip ----
+/* ---- the Qwen3-Reranker forward: csrc/crag_attention.hip (attention), csrc/crag_rerank.hip (head) ----
  *
  * crag_enc_attention_prefixed: crag_enc_attention with a per-sequence parent[B] int32 (-1: a root; otherwise the index
  *   of a ROOT sequence of the same batch, the shared prefix segment).  A child's queries attend to every key of its
