@@ -466,6 +466,7 @@ struct crag_upload_slot {
     hipEvent_t copied = nullptr;
     bool pending = false;
     int device = 0;
+    size_t bytes = 0;       // of host and dev each (grows on demand: crag_upload_slot_begin_)
 };
 namespace {
 constexpr size_t SLOT_QT_BYTES = (size_t)TECH_MAX_Q * 32 * sizeof(uint64_t);
@@ -488,7 +489,55 @@ extern "C" crag_upload_slot *crag_upload_slot_create(void) {
         return nullptr;
     }
     memset(s->host, 0, SLOT_BYTES);
+    s->bytes = SLOT_BYTES;
     return s;
+}
+
+// For the other lanes of the library that upload through a slot (crag_bm25_lane_host): wait until the slot's previous
+// copy has left the pinned buffer, make both buffers at least `bytes` large (a reallocation only when a call needs more
+// than any call before it; hipFree waits for the kernels that may still read the old device twin) and hand them out.
+extern "C" int crag_upload_slot_begin_(crag_upload_slot *s, size_t bytes, void **host, void **dev) {
+    if (!s) return ffail("upload_slot: NULL slot");
+    if (s->pending) {
+        if (hipEventSynchronize(s->copied) != hipSuccess) return ffail("upload_slot: waiting for the previous copy failed");
+        s->pending = false;
+    }
+    if (bytes > s->bytes) {
+        size_t want = s->bytes * 2 > bytes ? s->bytes * 2 : bytes;
+        void *h = nullptr, *d = nullptr;
+        int cur = 0;
+        (void)hipGetDevice(&cur);
+        (void)hipSetDevice(s->device);
+        const bool ok = hipHostMalloc(&h, want, hipHostMallocDefault) == hipSuccess && hipMalloc(&d, want) == hipSuccess;
+        if (ok) {
+            (void)hipHostFree(s->host);
+            (void)hipFree(s->dev);
+            s->host = h;
+            s->dev = d;
+            s->bytes = want;
+        } else {
+            if (h) (void)hipHostFree(h);
+        }
+        (void)hipSetDevice(cur);
+        if (!ok) {
+            crag_set_error_("upload_slot: growing the slot failed");
+            return CRAG_ENOMEM;
+        }
+    }
+    *host = s->host;
+    *dev = s->dev;
+    return CRAG_OK;
+}
+
+// ONE host-to-device copy of the first `bytes` of the slot on `stream`, and the event that frees the pinned buffer.
+extern "C" int crag_upload_slot_commit_(crag_upload_slot *s, size_t bytes, void *stream) {
+    if (hipMemcpyAsync(s->dev, s->host, bytes, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess ||
+        hipEventRecord(s->copied, (hipStream_t)stream) != hipSuccess) {
+        crag_set_error_("upload_slot: upload failed");
+        return CRAG_EHIP;
+    }
+    s->pending = true;
+    return CRAG_OK;
 }
 
 extern "C" void crag_upload_slot_destroy(crag_upload_slot *s) {

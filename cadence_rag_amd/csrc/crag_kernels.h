@@ -157,4 +157,31 @@ hipError_t launch_check_ids(const int64_t *ids, int64_t n, int64_t prev, unsigne
                             hipStream_t st);
 hipError_t launch_fill_ids(int64_t *ids, int64_t pos, int64_t n, int64_t first, hipStream_t st);
 
+// ---- BM25 lexical lane (crag_bm25.hip) ----
+constexpr int BM25_RANGE = 16384;             // row positions per workgroup: their fp32 accumulators fill 64 KiB of LDS
+constexpr int BM25_MAX_Q = 64;
+
+struct Bm25Params {
+    const int64_t *post_ptr;    // [V + 1] postings of term t: [post_ptr[t], post_ptr[t + 1])
+    const int32_t *post_pos;    // [nnz] row positions, ascending inside a term
+    const uint16_t *post_tf;    // [nnz]
+    const int32_t *doc_len;     // [n]
+    const int64_t *ids;         // [n], nullable (ids = positions)
+    const int32_t *q_ptr;       // [nq + 1] terms of query q: [q_ptr[q], q_ptr[q + 1])
+    const int32_t *q_term;      // term ids, strictly ascending inside a query
+    const float *q_w;           // qtf * idf * (k1 + 1)
+    const uint32_t *mask;       // nullable
+    int64_t mask_stride_w;      // words between the masks of consecutive queries (0: shared)
+    uint64_t *part_keys;        // [nq][n_ranges][k] (score bits << 32) | ~position, best first
+    int32_t *part_cnt;          // [nq][n_ranges]
+    int64_t n;
+    int n_ranges, nq, k;
+    float avgdl;
+    int64_t *out_ids;
+    float *out_scores;
+    int32_t *out_counts;
+};
+int64_t bm25_scratch_bytes(int64_t n_rows, int nq, int k);
+hipError_t launch_bm25(const Bm25Params &p, hipStream_t st);
+
 }  // namespace crag

@@ -293,12 +293,14 @@ class TechTokenIndex:
 class HybridSearcher:
     """The candidate stage of retrieve_evidence (/root/reference/app/retrieve.py:437-545) for a BATCH of up
     to 64 queries over one table, with every lane and the fusion on the device and no host round trip in
-    between: dense top-`dense_k` (exact cosine scan), exact-token top-`tech_k`, caller-supplied BM25 ids
-    (pg_search's ranking is an input, as it is to _rrf_merge), fused by reciprocal rank in the reference's
-    lane order bm25 -> tech_tokens -> dense."""
+    between: dense top-`dense_k` (exact cosine scan), exact-token top-`tech_k`, BM25 -- either caller-supplied
+    ids (pg_search's ranking as an input, as it is to _rrf_merge) or the native lane's top-`bm25_k`
+    (cadence_rag_amd.bm25.Bm25Index, non-parity) --, fused by reciprocal rank in the reference's lane order
+    bm25 -> tech_tokens -> dense."""
 
     def __init__(self, index, tech_index: "TechTokenIndex | None" = None, *, dense_k: int = 50, tech_k: int = 50,
-                 rrf_k: int = DEFAULT_RRF_K, verify_tokens: bool = False, overlap_lanes: bool = True) -> None:
+                 rrf_k: int = DEFAULT_RRF_K, verify_tokens: bool = False, overlap_lanes: bool = True,
+                 bm25_index=None, bm25_k: int = 50) -> None:
         """verify_tokens: run the exact-token lane's host-side string check (a blocking D2H copy per step); off by
         default so that a step only enqueues work on the caller's stream.
         overlap_lanes: run the exact-token lane on a side stream beside the dense search (forked from the caller's
@@ -311,14 +313,17 @@ class HybridSearcher:
         self.verify_tokens = bool(verify_tokens)
         self.overlap_lanes = bool(overlap_lanes)
         self.dense_k, self.tech_k, self.rrf_k = int(dense_k), int(tech_k), int(rrf_k)
+        self.bm25_index, self.bm25_k = bm25_index, int(bm25_k)
         self._dense_out: dict = {}  # per (stream, batch size): results of calls on different streams stay apart
         self._fused_out: dict = {}  # per (stream, batch size, out_k): the fusion's outputs
         self._side: dict = {}       # per caller stream: (side stream, fork event, join event)
 
     def search(self, query_vectors: torch.Tensor, query_token_lists=None, bm25=None, *, out_k: int = 0,
-               row_mask=None, mask_stride: int = 0, stream: int = 0) -> Dict[str, torch.Tensor]:
+               row_mask=None, mask_stride: int = 0, stream: int = 0, query_texts=None) -> Dict[str, torch.Tensor]:
         """query_vectors [nq, dim] fp32 CUDA; query_token_lists: per query its extract_tech_tokens();
-        bm25: (ids int64 [nq, w] CUDA, counts int32 [nq] CUDA) or None; row_mask: packed bits per row
+        bm25: (ids int64 [nq, w] CUDA, counts int32 [nq] CUDA) or None; query_texts: the query strings -- with a
+        `bm25_index` the native BM25 lane runs on them on `stream` behind the dense search and enters the fusion
+        first ("bm25_ids", "bm25_scores", "bm25_counts" in the result); a `bm25` given as well wins; row_mask: packed bits per row
         position (uint8 CUDA), shared (mask_stride 0) or per query.  Returns rrf_fuse's dict plus the dense
         lane itself ("dense_ids", "dense_scores", "dense_counts").  Everything is enqueued on `stream` (token
         lists longer than 32 tokens and verify_tokens=True are the exceptions: both visit the host); the
@@ -351,6 +356,11 @@ class HybridSearcher:
                                          stream=side.cuda_stream, verify=False, borrow=True)
             join.record(side)
         lanes = []
+        bm25_native = None
+        if bm25 is None and self.bm25_index is not None and query_texts is not None:
+            bm25_native = self.bm25_index.search(query_texts, self.bm25_k, row_mask=row_mask, mask_stride=mask_stride,
+                                                 stream=stream)
+            bm25 = (bm25_native[0], bm25_native[2])
         if bm25 is not None:
             lanes.append(bm25)
         if tech_lane is not None:
@@ -373,4 +383,6 @@ class HybridSearcher:
                     "counts": torch.empty(nq, dtype=torch.int32, device=dev)}
         out = dict(rrf_fuse(lanes, out_k=ok, rrf_k=self.rrf_k, stream=stream, out=fused))
         out["dense_ids"], out["dense_scores"], out["dense_counts"] = d_ids, d_sc, d_ct
+        if bm25_native is not None:
+            out["bm25_ids"], out["bm25_scores"], out["bm25_counts"] = bm25_native
         return out

@@ -376,6 +376,36 @@ class DenseTable:
         lane.table_generation = self.generation
         return lane
 
+    def build_bm25_lane(self, text_column: str):
+        """GPU BM25 lane (cadence_rag_amd.bm25.Bm25Index, non-parity with pg_search) over this table's
+        `text_column` -- "text" for chunks, "content" for artifact_chunks (retrieve.py:141,173).  Row i <-> position i,
+        so `filter_mask` serves this lane as it serves the other two.  The lane remembers the column and the table
+        generation it was built for: `sync_bm25_lane` brings a stale one up to date."""
+        import torch
+
+        from .bm25 import Bm25Index
+        if text_column not in self.columns and len(self):
+            raise ValueError(f"{self.name} has no column {text_column!r}")
+        lane = Bm25Index(self.columns.get(text_column, []), np.asarray(self.columns.get(self.id_field, []), dtype=np.int64),
+                         torch.device("cuda", self.index.device))
+        lane.text_column = text_column
+        lane.table_generation = self.generation
+        return lane
+
+    def sync_bm25_lane(self, lane):
+        """The lane for the table as it is now: unchanged when it is current, grown with `extend` (only the new rows
+        are tokenised) when rows were appended behind the ones it holds, rebuilt when rows moved (`insert`)."""
+        if getattr(lane, "table_generation", None) == self.generation and len(lane) == len(self):
+            return lane
+        ids = np.asarray(self.columns.get(self.id_field, []), dtype=np.int64)
+        held = len(lane)
+        if held <= ids.size and np.array_equal(ids[:held], lane.ids):
+            if held < ids.size:
+                lane.extend(self.columns[lane.text_column][held:], ids[held:])
+            lane.table_generation = self.generation
+            return lane
+        return self.build_bm25_lane(lane.text_column)
+
     def _positions(self) -> Dict[int, int]:
         if getattr(self, "_pos_of_id", None) is None:
             self._pos_of_id = {int(v): i for i, v in enumerate(self.columns[self.id_field])}
@@ -492,8 +522,10 @@ class RetrieveBackend:
 
 class GpuRetrieveBackend(RetrieveBackend):
     """Dense lanes from the HBM-resident DenseTables, exact-token lanes from GPU TechTokenIndex objects
-    (cadence_rag_amd.fusion) when attached, BM25 lanes from injected callables (pg_search's arithmetic
-    is not in the reference repository: its rows are an input here, as they are to _rrf_merge)."""
+    (cadence_rag_amd.fusion) when attached.  BM25 lanes: `bm25_chunks` / `bm25_artifacts` are either callables
+    (query, filters, call_ids, limit) -> rows -- pg_search's own rows as an input, as they are to _rrf_merge -- or
+    native lanes (cadence_rag_amd.bm25.Bm25Index from DenseTable.build_bm25_lane: a self-defined BM25, not parity
+    with pg_search, whose arithmetic is not in the reference repository)."""
 
     def __init__(self, chunks: DenseTable, artifact_chunks: DenseTable, *, calls: Sequence[Dict[str, Any]] = (),
                  bm25_chunks=None, bm25_artifacts=None, tech_chunks=None, tech_artifacts=None) -> None:
@@ -505,13 +537,37 @@ class GpuRetrieveBackend(RetrieveBackend):
     def resolve_call_ids(self, filters):
         return _resolve_call_ids(self.calls, filters)
 
+    def _bm25_rows(self, name, select, query, filters, call_ids, limit):
+        """retrieve.py:123-180: the SELECTed columns + `score`, best first."""
+        fn, table = self._bm25[name], self.tables[name]
+        if fn is None:
+            return []
+        if callable(fn):
+            return list(fn(query, filters, call_ids, limit))
+        if len(table) == 0 or int(limit) <= 0:
+            return []
+        import torch
+        lane = self._bm25[name] = table.sync_bm25_lane(fn)
+        mask = table.filter_mask(filters, call_ids)
+        d_mask = None
+        if mask is not None:
+            d_mask = torch.from_numpy(DenseIndex.pack_mask(mask)).to(lane.device)
+        ids, scores, counts = lane.search([query], min(int(limit), _native_max_k()), row_mask=d_mask, mask_stride=0)
+        n = int(counts[0])
+        pos_of = table._positions()
+        out = []
+        for rid, sc in zip(ids[0, :n].tolist(), scores[0, :n].tolist()):
+            pos = pos_of[int(rid)]
+            row = {col: table.columns[col][pos] for col in select}
+            row["score"] = float(sc)
+            out.append(row)
+        return out
+
     def fetch_chunks_bm25(self, query, filters, call_ids, limit):
-        fn = self._bm25["chunks"]
-        return list(fn(query, filters, call_ids, limit)) if fn else []
+        return self._bm25_rows("chunks", CHUNK_SELECT, query, filters, call_ids, limit)
 
     def fetch_artifacts_bm25(self, query, filters, call_ids, limit):
-        fn = self._bm25["artifact_chunks"]
-        return list(fn(query, filters, call_ids, limit)) if fn else []
+        return self._bm25_rows("artifact_chunks", ARTIFACT_SELECT, query, filters, call_ids, limit)
 
     def _tech_rows(self, name, select, tokens, filters, call_ids, limit):
         lane, table = self._tech[name], self.tables[name]

@@ -193,6 +193,35 @@ int crag_tech_lane_host(const int32_t *d_order, const int64_t *d_row_ptr, const 
                         crag_upload_slot *slot, uint64_t *d_bitmap_scratch, int64_t *d_out_ids, int32_t *d_out_counts,
                         void *stream);
 
+/* BM25 lexical lane for a batch of up to 64 queries (hybrid /retrieve, and the reference's lexical-only mode).
+ * Stands in for: _fetch_chunks_bm25 / _fetch_artifacts_bm25 (retrieve.py:123-180) -- `text @@@ :query` ordered by
+ * pdb.score(id) DESC LIMIT k over the pg_search index.  NOT parity with pg_search: Tantivy's arithmetic is not in the
+ * reference tree; this is a self-defined restatement of the published form it uses (DESIGN.md 4.7 lists the departures):
+ *   score(row) = sum over the query's terms t, ascending term id, of w_t * tf / (tf + k1 * (1 - b + b * dl / avgdl)),
+ *   k1 = 1.2, b = 0.75, w_t = qtf * ln(1 + (N - df + 0.5) / (df + 0.5)) * (k1 + 1) computed by the caller in fp64 and
+ *   rounded once to fp32; the rest is fp32 on the device, one rounding per operation, in that fixed order.
+ * The index is an inverted CSR the caller keeps on the device (cadence_rag_amd.bm25.Bm25Index builds it):
+ *   d_post_ptr [n_terms + 1] int64, d_post_pos [nnz] int32 row positions ascending inside a term, d_post_tf [nnz]
+ *   uint16 (saturated), d_doc_len [n_rows] int32, d_ids [n_rows] ascending with the position (NULL: ids = positions).
+ * The queries come from the HOST in CSR form: h_q_ptr [nq + 1] int32 (h_q_ptr[0] = 0), per query its term ids
+ * (strictly ascending, inside [0, n_terms)) and their weights -- any number of terms per query.  A query without terms
+ * returns nothing.  Only rows that hold at least one of the query's terms are returned (OR semantics; score > 0).
+ *   d_row_mask / mask_stride as in crag_index_search (bit per row POSITION; nullable)
+ *   slot       an upload slot as for crag_tech_lane_host (ONE host-to-device copy per call; it grows when a call needs more)
+ *   d_scratch  crag_bm25_scratch_bytes(n_rows, nq, k) bytes, 8-byte aligned, owned by the caller, one per stream in use
+ *   outputs    as crag_index_search: d_out_ids [nq, k] (-1 pad), d_out_scores [nq, k] fp32 (NaN pad), d_out_counts [nq]
+ * Order: descending score, equal scores by ascending id.  Everything is enqueued on `stream`; results do not depend on
+ * the launch geometry (same bits for the same (tf..., dl) whatever nq, k or the row's position).
+ * CRAG_EINVAL: NULL pointer, nq > 64, k > CRAG_MAX_K, n_rows >= 2^31, bad q_ptr / term ids / weights / mask_stride,
+ * scratch too small -- nothing was enqueued. */
+int64_t crag_bm25_scratch_bytes(int64_t n_rows, int nq, int k);
+int crag_bm25_lane_host(const int64_t *d_post_ptr, const int32_t *d_post_pos, const uint16_t *d_post_tf,
+                        const int32_t *d_doc_len, const int64_t *d_ids, int64_t n_rows, int64_t n_terms, float avgdl,
+                        const int32_t *h_q_ptr, const int32_t *h_term_ids, const float *h_weights, int nq, int k,
+                        const uint8_t *d_row_mask, int64_t mask_stride, crag_upload_slot *slot, void *d_scratch,
+                        int64_t scratch_bytes, int64_t *d_out_ids, float *d_out_scores, int32_t *d_out_counts,
+                        void *stream);
+
 /* Live kernel timing for bench.py's roofline: enabled = N > 0 records HIP events around the scan
  * (and merge) kernel of every N-th search, on the stream it is launched on (N = 1: every search;
  * larger N perturbs the timed region less); 0 disables.  crag_index_profile_read sums and clears
