@@ -233,7 +233,8 @@ extern "C" int crag_rrf_fuse(int n_lanes, const int64_t *const *d_lane_ids, cons
     FuseParams p;
     int total = 0;
     for (int l = 0; l < n_lanes; ++l) {
-        if (!d_lane_ids[l] || !d_lane_counts[l] || lane_width[l] < 0) return ffail("rrf_fuse: bad lane");
+        // (a lane of width 0 has no keys to point to -- an empty tensor's address is NULL -- and the kernel reads none)
+        if ((!d_lane_ids[l] && lane_width[l] != 0) || !d_lane_counts[l] || lane_width[l] < 0) return ffail("rrf_fuse: bad lane");
         p.lane_ids[l] = d_lane_ids[l];
         p.lane_counts[l] = d_lane_counts[l];
         p.width[l] = lane_width[l];
@@ -412,6 +413,12 @@ __global__ __launch_bounds__(256) void tech_select_kernel(TechParams p) {
     }
 }
 
+// The kernels index the mask in 32-bit words (mask_stride / 4 per query): a stride that is not a whole number of words,
+// or shorter than one row of bits, would silently read other queries' bits.
+bool tech_mask_stride_ok(const uint8_t *d_row_mask, int64_t mask_stride, int64_t n_rows) {
+    return !d_row_mask || mask_stride == 0 || (mask_stride % 4 == 0 && mask_stride >= (n_rows + 31) / 32 * 4);
+}
+
 }  // namespace
 
 extern "C" int crag_tech_lane(const int32_t *d_order, const int64_t *d_row_ptr, const uint64_t *d_tokens,
@@ -423,6 +430,8 @@ extern "C" int crag_tech_lane(const int32_t *d_order, const int64_t *d_row_ptr, 
         !d_out_ids || !d_out_counts)
         return ffail("tech_lane: NULL pointer");
     if (nq < 0 || nq > TECH_MAX_Q || k <= 0 || n_rows < 0) return ffail("tech_lane: need 0 <= nq <= 64, k > 0");
+    if (!tech_mask_stride_ok(d_row_mask, mask_stride, n_rows))
+        return ffail("tech_lane: mask_stride must be 0 or a multiple of 4 >= ceil(n_rows/32)*4");
     if (nq == 0) return CRAG_OK;
     TechParams p;
     p.order = d_order;
@@ -556,6 +565,8 @@ extern "C" int crag_tech_lane_host(const int32_t *d_order, const int64_t *d_row_
                                    int64_t *d_out_ids, int32_t *d_out_counts, void *stream) {
     if (!slot || !h_token_counts || (!h_token_hashes && nq > 0)) return ffail("tech_lane_host: NULL pointer");
     if (nq < 0 || nq > TECH_MAX_Q) return ffail("tech_lane_host: need 0 <= nq <= 64");
+    if (n_rows >= 0 && !tech_mask_stride_ok(d_row_mask, mask_stride, n_rows))   // (before the upload: nothing is enqueued)
+        return ffail("tech_lane_host: mask_stride must be 0 or a multiple of 4 >= ceil(n_rows/32)*4");
     if (nq == 0) return CRAG_OK;
     if (slot->pending) {   // the copy that last read the pinned buffer has left it
         if (hipEventSynchronize(slot->copied) != hipSuccess) return ffail("tech_lane_host: waiting for the upload slot failed");

@@ -153,8 +153,8 @@ int crag_merge_topk_packed(int device, const void *d_records, int n_lists, int n
 /* Reciprocal-rank fusion of up to 8 retrieval lanes on the GPU (hybrid /retrieve, BASELINE configs[4]).
  * Replaces: _rrf_merge (retrieve.py:245-260) — score += 1/(rrf_k + rank) per lane in lane order (fp64,
  * bit-identical to the Python floats), stable descending order (ties keep first-insertion order).
- *   d_lane_ids[l]    device [nq, lane_width[l]] int64 keys of lane l, best first
- *   d_lane_counts[l] device [nq] valid entries per query
+ *   d_lane_ids[l]    device [nq, lane_width[l]] int64 keys of lane l, best first (may be NULL when lane_width[l] is 0)
+ *   d_lane_counts[l] device [nq] valid entries per query (clamped to [0, lane_width[l]])
  *   outputs          [nq, out_k]: fused keys (-1 pad), fp64 scores (NaN pad), lane-hit bit masks; [nq] counts
  * The pointer arrays themselves live on the HOST. */
 int crag_rrf_fuse(int n_lanes, const int64_t *const *d_lane_ids, const int32_t *const *d_lane_counts,
@@ -163,13 +163,15 @@ int crag_rrf_fuse(int n_lanes, const int64_t *const *d_lane_ids, const int32_t *
 
 /* Exact-token lane for a batch of up to 64 queries (hybrid /retrieve).  Replaces: _fetch_chunks_tech /
  * _fetch_artifacts_tech (retrieve.py:183-242): rows whose token set overlaps the query's, first k in
- * the order (call_started_at DESC, id ASC).  Tokens are 64-bit hashes of the exact token strings.
+ * the order (call_started_at DESC, id ASC).  Tokens are 64-bit hashes of the exact token strings; the value 0 marks
+ * an empty table slot inside the kernel, so hashes 0 and 1 are ONE token to the lane (on the row and the query side).
  *   d_order [n] int32   row position at each rank r of that static order
  *   d_row_ptr [n+1] int64, d_tokens [nnz] uint64   CSR of the rows' token hashes, stored BY RANK
  *                       (CSR row r = the row at position d_order[r]) so the scan streams coalesced
  *   d_query_tokens [nq, 32] uint64, d_query_token_counts [nq] int32 (<= 32 tokens per query)
- *   d_row_mask as in crag_index_search (bit per row POSITION; nullable)
- *   d_bitmap_scratch [ceil(n/64) * nq] uint64
+ *   d_row_mask as in crag_index_search (bit per row POSITION; nullable); with a mask, mask_stride is 0 (shared) or a
+ *                       multiple of 4 >= ceil(n_rows/32)*4 -- CRAG_EINVAL otherwise, nothing is enqueued
+ *   d_bitmap_scratch [max(1, ceil(n/64)) * nq] uint64
  *   d_out_ids [nq, k] (-1 pad), d_out_counts [nq] */
 int crag_tech_lane(const int32_t *d_order, const int64_t *d_row_ptr, const uint64_t *d_tokens,
                    const int64_t *d_ids, int64_t n_rows, const uint64_t *d_query_tokens,
