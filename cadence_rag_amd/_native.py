@@ -29,6 +29,9 @@ SIGNATURES = {
     "crag_index_destroy": (_c.c_int, [_P]),
     "crag_index_add": (_c.c_int, [_P, _P, _P, _c.c_int64]),
     "crag_index_update": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64]),
+    "crag_index_remove": (_c.c_int, [_P, _P, _c.c_int64, _c.POINTER(_c.c_int64)]),
+    "crag_index_compact": (_c.c_int, [_P, _P, _c.POINTER(_c.c_int64)]),
+    "crag_index_insert": (_c.c_int, [_P, _P, _P, _c.c_int64]),
     "crag_index_size": (_c.c_int64, [_P]),
     "crag_index_capacity": (_c.c_int64, [_P]),
     "crag_index_dim": (_c.c_int, [_P]),

@@ -130,6 +130,11 @@ struct crag_index {
     unsigned long long *phase_trace = nullptr;  // device, 128 words; only with CRAG_PHASE_TRACE=1 (developer probe)
     const char *last_scan_kernel = "";  // name of the scan kernel the most recent search launched
     DevBuf stage_q, stage_rows, stage_ids, stage_mask, stage_out, scratch;
+    // in-place edits (crag_index_remove / compact / insert): destination rows per chunk (CRAG_EDIT_CHUNK_ROWS; the default
+    // keeps the bounce buffer, 6 156 bytes per row, below 128 MiB), the bounce buffer (held only during an edit), the
+    // chunk's source positions, the keep mask + its popcount prefix, the new rows' positions
+    int64_t edit_chunk_rows = 16384;
+    DevBuf edit_bounce, edit_srcpos, edit_mask, edit_prefix, edit_newpos;
     std::mutex mu;
     int pass_parity = 0;  // alternate scan direction between searches (Infinity Cache reuse)
     int64_t env_fail_after_scan = 0;  // CRAG_TEST_FAIL_AFTER_SCAN=n (tests): the n-th prefilter search returns CRAG_EHIP
@@ -546,6 +551,10 @@ int crag_index_create(int device, int dim, int64_t capacity, crag_index **out) {
         const int n = atoi(v);
         if (n >= 1 && n <= crag_index::MAX_PIPE) ix->n_pipe = n;
     }
+    if (const char *v = getenv("CRAG_EDIT_CHUNK_ROWS")) {   // developer switch: tests cross chunk boundaries on small tables
+        const long long c = atoll(v);
+        if (c >= 32 && c % 32 == 0 && c <= ((long long)1 << 24)) ix->edit_chunk_rows = c;
+    }
     if (const char *v = getenv("CRAG_PF_NT_ABOVE_MB")) ix->nt_above_bytes = (int64_t)atoll(v) << 20;
     if (!ix->env_no_prefilter && getenv("CRAG_NO_FP16_MIRROR") == nullptr) {
         // + 2 KiB per row beside the 4 KiB fp32 row: the prefilter scan then streams half the bytes.  Padding rows
@@ -624,6 +633,11 @@ int crag_index_destroy(crag_index *ix) {
     ix->stage_mask.release();
     ix->stage_out.release();
     ix->scratch.release();
+    ix->edit_bounce.release();
+    ix->edit_srcpos.release();
+    ix->edit_mask.release();
+    ix->edit_prefix.release();
+    ix->edit_newpos.release();
     delete ix;
     return CRAG_OK;
 }
@@ -649,7 +663,7 @@ static int store_rows_locked(crag_index *ix, int64_t pos, const float *rows, int
         if (!dev) HIP_TRY(hipStreamSynchronize(0));  // staging buffer is reused by the next chunk
     }
     HIP_TRY(hipStreamSynchronize(0));
-    if (!ix->irregular) {  // sticky: rows are never removed
+    if (!ix->irregular) {  // sticky until an edit recomputes it over the rows that are left (refresh_irregular)
         uint32_t flag = 0;
         HIP_TRY(hipMemcpy(&flag, ix->irregular_dev, sizeof(flag), hipMemcpyDeviceToHost));
         ix->irregular = flag != 0;
@@ -723,6 +737,216 @@ int crag_index_update(crag_index *ix, int64_t pos, const float *rows, int64_t n)
                     (long long)(pos + n), (long long)ix->size);
     DeviceGuard guard(ix->device);
     return store_rows_locked(ix, pos, rows, n);
+}
+
+// ---- in-place edits (kernels: crag_edit.hip) ----
+
+static crag::RowStore index_rows(crag_index *ix) { return crag::RowStore{ix->corpus, ix->corpus16, ix->inv_norm, ix->ids}; }
+
+// the bounce buffer as a RowStore of `rows` (a multiple of 32) rows
+static int bounce_rows(crag_index *ix, int64_t rows, crag::RowStore *out) {
+    const size_t b32 = (size_t)rows * crag::DIM * sizeof(float), b16 = ix->corpus16 ? (size_t)rows * crag::DIM * 2 : 0,
+                 binv = (size_t)rows * sizeof(float), bid = (size_t)rows * sizeof(int64_t);
+    int rc = ix->edit_bounce.ensure(b32 + b16 + bid + binv);
+    if (rc) return rc;
+    char *p = (char *)ix->edit_bounce.p;
+    out->corpus = (float *)p;
+    out->mirror = ix->corpus16 ? (_Float16 *)(p + b32) : nullptr;
+    out->ids = (int64_t *)(p + b32 + b16);
+    out->inv_norm = (float *)(p + b32 + b16 + bid);
+    return CRAG_OK;
+}
+
+static int64_t edit_chunk(const crag_index *ix, int64_t moved) {
+    const int64_t want = ((moved + 31) / 32) * 32;
+    return want < ix->edit_chunk_rows ? want : ix->edit_chunk_rows;
+}
+
+// after an edit: last_id from the last stored row, the irregular flag from the rows that are left
+static int refresh_after_edit(crag_index *ix) {
+    ix->last_id = INT64_MIN;
+    if (ix->size > 0)
+        HIP_TRY(hipMemcpy(&ix->last_id, ix->ids + (ix->size - 1), sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemsetAsync(ix->irregular_dev, 0, sizeof(uint32_t), 0));
+    HIP_TRY(crag::launch_irregular_flag(ix->inv_norm, ix->size, ix->irregular_dev, 0));
+    uint32_t flag = 0;
+    HIP_TRY(hipMemcpy(&flag, ix->irregular_dev, sizeof(flag), hipMemcpyDeviceToHost));
+    ix->irregular = flag != 0;
+    ix->edit_bounce.release();
+    return CRAG_OK;
+}
+
+// keep: one bit per stored row (bits beyond size already cleared), a cleared bit drops the row
+static int compact_locked(crag_index *ix, const std::vector<uint32_t> &keep) {
+    const int64_t n = ix->size, nw = (n + 31) / 32;
+    std::vector<uint32_t> prefix((size_t)nw + 1);
+    int64_t first = -1, total = 0;
+    for (int64_t w = 0; w < nw; ++w) {
+        prefix[w] = (uint32_t)total;
+        const uint32_t valid = (w == nw - 1 && (n & 31)) ? ((1u << (n & 31)) - 1u) : 0xffffffffu;
+        const uint32_t gone = ~keep[w] & valid;
+        if (first < 0 && gone) first = w * 32 + __builtin_ctz(gone);
+        total += __builtin_popcount(keep[w]);
+    }
+    prefix[nw] = (uint32_t)total;
+    const int64_t new_size = total;
+    if (new_size == n) return CRAG_OK;
+    const crag::RowStore index = index_rows(ix);
+    crag::RowStore bounce{};
+    const int64_t C = edit_chunk(ix, new_size - first);
+    int rc;
+    if (new_size > first) {   // every allocation in front of the first move
+        if ((rc = bounce_rows(ix, C, &bounce))) return rc;
+        if ((rc = ix->edit_srcpos.ensure((size_t)C * sizeof(int64_t)))) return rc;
+        if ((rc = ix->edit_mask.ensure((size_t)nw * 4))) return rc;
+        if ((rc = ix->edit_prefix.ensure(((size_t)nw + 1) * 4))) return rc;
+    }
+    HIP_TRY(hipDeviceSynchronize());   // every search in flight on this index, whichever stream it runs on
+    if (new_size > first) {
+        HIP_TRY(hipMemcpy(ix->edit_mask.p, keep.data(), (size_t)nw * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(ix->edit_prefix.p, prefix.data(), ((size_t)nw + 1) * 4, hipMemcpyHostToDevice));
+        int64_t *srcpos = (int64_t *)ix->edit_srcpos.p;
+        for (int64_t d0 = first; d0 < new_size; d0 += C) {   // rows move down: ascending chunks
+            const int64_t m = new_size - d0 < C ? new_size - d0 : C;
+            HIP_TRY(crag::launch_remove_srcpos((const uint32_t *)ix->edit_mask.p, (const uint32_t *)ix->edit_prefix.p, nw, d0, m,
+                                               srcpos, 0));
+            HIP_TRY(crag::launch_move_rows(index, bounce, srcpos, d0, m, 0));
+        }
+    }
+    HIP_TRY(crag::launch_clear_rows(index, new_size, n - new_size, 0));
+    HIP_TRY(hipStreamSynchronize(0));
+    ix->size = new_size;
+    return refresh_after_edit(ix);
+}
+
+int crag_index_remove(crag_index *ix, const int64_t *ids, int64_t n, int64_t *out_removed) {
+    if (out_removed) *out_removed = 0;
+    if (!ix) return fail(CRAG_EINVAL, "index is NULL");
+    if (n < 0) return fail(CRAG_EINVAL, "n must be >= 0");
+    if (n == 0) return CRAG_OK;
+    if (!ids) return fail(CRAG_EINVAL, "ids is NULL");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (ix->size == 0) return CRAG_OK;
+    DeviceGuard guard(ix->device);
+    const int64_t *d_ids = ids;
+    int rc;
+    if (!is_device_ptr(ids)) {
+        if ((rc = ix->stage_ids.ensure((size_t)n * sizeof(int64_t)))) return rc;
+        HIP_TRY(hipMemcpy(ix->stage_ids.p, ids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+        d_ids = (const int64_t *)ix->stage_ids.p;
+    }
+    const int64_t nw = (ix->size + 31) / 32;
+    if ((rc = ix->edit_mask.ensure((size_t)nw * 4))) return rc;
+    HIP_TRY(hipMemsetAsync(ix->edit_mask.p, 0, (size_t)nw * 4, 0));
+    HIP_TRY(crag::launch_lookup_ids(ix->ids, ix->size, d_ids, n, nullptr, 0, (uint32_t *)ix->edit_mask.p, nullptr, 0));
+    std::vector<uint32_t> keep((size_t)nw);
+    HIP_TRY(hipMemcpy(keep.data(), ix->edit_mask.p, (size_t)nw * 4, hipMemcpyDeviceToHost));
+    int64_t removed = 0;
+    for (int64_t w = 0; w < nw; ++w) {   // (the lookup marks stored positions only: no bit beyond size)
+        removed += __builtin_popcount(keep[w]);
+        const uint32_t valid = (w == nw - 1 && (ix->size & 31)) ? ((1u << (ix->size & 31)) - 1u) : 0xffffffffu;
+        keep[w] = ~keep[w] & valid;
+    }
+    if (removed == 0) return CRAG_OK;
+    if ((rc = compact_locked(ix, keep))) return rc;
+    if (out_removed) *out_removed = removed;
+    return CRAG_OK;
+}
+
+int crag_index_compact(crag_index *ix, const uint8_t *keep_mask, int64_t *out_size) {
+    if (!ix) return fail(CRAG_EINVAL, "index is NULL");
+    if (!keep_mask) return fail(CRAG_EINVAL, "keep_mask is NULL");
+    if (((uintptr_t)keep_mask) & 3) return fail(CRAG_EINVAL, "keep_mask must be 4-byte aligned");
+    if (is_device_ptr(keep_mask)) return fail(CRAG_EINVAL, "keep_mask must be a host pointer");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    DeviceGuard guard(ix->device);
+    const int64_t nw = (ix->size + 31) / 32;
+    std::vector<uint32_t> keep((size_t)nw);
+    if (nw) {
+        memcpy(keep.data(), keep_mask, (size_t)nw * 4);
+        if (ix->size & 31) keep[nw - 1] &= (1u << (ix->size & 31)) - 1u;
+        int rc = compact_locked(ix, keep);
+        if (rc) return rc;
+    }
+    if (out_size) *out_size = ix->size;
+    return CRAG_OK;
+}
+
+int crag_index_insert(crag_index *ix, const float *rows, const int64_t *ids, int64_t n) {
+    if (!ix) return fail(CRAG_EINVAL, "index is NULL");
+    if (n < 0) return fail(CRAG_EINVAL, "n must be >= 0");
+    if (n == 0) return CRAG_OK;
+    if (!rows) return fail(CRAG_EINVAL, "rows is NULL");
+    if (!ids) return fail(CRAG_EINVAL, "ids is NULL (an insertion needs explicit ids)");
+    std::unique_lock<std::mutex> lk(ix->mu);
+    DeviceGuard guard(ix->device);
+    const bool ids_dev = is_device_ptr(ids);
+    std::vector<int64_t> h_ids;
+    if (ids_dev) {
+        h_ids.resize((size_t)n);
+        HIP_TRY(hipMemcpy(h_ids.data(), ids, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    }
+    const int64_t *hid = ids_dev ? h_ids.data() : ids;
+    for (int64_t i = 1; i < n; ++i)
+        if (hid[i] <= hid[i - 1])
+            return fail(CRAG_EINVAL, "ids must be strictly ascending: ids[%lld] = %lld follows %lld", (long long)i,
+                        (long long)hid[i], (long long)hid[i - 1]);
+    if (hid[0] > ix->last_id) {   // nothing stored lies behind the new rows: exactly the crag_index_add route
+        lk.unlock();
+        return crag_index_add(ix, rows, ids, n);
+    }
+    if (ix->size + n > ix->capacity)
+        return fail(CRAG_ENOMEM, "capacity exceeded: size %lld + %lld > %lld", (long long)ix->size, (long long)n,
+                    (long long)ix->capacity);
+    if (ix->size + n >= (int64_t)0xfffffff0ll) return fail(CRAG_ENOMEM, "more than 2^32 rows per index");
+    int rc;
+    const int64_t *d_ids = ids;
+    if (!ids_dev) {
+        if ((rc = ix->stage_ids.ensure((size_t)n * sizeof(int64_t)))) return rc;
+        HIP_TRY(hipMemcpy(ix->stage_ids.p, ids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+        d_ids = (const int64_t *)ix->stage_ids.p;
+    }
+    // where each new row lands (stored ids below it + new ids below it), and that none of them is stored already
+    if ((rc = ix->edit_newpos.ensure((size_t)n * sizeof(int64_t)))) return rc;
+    if ((rc = ix->scratch.ensure(sizeof(unsigned long long)))) return rc;
+    int64_t *newpos = (int64_t *)ix->edit_newpos.p;
+    HIP_TRY(hipMemsetAsync(ix->scratch.p, 0, sizeof(unsigned long long), 0));
+    HIP_TRY(crag::launch_lookup_ids(ix->ids, ix->size, d_ids, n, newpos, 1, nullptr, (unsigned long long *)ix->scratch.p, 0));
+    unsigned long long dup = 0;
+    HIP_TRY(hipMemcpy(&dup, ix->scratch.p, sizeof(dup), hipMemcpyDeviceToHost));
+    if (dup) return fail(CRAG_EINVAL, "%llu of the %lld ids are stored already (crag_index_update re-embeds in place)", dup,
+                         (long long)n);
+    int64_t first = 0;
+    HIP_TRY(hipMemcpy(&first, newpos, sizeof(first), hipMemcpyDeviceToHost));
+    const int64_t new_size = ix->size + n;
+    const crag::RowStore index = index_rows(ix);
+    crag::RowStore bounce{};
+    const int64_t C = edit_chunk(ix, new_size - first);
+    if ((rc = bounce_rows(ix, C, &bounce))) return rc;
+    if ((rc = ix->edit_srcpos.ensure((size_t)C * sizeof(int64_t)))) return rc;
+    const int64_t CH = 65536;   // rows per staged chunk, as store_rows_locked
+    const bool rows_dev = is_device_ptr(rows);
+    if (!rows_dev && (rc = ix->stage_rows.ensure((size_t)(n < CH ? n : CH) * ix->dim * sizeof(float)))) return rc;
+    HIP_TRY(hipDeviceSynchronize());   // every search in flight on this index, whichever stream it runs on
+    int64_t *srcpos = (int64_t *)ix->edit_srcpos.p;
+    for (int64_t hi = new_size; hi > first; hi -= C) {   // rows move up: descending chunks
+        const int64_t d0 = hi - C > first ? hi - C : first;
+        HIP_TRY(crag::launch_insert_srcpos(newpos, n, d0, hi - d0, srcpos, 0));
+        HIP_TRY(crag::launch_move_rows(index, bounce, srcpos, d0, hi - d0, 0));
+    }
+    for (int64_t o = 0; o < n; o += CH) {
+        const int64_t m = (n - o < CH) ? (n - o) : CH;
+        const float *src = rows + (size_t)o * ix->dim;
+        if (!rows_dev) {
+            HIP_TRY(hipMemcpy(ix->stage_rows.p, src, (size_t)m * ix->dim * sizeof(float), hipMemcpyHostToDevice));
+            src = (const float *)ix->stage_rows.p;
+        }
+        HIP_TRY(crag::launch_store_rows_at(src, ix->dim, newpos + o, d_ids + o, m, index, ix->irregular_dev, 0));
+        if (!rows_dev) HIP_TRY(hipStreamSynchronize(0));  // staging buffer is reused by the next chunk
+    }
+    HIP_TRY(hipStreamSynchronize(0));
+    ix->size = new_size;
+    return refresh_after_edit(ix);
 }
 
 int crag_index_get_rows(crag_index *ix, int64_t pos, int64_t n, float *rows, int64_t *ids) {

@@ -157,6 +157,34 @@ hipError_t launch_check_ids(const int64_t *ids, int64_t n, int64_t prev, unsigne
                             hipStream_t st);
 hipError_t launch_fill_ids(int64_t *ids, int64_t pos, int64_t n, int64_t first, hipStream_t st);
 
+// ---- in-place edits (crag_edit.hip) ----
+// the four arrays a row lives in: the index's own, or a bounce buffer laid out like so many rows of the index
+struct RowStore {
+    float *corpus;        // tile32 layout
+    _Float16 *mirror;     // nullable; with it the fp32 rows are PS_BIG, without PS_SMALL
+    float *inv_norm;
+    int64_t *ids;
+};
+// binary search of ids[0, n) in the ascending stored[0, size): pos (nullable) = stored ids below each (+ j with
+// add_index), drop (nullable) = bit mask of the positions found, found (nullable) += their number
+hipError_t launch_lookup_ids(const int64_t *stored, int64_t size, const int64_t *ids, int64_t n, int64_t *pos,
+                             int add_index, uint32_t *drop, unsigned long long *found, hipStream_t st);
+// source position of destinations [d0, d0 + m): of a removal (keep mask + its per-word popcount prefix, n_words + 1
+// entries) / of an insertion (newpos ascending; -1 marks the slot of a new row)
+hipError_t launch_remove_srcpos(const uint32_t *keep, const uint32_t *prefix, int64_t n_words, int64_t d0, int64_t m,
+                                int64_t *srcpos, hipStream_t st);
+hipError_t launch_insert_srcpos(const int64_t *newpos, int64_t n_new, int64_t d0, int64_t m, int64_t *srcpos,
+                                hipStream_t st);
+// one chunk: index rows srcpos[0, m) -> bounce rows [0, m) -> index rows [d0, d0 + m) (two launches in stream order)
+hipError_t launch_move_rows(const RowStore &index, const RowStore &bounce, const int64_t *srcpos, int64_t d0, int64_t m,
+                            hipStream_t st);
+// launch_store_rows' bits at listed positions, + the ids
+hipError_t launch_store_rows_at(const float *rows, int dim, const int64_t *dstpos, const int64_t *new_ids, int64_t n,
+                                const RowStore &index, uint32_t *irregular, hipStream_t st);
+hipError_t launch_clear_rows(const RowStore &index, int64_t pos, int64_t n, hipStream_t st);
+// *flag = 1 when a row of [0, n) has a norm outside [1e-30, 1e30] (the caller zeroes it first)
+hipError_t launch_irregular_flag(const float *inv_norm, int64_t n, uint32_t *flag, hipStream_t st);
+
 // ---- BM25 lexical lane (crag_bm25.hip) ----
 constexpr int BM25_RANGE = 16384;             // row positions per workgroup: their fp32 accumulators fill 64 KiB of LDS
 constexpr int BM25_MAX_Q = 64;

@@ -102,6 +102,50 @@ class DenseIndex:
         _native.check(self._lib.crag_index_update(self._h, int(pos), ptr, n), "crag_index_update")
         del keep
 
+    # -- in-place edits (crag_index_remove / compact / insert): afterwards the index is what a fresh build from the
+    #    same rows in id order would be; each call waits for the searches in flight on this index ---------------
+    @staticmethod
+    def _ids_arg(ids, n: Optional[int] = None):
+        """(pointer, count, keepalive) for int64 ids given as a numpy-like sequence or a torch tensor."""
+        if _is_torch(ids):
+            keep = ids.to(torch.int64).contiguous().reshape(-1)
+            ptr, count = keep.data_ptr(), int(keep.numel())
+        else:
+            keep = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+            ptr, count = keep.ctypes.data, int(keep.size)
+        if n is not None and count != n:
+            raise ValueError("ids length mismatch")
+        return (ptr if count else None), count, keep
+
+    def remove(self, ids) -> int:
+        """Remove the rows with these ids (any order, repeats and absent ids allowed; host sequence or CUDA
+        tensor).  Returns the number of rows removed."""
+        ptr, n, keep = self._ids_arg(ids)
+        removed = ctypes.c_int64(0)
+        _native.check(self._lib.crag_index_remove(self._h, ptr, n, ctypes.byref(removed)), "crag_index_remove")
+        del keep
+        return int(removed.value)
+
+    def compact(self, keep) -> int:
+        """Keep the rows whose entry of the bool array `keep` (one per stored row) is true, remove the others.
+        Returns the new size."""
+        k = np.asarray(keep, dtype=bool).reshape(-1)
+        if k.size != len(self):
+            raise ValueError(f"keep must have one entry per stored row ({len(self)}), got {k.size}")
+        packed = self.pack_mask(k) if k.size else np.zeros((4,), dtype=np.uint8)
+        size = ctypes.c_int64(0)
+        _native.check(self._lib.crag_index_compact(self._h, packed.ctypes.data, ctypes.byref(size)), "crag_index_compact")
+        return int(size.value)
+
+    def insert(self, vectors, ids) -> None:
+        """`add` for rows whose ids (strictly ascending) may lie between the stored ones: the rows behind them
+        move up in place.  An id that is stored already is an error and leaves the index unchanged.  Takes host
+        arrays or CUDA tensors like `add`."""
+        ptr, n, keep = _as_f32_2d(vectors, self.dim, "vectors")
+        ids_ptr, _, keep_ids = self._ids_arg(ids, n)
+        _native.check(self._lib.crag_index_insert(self._h, ptr, ids_ptr, n), "crag_index_insert")
+        del keep, keep_ids
+
     def get_rows(self, pos: int, n: int) -> Tuple[np.ndarray, np.ndarray]:
         rows = np.empty((n, self.dim), dtype=np.float32)
         ids = np.empty((n,), dtype=np.int64)

@@ -121,7 +121,7 @@ class DenseTable:
         self.call_started_at = np.empty((0,), dtype="datetime64[us]")
         self.call_ids = np.empty((0,), dtype=object)
         self.call_tags: Dict[Any, Sequence[str]] = {}
-        # bumped whenever rows are appended or move: whatever is built over row POSITIONS (the exact-token lane,
+        # bumped whenever rows are appended, removed or move: whatever is built over row POSITIONS (the exact-token lane,
         # packed masks) is stale once it differs
         self.generation = 0
         # per-row tech_tokens (the `tech_tokens text[]` column), kept once a tech lane was built so that the lane
@@ -178,31 +178,19 @@ class DenseTable:
             return
         self._rebuild(capacity=max(need, int(self.index.capacity * 1.5) + 1024))
 
-    def _rebuild(self, capacity: int, order: Optional[np.ndarray] = None, extra=None) -> None:
-        """New index of `capacity` rows holding the current rows (+ `extra` = (vectors, ids)), permuted by
-        `order` (positions into the concatenation) when given."""
+    def _rebuild(self, capacity: int) -> None:
+        """New index of `capacity` rows holding the current rows (device to device)."""
         import torch
         old, n_old = self.index, len(self.index)
         dev = torch.device("cuda", old.device)
         new = DenseIndex(old.dim, capacity=capacity, device=old.device)
         try:
-            if order is None and extra is None:
-                step = 65536
-                for lo in range(0, n_old, step):
-                    m = min(step, n_old - lo)
-                    buf = torch.empty(m, old.dim, dtype=torch.float32, device=dev)
-                    ids = old.get_rows_into(lo, m, buf)
-                    new.add(buf, ids=ids)
-            else:
-                rows = torch.empty(n_old, old.dim, dtype=torch.float32, device=dev)
-                ids = old.get_rows_into(0, n_old, rows) if n_old else np.empty((0,), dtype=np.int64)
-                if extra is not None:
-                    rows = torch.cat([rows, _rows_on_device(extra[0], len(extra[1]), old.dim, dev)])
-                    ids = np.concatenate([ids, np.asarray(extra[1], dtype=np.int64)])
-                if order is not None:
-                    rows = rows[torch.as_tensor(order, device=dev)]
-                    ids = ids[order]
-                new.add(rows, ids=ids)
+            step = 65536
+            for lo in range(0, n_old, step):
+                m = min(step, n_old - lo)
+                buf = torch.empty(m, old.dim, dtype=torch.float32, device=dev)
+                ids = old.get_rows_into(lo, m, buf)
+                new.add(buf, ids=ids)
         except Exception:
             new.close()
             raise
@@ -213,9 +201,10 @@ class DenseTable:
     def insert(self, vectors, columns: Dict[str, Sequence[Any]], call_started_at: Optional[Sequence[Any]] = None,
                call_tags: Optional[Dict[Any, Sequence[str]]] = None) -> None:
         """`add` for rows in any id order (a row embedded late has an id below the stored maximum): when the
-        new ids do not simply continue the stored ones, the table is rebuilt in ascending id order, which
-        is the order every tie-break of the lane assumes.  An id that is already stored is an error (use
-        DenseIndex.update to re-embed in place)."""
+        new ids do not simply continue the stored ones, the index moves the rows behind them up in place
+        (DenseIndex.insert) and the host columns are merged in ascending id order, which is the order every
+        tie-break of the lane assumes.  The index object changes only when its capacity has to grow (`_reserve`).
+        An id that is already stored is an error (use DenseIndex.update to re-embed in place)."""
         new_ids = np.asarray(columns[self.id_field], dtype=np.int64)
         n = int(new_ids.size)
         if n == 0:
@@ -230,8 +219,18 @@ class DenseTable:
         order = np.argsort(all_ids, kind="stable")
         if np.any(np.diff(all_ids[order]) == 0):
             raise ValueError(f"duplicate {self.id_field} in insert")
+        self._reserve(n)
         # `vectors` may be a CUDA tensor (the device-resident backfill): it stays on the device
-        self._rebuild(capacity=max(self.index.capacity, all_ids.size), order=order, extra=(vectors, new_ids))
+        by_id = np.argsort(new_ids, kind="stable")
+        if np.array_equal(by_id, np.arange(n)):
+            self.index.insert(vectors, new_ids)
+        else:
+            import torch
+            if isinstance(vectors, torch.Tensor):
+                sorted_rows = vectors.reshape(n, self.index.dim)[torch.as_tensor(by_id, device=vectors.device)]
+            else:
+                sorted_rows = np.asarray(vectors, dtype=np.float32).reshape(n, self.index.dim)[by_id]
+            self.index.insert(sorted_rows, new_ids[by_id])
         for key in set(self.columns) | set(columns):
             merged = list(self.columns.get(key, [None] * old_ids.size)) + list(columns.get(key, [None] * n))
             self.columns[key] = [merged[i] for i in order]
@@ -246,6 +245,46 @@ class DenseTable:
             self.tech_tokens = [merged_t[i] for i in order]
         self._pos_of_id = None
         self.generation += 1
+
+    def _drop_host_rows(self, keep: np.ndarray) -> None:
+        """The host side of a removal: every per-row sequence loses the rows whose `keep` entry is false."""
+        kept = np.flatnonzero(keep)
+        for key, vals in self.columns.items():
+            self.columns[key] = [vals[i] for i in kept]
+        self.call_ids = self.call_ids[keep]
+        self.call_started_at = self.call_started_at[keep]
+        if self.tech_tokens is not None:
+            self.tech_tokens = [self.tech_tokens[i] for i in kept]
+        self._pos_of_id = None
+        self.generation += 1   # row positions moved: the exact-token lane and the BM25 lane rebuild
+
+    def delete(self, ids) -> int:
+        """Remove the rows with these ids (absent ids are ignored) from the index, in place, and from the
+        columns, call ids, timestamps and tech tokens.  Returns the number of rows removed.  `call_tags`
+        entries of calls that have no rows left may stay."""
+        old_ids = np.asarray(self.columns.get(self.id_field, []), dtype=np.int64)
+        keep = ~np.isin(old_ids, np.asarray(list(ids), dtype=np.int64))
+        gone = int(keep.size - np.count_nonzero(keep))
+        if gone == 0:
+            return 0
+        removed = self.index.remove(old_ids[~keep])
+        if removed != gone:
+            raise RuntimeError(f"{self.name}: the index removed {removed} rows where the columns hold {gone}")
+        self._drop_host_rows(keep)
+        return gone
+
+    def delete_calls(self, call_ids) -> int:
+        """Remove every row of these calls -- what `calls(call_id) ON DELETE CASCADE` does to the table
+        (alembic/versions/0001_initial_schema.py:59,79,123).  Returns the number of rows removed."""
+        wanted = set(call_ids)
+        keep = np.fromiter((c not in wanted for c in self.call_ids), dtype=bool, count=len(self.call_ids))
+        gone = int(keep.size - np.count_nonzero(keep))
+        if gone == 0:
+            return 0
+        if self.index.compact(keep) != keep.size - gone:
+            raise RuntimeError(f"{self.name}: the index and the columns disagree about the rows of the deleted calls")
+        self._drop_host_rows(keep)
+        return gone
 
     def sink(self, row_columns):
         """Backfill sink (embedding_pipeline.BackfillStore.update_embeddings -> HBM): an object whose
@@ -394,7 +433,9 @@ class DenseTable:
 
     def sync_bm25_lane(self, lane):
         """The lane for the table as it is now: unchanged when it is current, grown with `extend` (only the new rows
-        are tokenised) when rows were appended behind the ones it holds, rebuilt when rows moved (`insert`)."""
+        are tokenised) when rows were appended behind the ones it holds, rebuilt when rows moved (`insert`) or left
+        (`delete`: a table that shrank never passes for one that grew, the lane then holds more rows than the table
+        or ids the table no longer has at those positions)."""
         if getattr(lane, "table_generation", None) == self.generation and len(lane) == len(self):
             return lane
         ids = np.asarray(self.columns.get(self.id_field, []), dtype=np.int64)
@@ -410,15 +451,6 @@ class DenseTable:
         if getattr(self, "_pos_of_id", None) is None:
             self._pos_of_id = {int(v): i for i, v in enumerate(self.columns[self.id_field])}
         return self._pos_of_id
-
-
-def _rows_on_device(vectors, n: int, dim: int, dev):
-    """[n, dim] float32 on `dev` from host lists / numpy or from a torch tensor (a CUDA tensor never visits the
-    host)."""
-    import torch
-    if isinstance(vectors, torch.Tensor):
-        return vectors.to(device=dev, dtype=torch.float32).reshape(n, dim)
-    return torch.as_tensor(np.asarray(vectors, dtype=np.float32).reshape(n, dim), device=dev)
 
 
 def _native_max_k() -> int:

@@ -64,7 +64,7 @@ int crag_index_destroy(crag_index *ix);
  * ascending and above every id already stored (CRAG_EINVAL otherwise, nothing is stored): the
  * backfill feeds rows `ORDER BY id` (embedding_pipeline.py:136), and this is what makes the search
  * order below "descending score, then ascending id".  A row embedded late (its id below the stored
- * maximum) goes in through a rebuild: cadence_rag_amd.retrieve.DenseTable.insert does that.
+ * maximum) goes in through crag_index_insert.
  * Rows with a zero or non-finite norm are stored but never returned (pgvector gives them a NaN
  * distance).
  * Replaces: _update_embeddings' per-row UPDATE (embedding_pipeline.py:157-168).
@@ -76,6 +76,43 @@ int crag_index_add(crag_index *ix, const float *rows, const int64_t *ids, int64_
 
 /* Overwrite the vectors of rows [pos, pos+n) (positions, not ids) — re-embed in place. */
 int crag_index_update(crag_index *ix, int64_t pos, const float *rows, int64_t n);
+
+/* ---- in-place edits.  After any of the three the index is indistinguishable from one built fresh, with
+ * crag_index_add, from the same rows in id order: same size and ids, crag_index_get_rows bit-exact, every search path
+ * the same ids / scores / counts bit for bit, the same scan kernel chosen, the same crag_index_count_eligible, the same
+ * next crag_index_add accepted.  Rows that stay are copied through the layout (fp32 pieces, fp16 mirror pieces,
+ * 1/||row||, id), never recomputed; rows in front of the first changed position are not touched; vacated positions
+ * return to the state crag_index_create leaves them in.  The move works in chunks of CRAG_EDIT_CHUNK_ROWS destination
+ * rows (environment, a multiple of 32, read once at crag_index_create; default 16384) through a bounce buffer of at
+ * most 128 MiB that is held only during the call.
+ * All three are synchronous like crag_index_add, take the index's lock and WAIT FOR EVERY SEARCH IN FLIGHT on the index
+ * before the first row moves -- the searches of crag_index_search_async on the callers' streams (the workspaces'
+ * streams) and those of crag_index_search_pipelined on the index's own pipe streams: the device is synchronised.  A
+ * search enqueued after the call returns sees the edited index.  size is right afterwards and the largest stored id is
+ * that of the last row, or none when the index is empty (an emptied index accepts ids from any value again).  n == 0
+ * is CRAG_OK.  Mixed remove-and-insert in one call does not exist: call one after the other. */
+
+/* Remove the rows whose ids are listed (host OR device pointer, any order, repeats allowed; ids that are not stored are
+ * ignored).  out_removed (nullable) receives the number of rows actually removed.
+ * Replaces: what `calls(call_id) ON DELETE CASCADE` does to chunks, analysis_artifacts and artifact_chunks
+ * (alembic/versions/0001_initial_schema.py:59,79,123, 0006_add_artifact_chunks.py:23-24): a call deleted or re-ingested
+ * upstream takes its rows with it. */
+int crag_index_remove(crag_index *ix, const int64_t *ids, int64_t n, int64_t *out_removed);
+
+/* The same by position: keep_mask is a HOST pointer in the row_mask encoding over the current size (bit (i & 7) of byte
+ * i >> 3 = row at position i; 4-byte aligned, ceil(size/32)*4 bytes, bits beyond size ignored); a cleared bit removes
+ * the row.  out_size (nullable) receives the new size.  Same reference lines as crag_index_remove (the caller has
+ * resolved the cascade to row positions already, as DenseTable.delete_calls does). */
+int crag_index_compact(crag_index *ix, const uint8_t *keep_mask, int64_t *out_size);
+
+/* Insert n rows whose ids may lie anywhere between the stored ones (rows / ids: host OR device pointers; ids strictly
+ * ascending, CRAG_EINVAL otherwise).  An id that is stored already gives CRAG_EINVAL, a size above the capacity
+ * CRAG_ENOMEM -- both are checked before anything moves, the index is unchanged.  Ids that all lie above the largest
+ * stored id take exactly the crag_index_add route.
+ * Replaces: _update_embeddings' per-row `UPDATE ... SET embedding` (app/embedding_pipeline.py:149-168) for rows that
+ * arrive in arbitrary id order -- the backfill embeds whichever rows are NULL, and a row embedded late has an id below
+ * the stored maximum. */
+int crag_index_insert(crag_index *ix, const float *rows, const int64_t *ids, int64_t n);
 
 /* Rows currently stored / capacity / dim. */
 int64_t crag_index_size(const crag_index *ix);
