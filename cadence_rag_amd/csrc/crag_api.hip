@@ -646,6 +646,16 @@ int64_t crag_index_size(const crag_index *ix) { return ix ? ix->size : -1; }
 int64_t crag_index_capacity(const crag_index *ix) { return ix ? ix->capacity : -1; }
 int crag_index_dim(const crag_index *ix) { return ix ? ix->dim : -1; }
 
+// the irregular flag from the rows that are stored now (irregular_flag_kernel: store_row's own condition)
+static int recompute_irregular(crag_index *ix) {
+    HIP_TRY(hipMemsetAsync(ix->irregular_dev, 0, sizeof(uint32_t), 0));
+    HIP_TRY(crag::launch_irregular_flag(ix->inv_norm, ix->size, ix->irregular_dev, 0));
+    uint32_t flag = 0;
+    HIP_TRY(hipMemcpy(&flag, ix->irregular_dev, sizeof(flag), hipMemcpyDeviceToHost));
+    ix->irregular = flag != 0;
+    return CRAG_OK;
+}
+
 static int store_rows_locked(crag_index *ix, int64_t pos, const float *rows, int64_t n) {
     // chunked so that host staging stays bounded (64 Ki rows = 256 MiB at dim 1024)
     const int64_t CH = 65536;
@@ -663,7 +673,9 @@ static int store_rows_locked(crag_index *ix, int64_t pos, const float *rows, int
         if (!dev) HIP_TRY(hipStreamSynchronize(0));  // staging buffer is reused by the next chunk
     }
     HIP_TRY(hipStreamSynchronize(0));
-    if (!ix->irregular) {  // sticky until an edit recomputes it over the rows that are left (refresh_irregular)
+    // the store kernel can only raise the flag.  Set, it stays right while rows are appended; whoever may have taken
+    // an irregular row away (crag_index_update, the edits) recomputes it over the stored rows (recompute_irregular)
+    if (!ix->irregular) {
         uint32_t flag = 0;
         HIP_TRY(hipMemcpy(&flag, ix->irregular_dev, sizeof(flag), hipMemcpyDeviceToHost));
         ix->irregular = flag != 0;
@@ -736,7 +748,12 @@ int crag_index_update(crag_index *ix, int64_t pos, const float *rows, int64_t n)
         return fail(CRAG_EINVAL, "update range [%lld, %lld) exceeds size %lld", (long long)pos,
                     (long long)(pos + n), (long long)ix->size);
     DeviceGuard guard(ix->device);
-    return store_rows_locked(ix, pos, rows, n);
+    const bool was_irregular = ix->irregular;
+    int rc = store_rows_locked(ix, pos, rows, n);
+    if (rc) return rc;
+    // the overwritten rows may have been the irregular ones: as after an edit, the flag follows the rows stored now.
+    // (A clear flag needs nothing more: the store kernel has raised it if a new row is irregular.)
+    return was_irregular ? recompute_irregular(ix) : CRAG_OK;
 }
 
 // ---- in-place edits (kernels: crag_edit.hip) ----
@@ -767,13 +784,9 @@ static int refresh_after_edit(crag_index *ix) {
     ix->last_id = INT64_MIN;
     if (ix->size > 0)
         HIP_TRY(hipMemcpy(&ix->last_id, ix->ids + (ix->size - 1), sizeof(int64_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemsetAsync(ix->irregular_dev, 0, sizeof(uint32_t), 0));
-    HIP_TRY(crag::launch_irregular_flag(ix->inv_norm, ix->size, ix->irregular_dev, 0));
-    uint32_t flag = 0;
-    HIP_TRY(hipMemcpy(&flag, ix->irregular_dev, sizeof(flag), hipMemcpyDeviceToHost));
-    ix->irregular = flag != 0;
+    int rc = recompute_irregular(ix);
     ix->edit_bounce.release();
-    return CRAG_OK;
+    return rc;
 }
 
 // keep: one bit per stored row (bits beyond size already cleared), a cleared bit drops the row

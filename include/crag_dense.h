@@ -74,7 +74,12 @@ int crag_index_destroy(crag_index *ix);
  * streams of the index's own: crag_index_join + a synchronisation of the joined stream come first. */
 int crag_index_add(crag_index *ix, const float *rows, const int64_t *ids, int64_t n);
 
-/* Overwrite the vectors of rows [pos, pos+n) (positions, not ids) — re-embed in place. */
+/* Overwrite the vectors of rows [pos, pos+n) (positions, not ids; host OR device pointer) — re-embed in place.
+ * pos < 0, n < 0, pos + n > size or rows == NULL with n > 0 give CRAG_EINVAL and change nothing; n == 0 is CRAG_OK.
+ * Afterwards the index is what a fresh build, with crag_index_add, from the resulting rows would be: the same
+ * crag_index_get_rows, every search the same ids / scores / counts bit for bit, the same crag_index_count_eligible and
+ * the same scan kernel chosen -- an index whose only row with a norm outside [1e-30, 1e30] is overwritten by an
+ * ordinary one returns to the prefilter path, one that receives such a row leaves it. */
 int crag_index_update(crag_index *ix, int64_t pos, const float *rows, int64_t n);
 
 /* ---- in-place edits.  After any of the three the index is indistinguishable from one built fresh, with

@@ -1,4 +1,4 @@
-"""The contract of the in-place index edits (include/crag_dense.h: crag_index_remove / compact / insert) in numpy:
+"""The contract of the in-place index edits (include/crag_dense.h: crag_index_remove / compact / insert / update) in numpy:
 given the stored ids and rows and an edit, the ids and rows a FRESH build -- crag_index_add of the same rows in id
 order -- would hold.  The GPU tests build a second index from this result and compare bit for bit."""
 from __future__ import annotations
@@ -50,6 +50,23 @@ def insert(ids, rows, new_ids, new_rows) -> Tuple[np.ndarray, np.ndarray]:
     order = np.argsort(all_ids, kind="stable")
     all_rows = np.concatenate([rows.reshape(ids.size, new_rows.shape[1] if ids.size == 0 else rows.shape[1]), new_rows])
     return all_ids[order], all_rows[order]
+
+
+def update(ids, rows, pos, new_rows) -> Tuple[np.ndarray, np.ndarray]:
+    """crag_index_update: rows [pos, pos + n) take the new vectors, the ids stay.  The inputs are not modified;
+    ValueError for a range outside the table, as the ABI answers CRAG_EINVAL with nothing changed."""
+    ids, rows = _check_table(ids, rows)
+    new_rows = np.asarray(new_rows, dtype=np.float32)
+    if new_rows.ndim == 1:
+        new_rows = new_rows[None, :]
+    pos, n = int(pos), new_rows.shape[0]
+    if pos < 0 or pos + n > ids.size:
+        raise ValueError("update range outside the table")
+    if n and new_rows.shape[1] != rows.shape[1]:
+        raise ValueError("row width")
+    ids, rows = ids.copy(), rows.copy()
+    rows[pos:pos + n] = new_rows
+    return ids, rows
 
 
 def pack_keep(keep) -> np.ndarray:

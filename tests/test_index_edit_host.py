@@ -54,6 +54,25 @@ def test_oracle_edits_compose_to_a_fresh_build():
     assert np.array_equal(ids, IDS) and np.array_equal(rows, ROWS)
 
 
+def test_oracle_update_by_hand():
+    new = np.array([[100, 101, 102, 103], [200, 201, 202, 203]], dtype=np.float32)
+    ids_before, rows_before, new_before = IDS.copy(), ROWS.copy(), new.copy()
+    ids, rows = ox.update(IDS, ROWS, 3, new)
+    assert np.array_equal(IDS, ids_before) and np.array_equal(ROWS, rows_before) and np.array_equal(new, new_before)
+    assert ids is not IDS and rows is not ROWS and not np.shares_memory(rows, ROWS) and not np.shares_memory(rows, new)
+    assert np.array_equal(ids, IDS)
+    assert np.array_equal(rows, np.stack([ROWS[0], ROWS[1], ROWS[2], new[0], new[1]]))
+    ids, rows = ox.update(IDS, ROWS, 0, new[1])                     # one row given as a vector
+    assert np.array_equal(ids, IDS) and np.array_equal(rows, np.stack([new[1], ROWS[1], ROWS[2], ROWS[3], ROWS[4]]))
+    ids, rows = ox.update(IDS, ROWS, 5, np.empty((0, 4), np.float32))   # n == 0 is allowed anywhere up to the size
+    assert np.array_equal(ids, IDS) and np.array_equal(rows, ROWS)
+    for pos in (-1, 4, 5):
+        with pytest.raises(ValueError, match="outside"):
+            ox.update(IDS, ROWS, pos, new)
+    with pytest.raises(ValueError, match="width"):
+        ox.update(IDS, ROWS, 0, new[:, :3])
+
+
 _C_TYPES = {"crag_index *": ctypes.c_void_p, "const int64_t *": ctypes.c_void_p, "const float *": ctypes.c_void_p,
             "const uint8_t *": ctypes.c_void_p, "int64_t *": ctypes.POINTER(ctypes.c_int64), "int64_t": ctypes.c_int64}
 
