@@ -46,6 +46,10 @@ class Settings:
     rerank_topm_out: int = 12           # rows kept per side after reranking
     rerank_max_length: int = 1024
     rerank_device: int = -1             # -1: embeddings_device
+    # near-duplicate suppression of each side's fused list, in front of the reranker (the reference's planned "dedupe
+    # rules", PHASED_PLAN.md:299-303): a fused row is dropped when a kept, higher-ranked row of its side has at least
+    # this cosine with it.  0.0 = off
+    evidence_dedupe_cosine: float = 0.0
 
     def __post_init__(self) -> None:
         if self.rerank_device < 0:

@@ -1083,6 +1083,38 @@ int crag_index_join(crag_index *ix, void *stream) {
     return CRAG_OK;
 }
 
+int crag_index_dedupe_async(crag_index *ix, const int64_t *d_ids, const int32_t *d_counts, int nq, int width,
+                            float threshold, int64_t *d_out_ids, int32_t *d_out_counts, int32_t *d_out_dup_of,
+                            float *d_out_sim, void *stream) {
+    if (!ix) return fail(CRAG_EINVAL, "index is NULL");
+    if (nq < 0) return fail(CRAG_EINVAL, "nq must be >= 0 (got %d)", nq);
+    if (width < 1 || width > CRAG_DEDUPE_MAX_WIDTH)
+        return fail(CRAG_EINVAL, "width must be in [1, %d] (got %d)", CRAG_DEDUPE_MAX_WIDTH, width);
+    if (!(threshold > -1.f && threshold <= 1.f))   // (NaN fails both)
+        return fail(CRAG_EINVAL, "threshold must be finite, in (-1, 1] (got %g)", (double)threshold);
+    if (!d_ids || !d_counts || !d_out_ids || !d_out_counts)
+        return fail(CRAG_EINVAL, "ids / counts / out_ids / out_counts must not be NULL");
+    if (nq == 0) return CRAG_OK;
+    std::lock_guard<std::mutex> lk(ix->mu);
+    DeviceGuard guard(ix->device);
+    crag::DedupeParams p;
+    p.corpus = ix->corpus;
+    p.inv_norm = ix->inv_norm;
+    p.stored = ix->ids;
+    p.size = ix->size;
+    p.piece_shift = crag::crag_piece_shift(ix->corpus16 != nullptr);
+    p.ids = d_ids;
+    p.counts = d_counts;
+    p.width = width;
+    p.threshold = threshold;
+    p.out_ids = d_out_ids;
+    p.out_counts = d_out_counts;
+    p.out_dup_of = d_out_dup_of;
+    p.out_sim = d_out_sim;
+    HIP_TRY(crag::launch_dedupe(p, nq, (hipStream_t)stream));
+    return CRAG_OK;
+}
+
 int crag_index_search(crag_index *ix, const float *queries, int nq, int k, const uint8_t *row_mask,
                       int64_t mask_stride, int64_t *out_ids, float *out_scores, int32_t *out_counts) {
     int rc = check_search_args(ix, queries, nq, k, row_mask, mask_stride, out_ids, out_scores, out_counts);

@@ -212,4 +212,23 @@ struct Bm25Params {
 int64_t bm25_scratch_bytes(int64_t n_rows, int nq, int k);
 hipError_t launch_bm25(const Bm25Params &p, hipStream_t st);
 
+
+// ---- near-duplicate suppression of ranked lists (crag_dedupe.hip) ----
+struct DedupeParams {
+    const float *corpus;        // tile32 layout
+    const float *inv_norm;
+    const int64_t *stored;      // [size] ids, ascending with the position
+    int64_t size;
+    int piece_shift;
+    const int64_t *ids;         // [nq, width] ranked lists, best first
+    const int32_t *counts;      // [nq], clamped to [0, width]
+    int width;                  // <= CRAG_DEDUPE_MAX_WIDTH
+    float threshold;
+    int64_t *out_ids;           // [nq, width] kept ids in their order, -1 padded
+    int32_t *out_counts;        // [nq]
+    int32_t *out_dup_of;        // nullable [nq, width]: -1 kept, else the slot of the suppressor
+    float *out_sim;             // nullable [nq, width]: that pair's cosine, NaN where kept
+};
+hipError_t launch_dedupe(const DedupeParams &p, int nq, hipStream_t st);
+
 }  // namespace crag

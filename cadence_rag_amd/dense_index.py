@@ -245,6 +245,55 @@ class DenseIndex:
         """Make `stream` wait for every pipelined search issued so far (does not block the host)."""
         _native.check(self._lib.crag_index_join(self._h, ctypes.c_void_p(stream)), "crag_index_join")
 
+    # -- near-duplicate suppression (crag_index_dedupe_async) -------------------------------------
+    def dedupe_async(self, d_ids, d_counts, threshold: float, d_out_ids, d_out_counts, d_out_dup_of=None,
+                     d_out_sim=None, stream: int = 0) -> None:
+        """Greedy near-duplicate suppression of ranked lists, enqueued on `stream`: d_ids int64 [nq, width <= 256]
+        best first, d_counts int32 [nq] (the shape rrf_fuse emits).  An item is dropped iff a KEPT earlier item of its
+        list has a cosine >= threshold with it (ids that are not stored, -1 and rows with a zero or non-finite norm are
+        kept and suppress nothing).  d_out_ids [nq, width]: the kept ids in order, -1 padded; d_out_counts [nq];
+        d_out_dup_of int32 / d_out_sim fp32 [nq, width] (optional): per input slot the slot that suppressed it (-1:
+        kept) and that pair's cosine (NaN: kept).  Arguments are torch CUDA tensors."""
+        if d_ids.dim() != 2:
+            raise ValueError("d_ids must have shape [nq, width]")
+        nq, width = int(d_ids.shape[0]), int(d_ids.shape[1])
+        _native.check(self._lib.crag_index_dedupe_async(
+            self._h, d_ids.data_ptr(), d_counts.data_ptr(), nq, width, float(threshold), d_out_ids.data_ptr(),
+            d_out_counts.data_ptr(), None if d_out_dup_of is None else d_out_dup_of.data_ptr(),
+            None if d_out_sim is None else d_out_sim.data_ptr(), ctypes.c_void_p(stream)), "crag_index_dedupe_async")
+
+    def dedupe(self, ids, threshold: float):
+        """Host convenience over dedupe_async for one ranked list of ids (a flat sequence) or several (a sequence of
+        sequences, lengths may differ; at most 256 ids each).  Returns (keep_slots, dup_of, sim): the input slots that
+        are kept (int64, ascending), per input slot the slot that suppressed it (-1: kept) and that pair's cosine
+        (NaN: kept) -- arrays for one list, lists of arrays for several.  Synchronises."""
+        if torch is None:  # pragma: no cover
+            raise _native.NativeLibraryError("DenseIndex.dedupe stages its buffers with torch")
+        single = len(ids) == 0 or np.ndim(ids[0]) == 0
+        lists = [np.asarray(ids, dtype=np.int64).reshape(-1)] if single else \
+            [np.asarray(l, dtype=np.int64).reshape(-1) for l in ids]
+        width = max([int(l.size) for l in lists] + [1])
+        if width > _native.CRAG_DEDUPE_MAX_WIDTH:
+            raise ValueError(f"a list holds at most {_native.CRAG_DEDUPE_MAX_WIDTH} ids (got {width})")
+        h_ids = np.full((len(lists), width), -1, dtype=np.int64)
+        for q, l in enumerate(lists):
+            h_ids[q, :l.size] = l
+        dev = torch.device("cuda", self.device)
+        d_ids = torch.from_numpy(h_ids).to(dev)
+        d_ct = torch.tensor([int(l.size) for l in lists], dtype=torch.int32, device=dev)
+        d_out = torch.empty_like(d_ids)
+        d_oct = torch.empty_like(d_ct)
+        d_dup = torch.empty(len(lists), width, dtype=torch.int32, device=dev)
+        d_sim = torch.empty(len(lists), width, dtype=torch.float32, device=dev)
+        self.dedupe_async(d_ids, d_ct, threshold, d_out, d_oct, d_dup, d_sim,
+                          stream=torch.cuda.current_stream(dev).cuda_stream)
+        dup, sim = d_dup.cpu().numpy(), d_sim.cpu().numpy()
+        res = [(np.flatnonzero(dup[q, :l.size] < 0).astype(np.int64), dup[q, :l.size].copy(), sim[q, :l.size].copy())
+               for q, l in enumerate(lists)]
+        if single:
+            return res[0]
+        return [r[0] for r in res], [r[1] for r in res], [r[2] for r in res]
+
     # -- profiling / reporting -------------------------------------------------------------
     def profile_enable(self, every: int = 1) -> None:
         """Record HIP events around the scan/merge kernels of every `every`-th search (0 = off)."""

@@ -300,8 +300,13 @@ class HybridSearcher:
 
     def __init__(self, index, tech_index: "TechTokenIndex | None" = None, *, dense_k: int = 50, tech_k: int = 50,
                  rrf_k: int = DEFAULT_RRF_K, verify_tokens: bool = False, overlap_lanes: bool = True,
-                 bm25_index=None, bm25_k: int = 50) -> None:
-        """verify_tokens: run the exact-token lane's host-side string check (a blocking D2H copy per step); off by
+                 bm25_index=None, bm25_k: int = 50, dedupe_cosine: "float | None" = None) -> None:
+        """dedupe_cosine: when set (a cosine in (-1, 1]), the fused list is deduped on the same stream behind the
+        fusion kernel (DenseIndex.dedupe_async: an item is dropped iff a KEPT earlier item of its list is at least
+        that similar to it): "ids" and "counts" of the result are the deduped ones, "scores" and "lanes" are compacted
+        to match, "dup_of" / "dup_sim" tell per FUSED slot which slot suppressed it.  A fused width above 256 is then a
+        ValueError.  None (default): nothing changes, no launch.
+        verify_tokens: run the exact-token lane's host-side string check (a blocking D2H copy per step); off by
         default so that a step only enqueues work on the caller's stream.
         overlap_lanes: run the exact-token lane on a side stream beside the dense search (forked from the caller's
         stream behind the scan's launch, joined in front of the fusion kernel; same results, tested).  ON by default
@@ -314,9 +319,40 @@ class HybridSearcher:
         self.overlap_lanes = bool(overlap_lanes)
         self.dense_k, self.tech_k, self.rrf_k = int(dense_k), int(tech_k), int(rrf_k)
         self.bm25_index, self.bm25_k = bm25_index, int(bm25_k)
+        self.dedupe_cosine = None if dedupe_cosine is None else float(dedupe_cosine)
+        self._dedupe_out: dict = {}  # per (stream, batch size, out_k): the deduped lists and the compaction's scratch
         self._dense_out: dict = {}  # per (stream, batch size): results of calls on different streams stay apart
         self._fused_out: dict = {}  # per (stream, batch size, out_k): the fusion's outputs
         self._side: dict = {}       # per caller stream: (side stream, fork event, join event)
+
+    def _dedupe(self, fused, nq: int, ok: int, stream: int, dev) -> Dict[str, torch.Tensor]:
+        """The fused lists deduped on `stream`: one kernel, then the scores and lane masks of the kept slots moved up
+        (a scatter of the slot numbers to their new places, two gathers), padded like rrf_fuse's (NaN / 0)."""
+        with _on_stream(stream, dev):
+            d = self._dedupe_out.get((stream, nq, ok))
+            if d is None:
+                d = self._dedupe_out[(stream, nq, ok)] = {
+                    "ids": torch.empty(nq, ok, dtype=torch.int64, device=dev),
+                    "counts": torch.empty(nq, dtype=torch.int32, device=dev),
+                    "dup_of": torch.empty(nq, ok, dtype=torch.int32, device=dev),
+                    "dup_sim": torch.empty(nq, ok, dtype=torch.float32, device=dev),
+                    "scores": torch.empty(nq, ok, dtype=torch.float64, device=dev),
+                    "lanes": torch.empty(nq, ok, dtype=torch.int32, device=dev),
+                    "_col": torch.arange(ok, dtype=torch.int64, device=dev).expand(nq, ok).contiguous(),
+                    "_src": torch.empty(nq, ok + 1, dtype=torch.int64, device=dev)}   # (last column: the dropped slots' dump)
+            self.index.dedupe_async(fused["ids"], fused["counts"], self.dedupe_cosine, d["ids"], d["counts"], d["dup_of"],
+                                    d["dup_sim"], stream=stream)
+            col, src = d["_col"], d["_src"]
+            keep = (d["dup_of"] < 0) & (col < fused["counts"].unsqueeze(1))
+            dest = torch.where(keep, torch.cumsum(keep, dim=1) - 1, ok)
+            src.zero_()
+            src.scatter_(1, dest, col)
+            pad = col >= d["counts"].unsqueeze(1)
+            torch.gather(fused["scores"], 1, src[:, :ok], out=d["scores"])
+            torch.gather(fused["lanes"], 1, src[:, :ok], out=d["lanes"])
+            d["scores"].masked_fill_(pad, float("nan"))
+            d["lanes"].masked_fill_(pad, 0)
+        return {k: v for k, v in d.items() if not k.startswith("_")}
 
     def search(self, query_vectors: torch.Tensor, query_token_lists=None, bm25=None, *, out_k: int = 0,
                row_mask=None, mask_stride: int = 0, stream: int = 0, query_texts=None) -> Dict[str, torch.Tensor]:
@@ -373,6 +409,8 @@ class HybridSearcher:
         lanes.append((d_ids, d_ct))
         width = sum(int(t.shape[1]) for t, _ in lanes)
         ok = out_k or width
+        if self.dedupe_cosine is not None and ok > _native.CRAG_DEDUPE_MAX_WIDTH:
+            raise ValueError(f"dedupe_cosine takes fused lists of at most {_native.CRAG_DEDUPE_MAX_WIDTH} ids (got {ok})")
         fused = self._fused_out.get((stream, nq, ok))
         if fused is None:   # like the dense buffers: reused by the next call with the same stream and batch shape
             with _on_stream(stream, dev):
@@ -382,6 +420,8 @@ class HybridSearcher:
                     "lanes": torch.empty(nq, ok, dtype=torch.int32, device=dev),
                     "counts": torch.empty(nq, dtype=torch.int32, device=dev)}
         out = dict(rrf_fuse(lanes, out_k=ok, rrf_k=self.rrf_k, stream=stream, out=fused))
+        if self.dedupe_cosine is not None:
+            out.update(self._dedupe(fused, nq, ok, stream, dev))
         out["dense_ids"], out["dense_scores"], out["dense_counts"] = d_ids, d_sc, d_ct
         if bm25_native is not None:
             out["bm25_ids"], out["bm25_scores"], out["bm25_counts"] = bm25_native

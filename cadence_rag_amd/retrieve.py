@@ -447,6 +447,16 @@ class DenseTable:
             return lane
         return self.build_bm25_lane(lane.text_column)
 
+    def dedupe(self, ids, threshold: float) -> List[Tuple[Optional[int], Optional[float]]]:
+        """Greedy near-duplicate suppression of one ranked list of row ids (best first, at most 256) over the stored
+        vectors (DenseIndex.dedupe): per input id (slot of the kept, higher-ranked id that is at least `threshold`
+        similar, that cosine), or (None, None) for an id that stays.  Ids without a stored vector always stay."""
+        ids = [int(v) for v in ids]
+        if not ids or len(self) == 0:
+            return [(None, None)] * len(ids)
+        _, dup_of, sim = self.index.dedupe(np.asarray(ids, dtype=np.int64), float(threshold))
+        return [(None, None) if d < 0 else (int(d), float(c)) for d, c in zip(dup_of, sim)]
+
     def _positions(self) -> Dict[int, int]:
         if getattr(self, "_pos_of_id", None) is None:
             self._pos_of_id = {int(v): i for i, v in enumerate(self.columns[self.id_field])}
@@ -551,6 +561,11 @@ class RetrieveBackend:
     def fetch_chunks_dense(self, query_embedding, filters, call_ids, mode, limit): return []
     def fetch_artifacts_dense(self, query_embedding, filters, call_ids, mode, limit): return []
 
+    def dedupe(self, table_name, ids, threshold):
+        """Near-duplicate suppression of one side's fused ids (best first): per id (slot of the kept id that suppresses
+        it, their cosine) or (None, None).  A backend without vectors drops nothing."""
+        return [(None, None)] * len(ids)
+
 
 class GpuRetrieveBackend(RetrieveBackend):
     """Dense lanes from the HBM-resident DenseTables, exact-token lanes from GPU TechTokenIndex objects
@@ -639,6 +654,9 @@ class GpuRetrieveBackend(RetrieveBackend):
 
     def fetch_artifacts_dense(self, query_embedding, filters, call_ids, mode, limit):
         return _fetch_artifacts_dense(self.tables["artifact_chunks"], query_embedding, filters, call_ids, mode, limit)
+
+    def dedupe(self, table_name, ids, threshold):
+        return self.tables[table_name].dedupe(ids, threshold)
 
 
 _backend: Optional[RetrieveBackend] = None
@@ -792,6 +810,41 @@ class _RerankState:
         return out
 
 
+DEDUPE_MAX_ROWS = 256   # fused rows of a side that are examined (CRAG_DEDUPE_MAX_WIDTH); later rows pass through
+
+
+class _DedupeState:
+    """What near-duplicate suppression did to one request (echoed in notes / debug when the knob is on)."""
+
+    def __init__(self) -> None:
+        self.cosine = float(settings.evidence_dedupe_cosine or 0.0)
+        self.on = self.cosine != 0.0
+        self.dropped: Dict[str, int] = {s.table: 0 for s in _QUERY_ORDER}
+        self.pairs: Dict[str, List[Dict[str, Any]]] = {s.debug_key: [] for s in _QUERY_ORDER}
+
+    def apply(self, be: "RetrieveBackend", fused: Dict[str, List[Tuple[Dict[str, Any], Any, float]]]):
+        """Per side, in front of the reranker: a fused row goes when a kept, higher-ranked row of its side is at least
+        `cosine` similar to it -- the copy RRF ranked higher survives and duplicates cost no reranker slots."""
+        if not self.on:
+            return fused
+        out = dict(fused)
+        for s in _QUERY_ORDER:
+            rows = fused[s.table]
+            ids = [row[s.id_field] for row, _, _ in rows[:DEDUPE_MAX_ROWS]]
+            if not ids:
+                continue
+            verdict = be.dedupe(s.table, ids, self.cosine)
+            kept = []
+            for slot, (dup_of, cos) in enumerate(verdict):
+                if dup_of is None:
+                    kept.append(rows[slot])
+                else:
+                    self.pairs[s.debug_key].append({"dropped": ids[slot], "kept": ids[dup_of], "cosine": cos})
+            self.dropped[s.table] = len(ids) - len(kept)
+            out[s.table] = kept + list(rows[len(ids):])
+        return out
+
+
 def _gather_lanes(be: "RetrieveBackend", query: str, tokens: List[str], filters, dense: _DenseState
                   ) -> Dict[str, Dict[str, Sequence[Dict[str, Any]]]]:
     """table -> {lane name -> rows}, lanes in fusion order (bm25, tech_tokens, dense)."""
@@ -828,7 +881,8 @@ def _debug_section(lanes, dense: _DenseState) -> Dict[str, Any]:
     }
 
 
-def _retrieval_notes(tokens: List[str], dense: _DenseState, rerank: Optional[_RerankState] = None) -> Dict[str, Any]:
+def _retrieval_notes(tokens: List[str], dense: _DenseState, rerank: Optional[_RerankState] = None,
+                     dedupe: Optional[_DedupeState] = None) -> Dict[str, Any]:
     chunks, artifacts = _BY_TABLE["chunks"], _BY_TABLE["artifact_chunks"]
     notes = {
         "planner": dense.planner,
@@ -851,6 +905,9 @@ def _retrieval_notes(tokens: List[str], dense: _DenseState, rerank: Optional[_Re
         notes["reranked_from"] = rerank.scored
         notes["rerank_model_id"] = rerank.model_id
         notes["rerank_error"] = rerank.error
+    if dedupe is not None and dedupe.on:   # likewise
+        notes["dedupe_cosine"] = dedupe.cosine
+        notes["dedupe_dropped"] = dict(dedupe.dropped)
     return notes
 
 
@@ -880,6 +937,8 @@ def retrieve_evidence(payload: RetrieveRequest, backend: Optional[RetrieveBacken
     dense.embed(query)
     lanes = _gather_lanes(be, query, tokens, payload.filters, dense)
     fused = {s.table: _rrf_merge(lanes[s.table], s.id_field) for s in _SIDES}
+    dedupe = _DedupeState()
+    fused = dedupe.apply(be, fused)
     rerank = _RerankState()
     fused = rerank.apply(query, fused)
 
@@ -894,7 +953,9 @@ def retrieve_evidence(payload: RetrieveRequest, backend: Optional[RetrieveBacken
             cap = None if s.list_cap is None else min(s.list_cap, budget.max_evidence_items)
             packed[s.out] = _pack(fused[s.table], s, purse, cap)
         response = {**head, "intent": payload.intent, "budget": budget.model_dump(), **packed,
-                    "notes": {"retrieval": _retrieval_notes(tokens, dense, rerank)}}
+                    "notes": {"retrieval": _retrieval_notes(tokens, dense, rerank, dedupe)}}
     if payload.debug:
         response["debug"] = _debug_section(lanes, dense)
+        if dedupe.on:
+            response["debug"]["dedupe"] = {key: list(pairs) for key, pairs in dedupe.pairs.items()}
     return response

@@ -176,6 +176,33 @@ int crag_index_search_pipelined(crag_index *ix, const float *d_queries, int nq, 
                                 float *d_out_scores, int32_t *d_out_counts, void *stream, int flags);
 int crag_index_join(crag_index *ix, void *stream);
 
+/* Near-duplicate suppression of ranked lists (hybrid /retrieve: the fused list of a side before it reaches the reranker
+ * and the evidence pack).  Stands in for: the redundancy control the reference plans but has NO code for yet --
+ * PHASED_PLAN.md:299-303 "enforce per-call diversity caps and dedupe rules" and IMPLEMENTATION_PLAN.md:150-158 "Top
+ * evidence is not overly redundant (dedupe + per-call caps)"; the per-call cap exists on both sides, the dedupe rule is
+ * defined here.  Per query the list is walked in rank order: item i is DROPPED iff some KEPT item j < i has
+ * cos(row_i, row_j) >= threshold, else kept (greedy over the kept set: a ~ b, b ~ c, a !~ c keeps a and c).  An id that
+ * is not stored, the -1 pad and a stored row with a zero or non-finite norm are always kept and never suppress; a
+ * repeated id is a pair like any other (cosine 1 with itself).
+ *   cos(i, j) = clamp(dot(i, j) * (inv_norm[i] * inv_norm[j]), -1, 1), dot a fixed-order fp32 accumulation over the raw
+ *   stored rows: cos(i, j) and cos(j, i) are the same bits, which depend on the two rows only (not on the slot, width,
+ *   nq or the rows' positions).  They need not equal the bits of a search score.
+ *   d_ids [nq, width] best first; d_counts [nq], clamped to [0, width] -- the shape crag_rrf_fuse emits
+ *   threshold       finite, in (-1, 1]
+ *   d_out_ids [nq, width]     the kept ids in their original order, -1 padded (may be d_ids itself)
+ *   d_out_counts [nq]         (may be d_counts itself)
+ *   d_out_dup_of [nq, width]  nullable: per INPUT slot -1 if the item is kept (or lies beyond the count), else the input
+ *                             slot of the item that suppressed it (the lowest kept one at or above the threshold)
+ *   d_out_sim [nq, width]     nullable: that pair's cosine, NaN where the item is kept
+ * All pointers DEVICE; one launch on `stream`, no host synchronisation, no workspace of the index.  Ordering against
+ * edits as for crag_index_search_async (edits synchronise the device first).
+ * CRAG_EINVAL, nothing enqueued: NULL index or required pointer, nq < 0, width < 1, width > CRAG_DEDUPE_MAX_WIDTH, a
+ * non-finite or out-of-range threshold.  nq == 0 is CRAG_OK. */
+#define CRAG_DEDUPE_MAX_WIDTH 256
+int crag_index_dedupe_async(crag_index *ix, const int64_t *d_ids, const int32_t *d_counts, int nq, int width,
+                            float threshold, int64_t *d_out_ids, int32_t *d_out_counts,
+                            int32_t *d_out_dup_of, float *d_out_sim, void *stream);
+
 /* Merge per-shard results (the multi-GPU exchange step: each rank's [nq, k] top-k after an
  * RCCL all-gather) into the global top-k.  All pointers DEVICE.
  *   d_ids/d_scores/d_counts  [n_lists, nq, k] / [n_lists, nq, k] / [n_lists, nq]
