@@ -18,6 +18,7 @@ LIB_PATH = Path(os.environ["CRAG_DENSE_LIB"]) if os.environ.get("CRAG_DENSE_LIB"
 CRAG_MAX_K = 128
 CRAG_DIM = 1024
 CRAG_DEDUPE_MAX_WIDTH = 256
+CRAG_FILTER_MAX_QUERIES = 64
 
 # every symbol include/crag_dense.h declares: name -> (restype, argtypes)
 _c = ctypes
@@ -52,6 +53,7 @@ SIGNATURES = {
     "crag_bm25_scratch_bytes": (_c.c_int64, [_c.c_int64, _c.c_int, _c.c_int]),
     "crag_bm25_lane_host": (_c.c_int, [_P, _P, _P, _P, _P, _c.c_int64, _c.c_int64, _c.c_float, _P, _P, _P, _c.c_int, _c.c_int,
                                        _P, _c.c_int64, _P, _P, _c.c_int64, _P, _P, _P, _P]),
+    "crag_filter_masks_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P, _P, _c.c_int, _P, _P, _c.c_int64, _P]),
     "crag_index_profile_enable": (_c.c_int, [_P, _c.c_int]),
     "crag_index_profile_read": (_c.c_int, [_P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_double),
                                            _c.POINTER(_c.c_double)]),

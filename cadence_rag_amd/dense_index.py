@@ -176,22 +176,36 @@ class DenseIndex:
             packed = np.pad(packed, width)
         return np.ascontiguousarray(packed)
 
-    def count_eligible(self, row_mask: Optional[np.ndarray] = None) -> int:
+    @staticmethod
+    def _mask_arg(row_mask):
+        """(pointer, array-like kept alive) of a packed mask given as numpy bytes or as a uint8 CUDA tensor (the C ABI
+        detects the pointer kind).  A device mask must be complete in memory: the synchronous entries run on a stream
+        of their own."""
+        if _is_torch(row_mask):
+            if row_mask.dtype != torch.uint8 or not row_mask.is_cuda or not row_mask.is_contiguous():
+                raise ValueError("a tensor row_mask must be a contiguous uint8 CUDA tensor")
+            return (row_mask.data_ptr() or None), row_mask
+        row_mask = np.ascontiguousarray(np.asarray(row_mask, dtype=np.uint8))
+        return row_mask.ctypes.data, row_mask
+
+    def count_eligible(self, row_mask=None) -> int:
+        """Rows a search could return under the (shared) mask: numpy bytes from pack_mask() or a uint8 CUDA tensor."""
         out = ctypes.c_int64(0)
         ptr = None
         if row_mask is not None:
-            row_mask = np.ascontiguousarray(np.asarray(row_mask, dtype=np.uint8))
-            ptr = row_mask.ctypes.data
+            ptr, row_mask = self._mask_arg(row_mask)
+            if row_mask.shape[-1] < ((len(self) + 31) // 32) * 4 and _is_torch(row_mask):
+                raise ValueError("a device row_mask needs ceil(size/32)*4 bytes")
         _native.check(self._lib.crag_index_count_eligible(self._h, ptr, ctypes.byref(out)),
                       "crag_index_count_eligible")
         return int(out.value)
 
     # -- search ----------------------------------------------------------------------------
-    def search(self, queries, k: int, row_mask: Optional[np.ndarray] = None
-               ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def search(self, queries, k: int, row_mask=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Synchronous exact top-k.  Returns (ids [nq,k] int64 (-1 pad), scores [nq,k] float32
-        (NaN pad), counts [nq] int32).  row_mask: packed bits from pack_mask(), shape
-        [bytes] (shared) or [nq, bytes] (per query)."""
+        (NaN pad), counts [nq] int32).  row_mask: packed bits from pack_mask() or a uint8 CUDA tensor in the same
+        encoding (DenseTable.filter_mask_device; complete in memory), shape [bytes] (shared) or [nq, bytes] (per
+        query)."""
         ptr, nq, keep = _as_f32_2d(queries, self.dim, "queries")
         if not 1 <= int(k) <= _native.CRAG_MAX_K:
             raise ValueError(f"k must be in [1, {_native.CRAG_MAX_K}] (got {k})")
@@ -200,17 +214,16 @@ class DenseIndex:
         out_counts = np.empty((nq,), dtype=np.int32)
         mptr, stride = None, 0
         if row_mask is not None:
-            row_mask = np.ascontiguousarray(np.asarray(row_mask, dtype=np.uint8))
+            mptr, row_mask = self._mask_arg(row_mask)
             need = ((len(self) + 31) // 32) * 4
             if row_mask.shape[-1] < need:
                 raise ValueError(f"row_mask needs {need} bytes per row (use pack_mask)")
             if row_mask.ndim == 2:
                 if row_mask.shape[0] != nq:
                     raise ValueError("per-query row_mask must have one row per query")
-                stride = row_mask.shape[1]
+                stride = int(row_mask.shape[1])
                 if stride % 4:
                     raise ValueError("row_mask row stride must be a multiple of 4 bytes")
-            mptr = row_mask.ctypes.data
         _native.check(self._lib.crag_index_search(self._h, ptr, nq, int(k), mptr, stride,
                                                   out_ids.ctypes.data, out_scores.ctypes.data,
                                                   out_counts.ctypes.data), "crag_index_search")

@@ -127,11 +127,18 @@ class DenseTable:
         # per-row tech_tokens (the `tech_tokens text[]` column), kept once a tech lane was built so that the lane
         # can be rebuilt when the table changes; None = not tracked
         self.tech_tokens: Optional[List[List[str]]] = None
+        # device filter columns (cadence_rag_amd.filters), built on first use per generation, and the one mask the
+        # lanes of a request share
+        self._filter_cols = None
+        self._mask_memo: Optional[Tuple[Any, Any]] = None
 
     def __len__(self) -> int:
         return len(self.index)
 
     def close(self) -> None:
+        if self._filter_cols is not None:
+            self._filter_cols.close()
+        self._filter_cols = self._mask_memo = None
         self.index.close()
 
     def _take_tokens(self, columns: Dict[str, Sequence[Any]], n: int) -> Tuple[Dict[str, Sequence[Any]], List[List[str]]]:
@@ -327,10 +334,66 @@ class DenseTable:
                 land(np.fromiter((c in ok_calls for c in self.call_ids), dtype=bool, count=n))
         return keep
 
+    # -- the same clause evaluated on the GPU (cadence_rag_amd.filters, crag_filter_masks_host) ----------
+    def filter_columns(self):
+        """The table's device filter columns (FilterColumns: call_started_at and the call number of every row in
+        HBM, 12 bytes per row), built in one host pass on first use and again when `generation` or the length
+        changed -- the way the exact-token and BM25 lanes follow the generation."""
+        import torch
+
+        from .filters import FilterColumns
+        cols = self._filter_cols
+        if cols is None or cols.generation != self.generation or cols.n != len(self):
+            if cols is not None:
+                torch.cuda.synchronize(self.index.device)   # a mask kernel in flight may still read the old columns
+                cols.close()
+            self._mask_memo = None
+            cols = self._filter_cols = FilterColumns(self.call_started_at, self.call_ids,
+                                                     device=torch.device("cuda", self.index.device),
+                                                     generation=self.generation)
+        return cols
+
+    def filter_masks_device(self, batch: Sequence[Tuple[Optional[RetrieveFilters], Optional[Sequence[UUID]]]],
+                            stream: Optional[int] = None):
+        """Per-query masks for a batch of up to 64 (filters, call_ids) pairs -- the arguments of `filter_mask` --
+        built by one kernel launch: (uint8 CUDA tensor [nq, stride], stride), what HybridSearcher.search(row_mask=,
+        mask_stride=) and the lanes take.  An unfiltered query gets all ones up to len(self).  Enqueued on `stream`
+        (default: torch's current stream) without a host synchronisation: a consumer on another stream orders itself
+        behind it.  More than 64 queries: ValueError, the caller splits."""
+        from .filters import compile_predicates
+        batch = list(batch)
+        if not batch:
+            raise ValueError("filter_masks_device needs at least one query")
+        cols = self.filter_columns()
+        out = cols.masks(*compile_predicates(cols, self.call_tags, batch), stream=stream)
+        return out, int(out.shape[1])
+
+    def filter_mask_device(self, filters: Optional[RetrieveFilters], call_ids: Optional[Sequence[UUID]]):
+        """`filter_mask` on the GPU: the packed mask as a uint8 CUDA tensor [ceil(n/32)*4] (== pack_mask(filter_mask(..))),
+        or None exactly when `filter_mask` returns None.  No pass over the rows on the host.  The mask is COMPLETE on
+        return (the producing stream is synchronised once), so the synchronous entries of the index, which run on a
+        stream of their own, may read it; the lanes of one request ask for the same predicates eight times and get the
+        same tensor (a one-entry memo per table, dropped with the generation).  `call_tags` that change reach the memo
+        through `add` / `insert`, which bump the generation."""
+        import torch
+
+        from .filters import compile_predicates
+        if not filters or not (filters.date_from or filters.date_to or call_ids is not None or filters.call_tags):
+            return None
+        cols = self.filter_columns()
+        key = (cols.generation, cols.n, filters.date_from, filters.date_to,
+               None if call_ids is None else tuple(call_ids), tuple(filters.call_tags or ()))
+        if self._mask_memo is not None and self._mask_memo[0] == key:
+            return self._mask_memo[1]
+        compiled = compile_predicates(cols, self.call_tags, [(filters, call_ids)])
+        mask = cols.masks(*compiled)[0]
+        torch.cuda.current_stream(cols.device).synchronize()
+        self._mask_memo = (key, mask)
+        return mask
+
     def estimate_candidates(self, filters: Optional[RetrieveFilters], call_ids: Optional[Sequence[UUID]]) -> int:
         """COUNT(*) ... WHERE <filters> AND embedding IS NOT NULL (retrieve.py:303-323)."""
-        mask = self.filter_mask(filters, call_ids)
-        return self.index.count_eligible(None if mask is None else DenseIndex.pack_mask(mask))
+        return self.index.count_eligible(self.filter_mask_device(filters, call_ids))
 
     def fetch_dense(self, query_embedding, filters: Optional[RetrieveFilters],
                     call_ids: Optional[Sequence[UUID]], mode: str, limit: int,
@@ -340,10 +403,9 @@ class DenseTable:
         if len(self) == 0 or limit <= 0:
             return []
         q = _parse_vector(query_embedding)
-        mask = self.filter_mask(filters, call_ids)
-        packed = None if mask is None else DenseIndex.pack_mask(mask)
         rows: List[Dict[str, Any]] = []
-        ids, scores, counts = self.index.search(q[None, :], min(int(limit), _native_max_k()), row_mask=packed)
+        ids, scores, counts = self.index.search(q[None, :], min(int(limit), _native_max_k()),
+                                                row_mask=self.filter_mask_device(filters, call_ids))
         pos_of = self._positions()
         for rid, sc in zip(ids[0, :counts[0]], scores[0, :counts[0]]):
             pos = pos_of[int(rid)]
@@ -584,6 +646,18 @@ class GpuRetrieveBackend(RetrieveBackend):
     def resolve_call_ids(self, filters):
         return _resolve_call_ids(self.calls, filters)
 
+    @staticmethod
+    def _lane_mask(table, lane, filters, call_ids):
+        """The request's filters as the packed device mask of a lane over `table`: a DenseTable evaluates them on the GPU
+        (filter_mask_device); a duck-typed table that brings only the host form `filter_mask` has it packed and
+        uploaded."""
+        on_device = getattr(table, "filter_mask_device", None)
+        if on_device is not None:
+            return on_device(filters, call_ids)
+        import torch
+        mask = table.filter_mask(filters, call_ids)
+        return None if mask is None else torch.from_numpy(DenseIndex.pack_mask(mask)).to(lane.device)
+
     def _bm25_rows(self, name, select, query, filters, call_ids, limit):
         """retrieve.py:123-180: the SELECTed columns + `score`, best first."""
         fn, table = self._bm25[name], self.tables[name]
@@ -593,12 +667,8 @@ class GpuRetrieveBackend(RetrieveBackend):
             return list(fn(query, filters, call_ids, limit))
         if len(table) == 0 or int(limit) <= 0:
             return []
-        import torch
         lane = self._bm25[name] = table.sync_bm25_lane(fn)
-        mask = table.filter_mask(filters, call_ids)
-        d_mask = None
-        if mask is not None:
-            d_mask = torch.from_numpy(DenseIndex.pack_mask(mask)).to(lane.device)
+        d_mask = self._lane_mask(table, lane, filters, call_ids)
         ids, scores, counts = lane.search([query], min(int(limit), _native_max_k()), row_mask=d_mask, mask_stride=0)
         n = int(counts[0])
         pos_of = table._positions()
@@ -620,7 +690,6 @@ class GpuRetrieveBackend(RetrieveBackend):
         lane, table = self._tech[name], self.tables[name]
         if not tokens or lane is None or len(table) == 0:
             return []
-        import torch
         if getattr(lane, "table_generation", table.generation) != table.generation or lane.n != len(table):
             # rows were appended or moved since the lane was built: its row positions (and with them every packed
             # mask bit) no longer mean the table's rows
@@ -628,10 +697,7 @@ class GpuRetrieveBackend(RetrieveBackend):
                 raise RuntimeError(f"the exact-token lane of {name} is stale (table generation {table.generation}) "
                                    "and the table does not track tech_tokens: rebuild it with build_tech_lane")
             lane = self._tech[name] = table.build_tech_lane()
-        mask = table.filter_mask(filters, call_ids)
-        d_mask = None
-        if mask is not None:
-            d_mask = torch.from_numpy(DenseIndex.pack_mask(mask)).to(lane.device)
+        d_mask = self._lane_mask(table, lane, filters, call_ids)
         ids, counts = lane.search([list(tokens)], int(limit), row_mask=d_mask, mask_stride=0)
         pos_of = table._positions()
         out = []

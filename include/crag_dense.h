@@ -293,6 +293,33 @@ int crag_bm25_lane_host(const int64_t *d_post_ptr, const int32_t *d_post_pos, co
                         int64_t scratch_bytes, int64_t *d_out_ids, float *d_out_scores, int32_t *d_out_counts,
                         void *stream);
 
+/* Filter row masks for up to 64 queries, built on the device from device-resident columns: the producer of the
+ * `row_mask` every lane above takes (crag_index_search*, crag_index_count_eligible, crag_tech_lane*, crag_bm25_lane_host).
+ * Replaces: _build_filter_clause (retrieve.py:93-120) -- call_started_at >= :date_from, <= :date_to, call_id = ANY(:ids),
+ * calls.tags && :tags; the last two arrive resolved to the table's call dictionary (cadence_rag_amd.filters).
+ *   d_started_us [n_rows] int64  the row's call_started_at in us since the epoch; INT64_MIN = NULL / NaT
+ *   d_call_slot [n_rows] int32   the dense number, in [0, n_calls), of the row's call
+ *   h_call_qset [n_calls] HOST, nullable: bit q of word c set <=> query q admits call c (a query without call scoping has
+ *                                its bit set in every word; NULL: no query is call-scoped)
+ *   h_date_from, h_date_to [nq] HOST: inclusive bounds in us; INT64_MIN = no lower bound, INT64_MAX = no upper bound
+ * Bit (q, i) is set iff   (h_call_qset == NULL or 0 <= slot[i] < n_calls and bit q of qset[slot[i]] is set)
+ *                     and (from[q] == INT64_MIN or started[i] != INT64_MIN and started[i] >= from[q])
+ *                     and (to[q]   == INT64_MAX or started[i] != INT64_MIN and started[i] <= to[q]).
+ * A NULL timestamp passes a query without a date bound and fails one with any (what SQL and numpy do with NULL / NaT);
+ * a slot outside [0, n_calls) is never dereferenced: with h_call_qset given that row passes no query.
+ *   d_out_mask  nq runs of mask_stride bytes in the row_mask encoding of crag_index_search (4-byte aligned); mask_stride a
+ *               multiple of 4 >= ceil(n_rows/32)*4.  EVERY byte of every run is written -- bits at positions >= n_rows
+ *               and the bytes up to mask_stride are 0 --, nothing outside nq * mask_stride bytes is; plain stores, never
+ *               OR: the buffer may be uninitialised and reused.  The output depends on the input alone.
+ *   slot        an upload slot as for crag_tech_lane_host: ONE host-to-device copy per call (bounds + qset)
+ * Everything is enqueued on `stream`, no host synchronisation.  CRAG_EINVAL with a message, checked before any HIP call
+ * and nothing enqueued: NULL required pointer, nq < 1, nq > 64, n_rows < 0, n_rows >= 2^31, n_calls < 0, bad mask_stride.
+ * n_rows == 0 is CRAG_OK (the runs are zeroed when mask_stride > 0). */
+#define CRAG_FILTER_MAX_QUERIES 64
+int crag_filter_masks_host(const int64_t *d_started_us, const int32_t *d_call_slot, int64_t n_rows, int64_t n_calls,
+                           const uint64_t *h_call_qset, const int64_t *h_date_from, const int64_t *h_date_to, int nq,
+                           crag_upload_slot *slot, uint8_t *d_out_mask, int64_t mask_stride, void *stream);
+
 /* Live kernel timing for bench.py's roofline: enabled = N > 0 records HIP events around the scan
  * (and merge) kernel of every N-th search, on the stream it is launched on (N = 1: every search;
  * larger N perturbs the timed region less); 0 disables.  crag_index_profile_read sums and clears
