@@ -1115,6 +1115,52 @@ int crag_index_dedupe_async(crag_index *ix, const int64_t *d_ids, const int32_t 
     return CRAG_OK;
 }
 
+int64_t crag_index_search_ids_scratch_bytes(int nq, int width) { return crag::subset_scratch_bytes(nq, width); }
+
+int crag_index_search_ids_async(crag_index *ix, const float *d_queries, int nq, const int64_t *d_ids,
+                                const int32_t *d_counts, int width, int64_t list_stride, int k, int64_t *d_out_ids,
+                                float *d_out_scores, int32_t *d_out_counts, float *d_out_slot_scores, void *d_scratch,
+                                int64_t scratch_bytes, void *stream) {
+    if (!ix) return fail(CRAG_EINVAL, "search_ids: index is NULL");
+    if (nq < 0 || nq > 65535) return fail(CRAG_EINVAL, "search_ids: nq must be in [0, 65535] (got %d)", nq);
+    if (width < 1) return fail(CRAG_EINVAL, "search_ids: width must be >= 1 (got %d)", width);
+    if (k < 1 || k > CRAG_MAX_K) return fail(CRAG_EINVAL, "search_ids: k must be in [1, %d] (got %d)", CRAG_MAX_K, k);
+    if (list_stride != 0 && list_stride != width)
+        return fail(CRAG_EINVAL, "search_ids: list_stride must be 0 (one shared list) or width (got %lld)",
+                    (long long)list_stride);
+    if (!d_queries || !d_ids || !d_counts || !d_out_ids || !d_out_scores || !d_out_counts || !d_scratch)
+        return fail(CRAG_EINVAL, "search_ids: queries / ids / counts / outputs / scratch must not be NULL");
+    if (width > CRAG_SUBSET_MAX_WIDTH)
+        return fail(CRAG_E2BIG, "search_ids: width %d exceeds CRAG_SUBSET_MAX_WIDTH (%d): use the row_mask route", width,
+                    CRAG_SUBSET_MAX_WIDTH);
+    if (scratch_bytes < crag::subset_scratch_bytes(nq, width) || ((uintptr_t)d_scratch & 7))
+        return fail(CRAG_EINVAL, "search_ids: scratch too small or not 8-byte aligned (crag_index_search_ids_scratch_bytes)");
+    if (nq == 0) return CRAG_OK;
+    std::lock_guard<std::mutex> lk(ix->mu);
+    DeviceGuard guard(ix->device);
+    crag::SubsetParams p;
+    p.corpus = ix->corpus;
+    p.inv_norm = ix->inv_norm;
+    p.stored = ix->ids;
+    p.size = ix->size;
+    p.piece_shift = crag::crag_piece_shift(ix->corpus16 != nullptr);
+    p.queries = d_queries;
+    p.nq = nq;
+    p.dim = ix->dim;
+    p.k = k;
+    p.ids = d_ids;
+    p.counts = d_counts;
+    p.width = width;
+    p.list_stride = list_stride;
+    p.keys = (uint64_t *)d_scratch;
+    p.out_ids = d_out_ids;
+    p.out_scores = d_out_scores;
+    p.out_counts = d_out_counts;
+    p.out_slot_scores = d_out_slot_scores;
+    HIP_TRY(crag::launch_subset(p, (hipStream_t)stream));
+    return CRAG_OK;
+}
+
 int crag_index_search(crag_index *ix, const float *queries, int nq, int k, const uint8_t *row_mask,
                       int64_t mask_stride, int64_t *out_ids, float *out_scores, int32_t *out_counts) {
     int rc = check_search_args(ix, queries, nq, k, row_mask, mask_stride, out_ids, out_scores, out_counts);

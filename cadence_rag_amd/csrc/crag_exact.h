@@ -1,0 +1,102 @@
+// crag_exact.h -- the exact-score arithmetic of the dense lane, in one place: the 64-bit candidate key, the canonical
+// 1/||q||, one 128-dim slice of the exact fp32 dot product and the score -> key expression.  crag_search.hip (the scans
+// and the selection kernel) and crag_subset.hip (the search over id lists) include it, so a (query, row) pair has the same
+// score bits on every path.  Device code only.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "crag_kernels.h"
+#include "crag_layout.h"
+
+namespace crag {
+
+// ------------------------------------------------------------------------------------------
+// key helpers: a candidate is the 64-bit key (orderable(score) << 32) | ~row ; larger = better
+// (higher score, then lower row position).  Key 0 is the "empty" sentinel.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t f2ord(float f) {
+    uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(uint32_t u) {
+    u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+    return __uint_as_float(u);
+}
+__device__ __forceinline__ uint64_t mk64(uint32_t hi, uint32_t lo) {
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// ---- the canonical 1/||q||: ONE piece of arithmetic for every kernel that needs a query's norm -------------------
+// Thread t < 256 holds dims 4t .. 4t+3 of the query (zeros beyond dim / for threads >= 256); squares in fp64, a
+// butterfly sum inside each of the first four waves, the four wave sums added in wave order.  prep_queries_kernel,
+// the selection kernel and the fallback scan all call this, so the exact scores (x 1/||row|| x 1/||q||) are the same
+// bits on every path.  All threads of the workgroup must call it (two barriers); sh: 4 doubles of LDS.
+__device__ __forceinline__ f32x4 load_query_quad(const float *queries, int dim, int q, int nq, int t) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (q < nq && t < 256) {
+        const float *src = queries + (size_t)q * dim;
+        if ((dim & 3) == 0) {
+            if (4 * t < dim) v = *reinterpret_cast<const f32x4 *>(src + 4 * t);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (4 * t + c < dim) v[c] = src[4 * t + c];
+        }
+    }
+    return v;
+}
+
+__device__ __forceinline__ float canonical_qinv(const f32x4 v, bool real_query, double *sh) {
+    double ss = ((double)v[0] * v[0] + (double)v[1] * v[1]) + ((double)v[2] * v[2] + (double)v[3] * v[3]);
+    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+    const int wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0 && wv < 4) sh[wv] = ss;
+    __syncthreads();
+    const double tot = sh[0] + sh[1] + sh[2] + sh[3];
+    __syncthreads();
+    const bool ok = real_query && (tot > 0.0) && (tot < 1.0e300) && (tot == tot);
+    float qinv = ok ? (float)(1.0 / sqrt(tot)) : 0.f;
+    if (!(qinv < 3.0e38f)) qinv = 0.f;
+    return qinv;
+}
+
+// score -> key for one owned (query, row) pair
+// (the pipelined kernels' and the selection kernel's expression, so that all of them produce the same bits:
+// scale = 1/||row|| * 1/||q||, or 0 when the pair is not eligible)
+__device__ __forceinline__ void make_key(float dot, float scale, int64_t row, uint32_t &khi, uint32_t &klo) {
+    float sc = dot * scale;
+    sc = __builtin_amdgcn_fmed3f(sc, -1.f, 1.f);  // pgvector clamps the similarity to [-1, 1]
+    const bool ok = (scale > 0.f) && (sc == sc);
+    khi = ok ? f2ord(sc) : 0u;
+    klo = ok ? ~(uint32_t)row : 0u;
+}
+
+// One 128-dim slice of the exact dot product: the query slice comes from LDS (fragment order), the row's 32
+// float4 are fetched first, all of them (32 independent 16-byte loads in flight, four per 64-byte piece of the
+// row: latency is everything here), then the fmaf chain runs in the scan's k order:
+// s = 0..15, then component, then lane half (k = 0, 1 of one 32x32x2 MFMA).
+template <int PS>
+__device__ __forceinline__ float exact_slice_dot(const f32x4 *qslice /* [16][2] float4 in LDS */,
+                                                 const f32x4 *ctile /* tile base + slice */, int jrow) {
+    f32x4 c0[16], c1[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        // float4 kq = 2s (and 2s + 1) of the slice: piece kq >> PS of the row
+        c0[s] = ctile[(((2 * s) >> PS) * 32 + jrow) * (1 << PS) + ((2 * s) & ((1 << PS) - 1))];
+        c1[s] = ctile[(((2 * s) >> PS) * 32 + jrow) * (1 << PS) + ((2 * s) & ((1 << PS) - 1)) + 1];
+    }
+    float acc = 0.f;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        const f32x4 q0 = qslice[2 * s], q1 = qslice[2 * s + 1];
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) {
+            acc = __builtin_fmaf(q0[cc], c0[s][cc], acc);
+            acc = __builtin_fmaf(q1[cc], c1[s][cc], acc);
+        }
+    }
+    return acc;
+}
+
+}  // namespace crag

@@ -231,4 +231,26 @@ struct DedupeParams {
 };
 hipError_t launch_dedupe(const DedupeParams &p, int nq, hipStream_t st);
 
+// ---- exact top-k and scores over listed rows (crag_subset.hip) ----
+struct SubsetParams {
+    const float *corpus;        // tile32 layout
+    const float *inv_norm;
+    const int64_t *stored;      // [size] ids, ascending with the position
+    int64_t size;
+    int piece_shift;
+    const float *queries;       // [nq, dim] row-major fp32, raw
+    int nq, dim, k;
+    const int64_t *ids;         // [nq, width] lists (list_stride == width) or one shared [width] list (list_stride == 0)
+    const int32_t *counts;      // [nq] / [1], clamped to [0, width]
+    int width;                  // <= CRAG_SUBSET_MAX_WIDTH
+    int64_t list_stride;
+    uint64_t *keys;             // scratch [nq, width]: (orderable score << 32) | ~position per slot, 0 = ignored
+    int64_t *out_ids;           // [nq, k], -1 padded
+    float *out_scores;          // [nq, k], NaN padded
+    int32_t *out_counts;        // [nq]
+    float *out_slot_scores;     // nullable [nq, width]: the score of each input slot, NaN where ignored
+};
+int64_t subset_scratch_bytes(int nq, int width);
+hipError_t launch_subset(const SubsetParams &p, hipStream_t st);
+
 }  // namespace crag

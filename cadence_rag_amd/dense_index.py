@@ -307,6 +307,66 @@ class DenseIndex:
             return res[0]
         return [r[0] for r in res], [r[1] for r in res], [r[2] for r in res]
 
+    # -- exact top-k and scores over listed rows (crag_index_search_ids_async) ----------------------
+    @staticmethod
+    def search_ids_scratch_bytes(nq: int, width: int) -> int:
+        return int(_native.load().crag_index_search_ids_scratch_bytes(int(nq), int(width)))
+
+    def search_ids_async(self, d_queries, d_ids, d_counts, k: int, d_out_ids, d_out_scores, d_out_counts,
+                         d_out_slot_scores=None, shared: bool = False, scratch=None, stream: int = 0) -> None:
+        """The search of `search_async` over LISTED rows only, enqueued on `stream`: d_ids int64 [nq, width <= 4096]
+        (shared=True: one [width] list for every query), d_counts int32 [nq] ([1] when shared).  The outputs are what
+        search_async returns under a mask of the listed ids' positions, bit for bit; d_out_slot_scores fp32
+        [nq, width] (optional) receives the score of every input slot (NaN: beyond the count or ignored).  scratch: a
+        uint8 CUDA tensor of search_ids_scratch_bytes(nq, width) bytes, one per stream in use (default: allocated
+        here).  Arguments are torch CUDA tensors."""
+        nq = int(d_queries.shape[0])
+        if d_ids.dim() != (1 if shared else 2) or (not shared and int(d_ids.shape[0]) != nq):
+            raise ValueError("d_ids must have shape [nq, width], or [width] with shared=True")
+        width = int(d_ids.shape[-1])
+        if scratch is None:
+            scratch = torch.empty(self.search_ids_scratch_bytes(nq, width), dtype=torch.uint8, device=d_ids.device)
+        _native.check(self._lib.crag_index_search_ids_async(
+            self._h, d_queries.data_ptr(), nq, d_ids.data_ptr(), d_counts.data_ptr(), width, 0 if shared else width,
+            int(k), d_out_ids.data_ptr(), d_out_scores.data_ptr(), d_out_counts.data_ptr(),
+            None if d_out_slot_scores is None else d_out_slot_scores.data_ptr(), scratch.data_ptr(),
+            int(scratch.numel()) * scratch.element_size(), ctypes.c_void_p(stream)), "crag_index_search_ids_async")
+
+    def search_ids(self, queries, ids, k: int, slot_scores: bool = False):
+        """Host convenience over search_ids_async: exact top-k of every query among the listed ids -- one flat list
+        shared by all queries, or one list per query (lengths may differ; at most 4096 ids each, ValueError above:
+        use a row_mask).  Returns numpy (ids [nq, k], scores [nq, k], counts [nq]) as `search` does, and with
+        slot_scores=True also [nq, width] scores per input slot (NaN: pad or ignored id).  Synchronises."""
+        if torch is None:  # pragma: no cover
+            raise _native.NativeLibraryError("DenseIndex.search_ids stages its buffers with torch")
+        ptr, nq, keep = _as_f32_2d(queries, self.dim, "queries")
+        if not 1 <= int(k) <= _native.CRAG_MAX_K:
+            raise ValueError(f"k must be in [1, {_native.CRAG_MAX_K}] (got {k})")
+        shared = len(ids) == 0 or np.ndim(ids[0]) == 0
+        lists = [np.asarray(ids, dtype=np.int64).reshape(-1)] if shared else \
+            [np.asarray(l, dtype=np.int64).reshape(-1) for l in ids]
+        if not shared and len(lists) != nq:
+            raise ValueError("per-query id lists must have one list per query")
+        width = max([int(l.size) for l in lists] + [1])
+        if width > _native.CRAG_SUBSET_MAX_WIDTH:
+            raise ValueError(f"a list holds at most {_native.CRAG_SUBSET_MAX_WIDTH} ids (got {width}): use a row_mask")
+        h_ids = np.full((len(lists), width), -1, dtype=np.int64)
+        for q, l in enumerate(lists):
+            h_ids[q, :l.size] = l
+        dev = torch.device("cuda", self.device)
+        d_q = keep.to(dev) if _is_torch(keep) else torch.from_numpy(keep).to(dev)
+        d_ids = torch.from_numpy(h_ids[0] if shared else h_ids).to(dev)
+        d_ct = torch.tensor([int(l.size) for l in lists], dtype=torch.int32, device=dev)
+        out_ids = torch.empty(nq, int(k), dtype=torch.int64, device=dev)
+        out_sc = torch.empty(nq, int(k), dtype=torch.float32, device=dev)
+        out_ct = torch.empty(nq, dtype=torch.int32, device=dev)
+        slot = torch.empty(nq, width, dtype=torch.float32, device=dev) if slot_scores else None
+        if nq:
+            self.search_ids_async(d_q, d_ids, d_ct, k, out_ids, out_sc, out_ct, slot, shared=shared,
+                                  stream=torch.cuda.current_stream(dev).cuda_stream)
+        res = (out_ids.cpu().numpy(), out_sc.cpu().numpy(), out_ct.cpu().numpy())
+        return res + (slot.cpu().numpy(),) if slot_scores else res
+
     # -- profiling / reporting -------------------------------------------------------------
     def profile_enable(self, every: int = 1) -> None:
         """Record HIP events around the scan/merge kernels of every `every`-th search (0 = off)."""

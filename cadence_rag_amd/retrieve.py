@@ -334,6 +334,41 @@ class DenseTable:
                 land(np.fromiter((c in ok_calls for c in self.call_ids), dtype=bool, count=n))
         return keep
 
+    def _call_positions(self) -> Dict[Any, np.ndarray]:
+        """call id -> the ascending positions of its rows, built in one host pass per (generation, length), the way
+        `_positions` is cached."""
+        key = (getattr(self, "generation", 0), len(self))
+        memo = getattr(self, "_call_pos", None)
+        if memo is None or memo[0] != key:
+            by_call: Dict[Any, List[int]] = {}
+            for i, c in enumerate(self.call_ids):
+                by_call.setdefault(c, []).append(i)
+            memo = self._call_pos = (key, {c: np.asarray(v, dtype=np.intp) for c, v in by_call.items()})
+        return memo[1]
+
+    def scoped_positions(self, filters: Optional[RetrieveFilters], call_ids: Optional[Sequence[UUID]],
+                         limit: int) -> Optional[np.ndarray]:
+        """np.flatnonzero(filter_mask(filters, call_ids)) for a call-scoped request, without a pass over all rows:
+        the rows of the scoped calls come from the call -> positions map, the date and tag predicates are applied to
+        those positions only.  None when the route does not apply: `filters` is falsy (filter_mask honours call_ids
+        only under truthy filters), call_ids is None, or the scoped calls together hold more than `limit` rows.
+        Host only."""
+        if not filters or call_ids is None:
+            return None
+        by_call = self._call_positions()
+        parts = [by_call[c] for c in set(call_ids) if c in by_call]
+        if sum(int(p.size) for p in parts) > int(limit):
+            return None
+        if filters.call_tags:
+            tags = set(filters.call_tags)
+            parts = [p for p in parts if tags.intersection(self.call_tags.get(self.call_ids[p[0]]) or ())]
+        pos = np.sort(np.concatenate(parts)) if parts else np.empty((0,), dtype=np.intp)
+        if filters.date_from:
+            pos = pos[self.call_started_at[pos] >= np.datetime64(_naive_utc(filters.date_from), "us")]
+        if filters.date_to:
+            pos = pos[self.call_started_at[pos] <= np.datetime64(_naive_utc(filters.date_to), "us")]
+        return pos
+
     # -- the same clause evaluated on the GPU (cadence_rag_amd.filters, crag_filter_masks_host) ----------
     def filter_columns(self):
         """The table's device filter columns (FilterColumns: call_started_at and the call number of every row in
@@ -404,8 +439,20 @@ class DenseTable:
             return []
         q = _parse_vector(query_embedding)
         rows: List[Dict[str, Any]] = []
-        ids, scores, counts = self.index.search(q[None, :], min(int(limit), _native_max_k()),
-                                                row_mask=self.filter_mask_device(filters, call_ids))
+        # the reference's "exact" dense mode (retrieve.py:277-287): a call-scoped request whose calls hold few rows reads
+        # those rows only (crag_index_search_ids_async) -- the same rows and score bits as the masked scan below
+        from ._native import CRAG_SUBSET_MAX_WIDTH
+        cap = min(max(settings.embeddings_exact_scan_threshold, 0), CRAG_SUBSET_MAX_WIDTH)
+        listed = self.scoped_positions(filters, call_ids, cap) if cap > 0 else None
+        if listed is not None:
+            if listed.size == 0:
+                return []
+            id_col = self.columns[self.id_field]
+            ids, scores, counts = self.index.search_ids(q[None, :], [[int(id_col[i]) for i in listed]],
+                                                        min(int(limit), _native_max_k()))
+        else:
+            ids, scores, counts = self.index.search(q[None, :], min(int(limit), _native_max_k()),
+                                                    row_mask=self.filter_mask_device(filters, call_ids))
         pos_of = self._positions()
         for rid, sc in zip(ids[0, :counts[0]], scores[0, :counts[0]]):
             pos = pos_of[int(rid)]

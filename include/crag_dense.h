@@ -203,6 +203,40 @@ int crag_index_dedupe_async(crag_index *ix, const int64_t *d_ids, const int32_t 
                             float threshold, int64_t *d_out_ids, int32_t *d_out_counts,
                             int32_t *d_out_dup_of, float *d_out_sim, void *stream);
 
+/* Exact cosine top-k and scores over LISTED rows: the id_subset half of search(query_vecs, k, row_mask|id_subset).  Only
+ * the listed rows are read (4 KiB each), where a masked search streams the whole table.
+ * Replaces: the reference's "exact" dense mode -- _choose_dense_mode (retrieve.py:277-287) answers "exact" for a scoped
+ * request whose filters pass at most EMBEDDINGS_EXACT_SCAN_THRESHOLD rows, and `ORDER BY embedding <=> q LIMIT k`
+ * (retrieve.py:339-353) then reads those rows only -- and serves the exact cosine of a query with rows another lane found
+ * (BM25 / exact-token hits for the debug lanes, reranker features).
+ *   d_queries [nq, dim] fp32, raw
+ *   d_ids     [nq, width] int64 when list_stride == width; ONE [width] list shared by all queries when list_stride == 0
+ *             (as mask_stride == 0 means a shared mask)
+ *   d_counts  [nq] ([1] for a shared list), clamped to [0, width]
+ *   d_out_ids [nq, k] (-1 pad), d_out_scores [nq, k] (NaN pad), d_out_counts [nq]: EXACTLY what crag_index_search_async
+ *             returns for the same queries and k under a mask whose set bits are the positions of the listed ids -- ids,
+ *             score bits and counts; descending score, then ascending id.
+ *   d_out_slot_scores  nullable [nq, width]: per INPUT slot the score of (query, that id), the same bits; NaN where the
+ *             slot lies beyond the count or the pair is ignored.  A repeated id receives its score in every slot it holds.
+ *   d_scratch crag_index_search_ids_scratch_bytes(nq, width) bytes, 8-byte aligned, owned by the caller, one per stream in
+ *             use (as for crag_bm25_lane_host)
+ * A list is a set: its order and repeated ids change nothing in the top-k outputs.  An id that is not stored, the -1 pad, a
+ * row with a zero or non-finite norm and every row for a zero or non-finite query are ignored (the count falls
+ * accordingly).  The score of a (query, row) pair depends on those two alone: not on the slot, width, nq, k, shared or
+ * per-query lists, the row's position or the row layout (with or without the fp16 mirror).
+ * All pointers DEVICE; two launches on `stream`, no host synchronisation, no allocation, no workspace of the index.
+ * Ordering against edits as for crag_index_dedupe_async (edits synchronise the device first).  An empty index is valid:
+ * every count is 0.
+ * CRAG_EINVAL, checked before any HIP call, nothing enqueued: NULL index or required pointer, nq < 0 (or > 65535),
+ * width < 1, k outside [1, CRAG_MAX_K], list_stride neither 0 nor width, scratch too small or not 8-byte aligned.
+ * CRAG_E2BIG, nothing enqueued: width > CRAG_SUBSET_MAX_WIDTH -- the caller uses the row_mask route.  nq == 0 is CRAG_OK. */
+#define CRAG_SUBSET_MAX_WIDTH 4096
+int64_t crag_index_search_ids_scratch_bytes(int nq, int width);
+int crag_index_search_ids_async(crag_index *ix, const float *d_queries, int nq, const int64_t *d_ids,
+                                const int32_t *d_counts, int width, int64_t list_stride, int k, int64_t *d_out_ids,
+                                float *d_out_scores, int32_t *d_out_counts, float *d_out_slot_scores, void *d_scratch,
+                                int64_t scratch_bytes, void *stream);
+
 /* Merge per-shard results (the multi-GPU exchange step: each rank's [nq, k] top-k after an
  * RCCL all-gather) into the global top-k.  All pointers DEVICE.
  *   d_ids/d_scores/d_counts  [n_lists, nq, k] / [n_lists, nq, k] / [n_lists, nq]
