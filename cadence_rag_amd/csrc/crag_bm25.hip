@@ -20,6 +20,7 @@
 
 #include "../../include/crag_dense.h"
 #include "crag_kernels.h"
+#include "crag_host.h"
 
 namespace crag {
 namespace {
@@ -263,3 +264,89 @@ hipError_t launch_bm25(const Bm25Params &p, hipStream_t st) {
 }
 
 }  // namespace crag
+
+extern "C" {
+
+// ---- the lane from host query terms (uploaded through the slot of crag_fusion.hip) ----
+
+int64_t crag_bm25_scratch_bytes(int64_t n_rows, int nq, int k) {
+    if (n_rows < 0 || n_rows > INT32_MAX || nq < 0 || nq > crag::BM25_MAX_Q || k <= 0 || k > CRAG_MAX_K) return -1;
+    return crag::bm25_scratch_bytes(n_rows, nq, k);
+}
+
+int crag_bm25_lane_host(const int64_t *d_post_ptr, const int32_t *d_post_pos, const uint16_t *d_post_tf,
+                        const int32_t *d_doc_len, const int64_t *d_ids, int64_t n_rows, int64_t n_terms, float avgdl,
+                        const int32_t *h_q_ptr, const int32_t *h_term_ids, const float *h_weights, int nq, int k,
+                        const uint8_t *d_row_mask, int64_t mask_stride, crag_upload_slot *slot, void *d_scratch,
+                        int64_t scratch_bytes, int64_t *d_out_ids, float *d_out_scores, int32_t *d_out_counts,
+                        void *stream) {
+    // every check comes before the first HIP call: on error nothing is enqueued
+    if (!d_post_ptr || !d_post_pos || !d_post_tf || !d_doc_len || !h_q_ptr || !slot || !d_scratch || !d_out_ids ||
+        !d_out_scores || !d_out_counts)
+        return fail(CRAG_EINVAL, "bm25_lane_host: NULL pointer argument");
+    if (((uintptr_t)d_scratch & 7) != 0) return fail(CRAG_EINVAL, "bm25_lane_host: scratch must be 8-byte aligned");
+    if (nq < 0 || nq > crag::BM25_MAX_Q || k <= 0 || k > CRAG_MAX_K)
+        return fail(CRAG_EINVAL, "bm25_lane_host: need 0 <= nq <= 64 and 1 <= k <= %d (nq=%d k=%d)", CRAG_MAX_K, nq, k);
+    if (n_rows < 0 || n_rows > INT32_MAX || n_terms < 0 || n_terms > INT32_MAX)
+        return fail(CRAG_EINVAL, "bm25_lane_host: n_rows / n_terms out of range");
+    if (n_rows > 0 && !(avgdl > 0.0f && avgdl < 3.0e38f)) return fail(CRAG_EINVAL, "bm25_lane_host: avgdl must be positive and finite");
+    if (d_row_mask) {
+        if (((uintptr_t)d_row_mask & 3) != 0) return fail(CRAG_EINVAL, "bm25_lane_host: row_mask must be 4-byte aligned");
+        if (mask_stride != 0 && (mask_stride % 4 != 0 || mask_stride < (n_rows + 31) / 32 * 4))
+            return fail(CRAG_EINVAL, "bm25_lane_host: mask_stride must be 0 or a multiple of 4 >= ceil(n_rows/32)*4");
+    }
+    if (scratch_bytes < crag::bm25_scratch_bytes(n_rows, nq, k))
+        return fail(CRAG_EINVAL, "bm25_lane_host: scratch too small (crag_bm25_scratch_bytes)");
+    if (nq == 0) return CRAG_OK;
+    if (h_q_ptr[0] != 0) return fail(CRAG_EINVAL, "bm25_lane_host: q_ptr[0] must be 0");
+    for (int q = 0; q < nq; ++q) {
+        const int a = h_q_ptr[q], b = h_q_ptr[q + 1];
+        if (b < a) return fail(CRAG_EINVAL, "bm25_lane_host: q_ptr must not descend");
+        if (b > a && (!h_term_ids || !h_weights)) return fail(CRAG_EINVAL, "bm25_lane_host: NULL term arrays");
+        for (int i = a; i < b; ++i) {
+            if (h_term_ids[i] < 0 || h_term_ids[i] >= n_terms || (i > a && h_term_ids[i] <= h_term_ids[i - 1]))
+                return fail(CRAG_EINVAL, "bm25_lane_host: term ids of a query must ascend strictly inside [0, n_terms)");
+            if (!(h_weights[i] > 0.0f && h_weights[i] < 3.0e38f))
+                return fail(CRAG_EINVAL, "bm25_lane_host: weights must be positive and finite");
+        }
+    }
+    const int nt = h_q_ptr[nq];
+    // slot layout: q_ptr [BM25_MAX_Q + 4] int32 | term ids [nt] int32 | weights [nt] fp32
+    const size_t head = (size_t)(crag::BM25_MAX_Q + 4) * 4;
+    const size_t bytes = head + (size_t)nt * 8;
+    void *h = nullptr, *d = nullptr;
+    int rc = crag_upload_slot_begin_(slot, bytes, &h, &d);
+    if (rc != CRAG_OK) return rc;
+    memcpy(h, h_q_ptr, (size_t)(nq + 1) * 4);
+    if (nt > 0) {
+        memcpy((char *)h + head, h_term_ids, (size_t)nt * 4);
+        memcpy((char *)h + head + (size_t)nt * 4, h_weights, (size_t)nt * 4);
+    }
+    rc = crag_upload_slot_commit_(slot, bytes, stream);
+    if (rc != CRAG_OK) return rc;
+    crag::Bm25Params p;
+    p.post_ptr = d_post_ptr;
+    p.post_pos = d_post_pos;
+    p.post_tf = d_post_tf;
+    p.doc_len = d_doc_len;
+    p.ids = d_ids;
+    p.q_ptr = (const int32_t *)d;
+    p.q_term = (const int32_t *)((const char *)d + head);
+    p.q_w = (const float *)((const char *)d + head + (size_t)nt * 4);
+    p.mask = (const uint32_t *)d_row_mask;
+    p.mask_stride_w = mask_stride / 4;
+    p.n = n_rows;
+    p.n_ranges = (int)((n_rows + crag::BM25_RANGE - 1) / crag::BM25_RANGE);
+    p.nq = nq;
+    p.k = k;
+    p.avgdl = avgdl;
+    p.part_keys = (uint64_t *)d_scratch;
+    p.part_cnt = (int32_t *)((char *)d_scratch + (size_t)p.n_ranges * nq * k * 8);
+    p.out_ids = d_out_ids;
+    p.out_scores = d_out_scores;
+    p.out_counts = d_out_counts;
+    HIP_TRY(crag::launch_bm25(p, (hipStream_t)stream));
+    return CRAG_OK;
+}
+
+}  // extern "C"

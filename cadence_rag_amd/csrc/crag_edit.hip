@@ -6,7 +6,7 @@
 // arithmetic of store_rows_kernel.
 //
 // Moving in place: a removal moves rows to lower positions only, an insertion to higher positions only, but inside
-// one launch a workgroup may write a row that another one still has to read.  The host (crag_api.hip) therefore
+// one launch a workgroup may write a row that another one still has to read.  The host (crag_api_store.hip) therefore
 // works in chunks of C destination rows through a bounce buffer laid out like C rows of the index: source positions
 // of the chunk -> gather into the bounce buffer -> write to the destination, in stream order; chunks ascend for a
 // removal and descend for an insertion, so that no chunk overwrites a row a later chunk reads.  Rows in front of the

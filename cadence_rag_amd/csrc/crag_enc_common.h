@@ -3,13 +3,10 @@
 // bf16 conversion, fragment load, block reduction.  Internal linkage: nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "crag_arch.h"
-
-extern "C" void crag_set_error_(const char *msg);  // defined in crag_api.hip
+#include "crag_host.h"
 
 namespace {
 
@@ -18,27 +15,10 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint16_t u16;
 
-// records the message for crag_last_error(); every C entry point returns through one of these two
-int efail(const char *fmt, ...) {
-    char buf[384];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    crag_set_error_(buf);
-    return -1;
-}
-
-int hip_ok(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[256];
-        snprintf(buf, sizeof(buf), "%s launch failed: %s", what, hipGetErrorString(e));
-        crag_set_error_(buf);
-        return -2;
-    }
-    return 0;
-}
+// records the message for crag_last_error(); every C entry point of the encoder lane returns through one of these
+// two: -1 for a bad argument, -2 behind a launch that failed (the values of CRAG_EINVAL / CRAG_EHIP)
+#define efail(...) fail(-1, __VA_ARGS__)
+int hip_ok(const char *what) { return launch_ok(what); }
 
 __device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((uint32_t)v << 16); }
 __device__ __forceinline__ u16 f2bf(float f) {  // round-to-nearest-even, NaN stays NaN (v_cvt_pk_bf16_f32)

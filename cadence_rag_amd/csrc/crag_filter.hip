@@ -19,15 +19,10 @@
 #include "crag_arch.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <string.h>
 
 #include "../../include/crag_dense.h"
+#include "crag_host.h"
 
-extern "C" void crag_set_error_(const char *msg);  // crag_api.hip
-// the upload slot lives in crag_fusion.hip
-extern "C" int crag_upload_slot_begin_(crag_upload_slot *s, size_t bytes, void **host, void **dev);
-extern "C" int crag_upload_slot_commit_(crag_upload_slot *s, size_t bytes, void *stream);
 
 namespace crag {
 namespace {
@@ -106,11 +101,6 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_masks_kernel(FilterPara
         for (int q = tid >> 5; q < nq; q += FILTER_THREADS / 32) p.out[(int64_t)q * p.stride_w + gw] = s_words[q * FILTER_LDS_STRIDE + w];
 }
 
-int filter_fail(const char *msg) {
-    crag_set_error_(msg);
-    return CRAG_EINVAL;
-}
-
 }  // namespace
 }  // namespace crag
 
@@ -118,17 +108,16 @@ extern "C" int crag_filter_masks_host(const int64_t *d_started_us, const int32_t
                                       int64_t n_calls, const uint64_t *h_call_qset, const int64_t *h_date_from,
                                       const int64_t *h_date_to, int nq, crag_upload_slot *slot, uint8_t *d_out_mask,
                                       int64_t mask_stride, void *stream) {
-    using crag::filter_fail;
     // every check comes before the first HIP call: on error nothing is enqueued
-    if (nq < 1 || nq > CRAG_FILTER_MAX_QUERIES) return filter_fail("filter_masks_host: need 1 <= nq <= 64");
-    if (n_rows < 0 || n_rows > INT32_MAX) return filter_fail("filter_masks_host: n_rows must be in [0, 2^31)");
-    if (n_calls < 0) return filter_fail("filter_masks_host: n_calls must not be negative");
+    if (nq < 1 || nq > CRAG_FILTER_MAX_QUERIES) return fail(CRAG_EINVAL, "filter_masks_host: need 1 <= nq <= 64");
+    if (n_rows < 0 || n_rows > INT32_MAX) return fail(CRAG_EINVAL, "filter_masks_host: n_rows must be in [0, 2^31)");
+    if (n_calls < 0) return fail(CRAG_EINVAL, "filter_masks_host: n_calls must not be negative");
     if (mask_stride < 0 || mask_stride % 4 != 0 || mask_stride < (n_rows + 31) / 32 * 4 || mask_stride > ((int64_t)1 << 32))
-        return filter_fail("filter_masks_host: mask_stride must be a multiple of 4 in [ceil(n_rows/32)*4, 2^32]");
-    if (!h_date_from || !h_date_to || !slot) return filter_fail("filter_masks_host: NULL pointer argument");
-    if (n_rows > 0 && (!d_started_us || !d_call_slot)) return filter_fail("filter_masks_host: NULL column pointer");
-    if (mask_stride > 0 && !d_out_mask) return filter_fail("filter_masks_host: NULL output pointer");
-    if (((uintptr_t)d_out_mask & 3) != 0) return filter_fail("filter_masks_host: the output must be 4-byte aligned");
+        return fail(CRAG_EINVAL, "filter_masks_host: mask_stride must be a multiple of 4 in [ceil(n_rows/32)*4, 2^32]");
+    if (!h_date_from || !h_date_to || !slot) return fail(CRAG_EINVAL, "filter_masks_host: NULL pointer argument");
+    if (n_rows > 0 && (!d_started_us || !d_call_slot)) return fail(CRAG_EINVAL, "filter_masks_host: NULL column pointer");
+    if (mask_stride > 0 && !d_out_mask) return fail(CRAG_EINVAL, "filter_masks_host: NULL output pointer");
+    if (((uintptr_t)d_out_mask & 3) != 0) return fail(CRAG_EINVAL, "filter_masks_host: the output must be 4-byte aligned");
     if (mask_stride == 0) return CRAG_OK;   // (n_rows is 0: the runs are empty)
 
     // slot layout: from [64] int64 | to [64] int64 | qset [n_calls] uint64
@@ -159,12 +148,5 @@ extern "C" int crag_filter_masks_host(const int64_t *d_started_us, const int32_t
     p.out = (uint32_t *)d_out_mask;
     const int64_t blocks = (p.stride_w + crag::FILTER_SPAN_WORDS - 1) / crag::FILTER_SPAN_WORDS;
     hipLaunchKernelGGL(crag::filter_masks_kernel, dim3((unsigned)blocks), dim3(crag::FILTER_THREADS), 0, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[200];
-        snprintf(buf, sizeof(buf), "filter_masks launch failed: %s", hipGetErrorString(e));
-        crag_set_error_(buf);
-        return CRAG_EHIP;
-    }
-    return CRAG_OK;
+    return launch_ok("filter_masks");
 }

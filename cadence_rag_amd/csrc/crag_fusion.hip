@@ -7,13 +7,10 @@
 #include "crag_arch.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <string.h>
 #include <new>
 
 #include "../../include/crag_dense.h"
-
-extern "C" void crag_set_error_(const char *msg);
+#include "crag_host.h"
 
 namespace {
 
@@ -209,11 +206,6 @@ __global__ __launch_bounds__(FUSE_THREADS) void rrf_fuse_kernel(FuseParams p) {
     FUSE_T(5);
 }
 
-int ffail(const char *msg) {
-    crag_set_error_(msg);
-    return CRAG_EINVAL;
-}
-
 }  // namespace
 
 #ifdef CRAG_FUSE_TRACE
@@ -225,22 +217,22 @@ extern "C" int crag_fuse_trace_read(unsigned long long *host16) {
 extern "C" int crag_rrf_fuse(int n_lanes, const int64_t *const *d_lane_ids, const int32_t *const *d_lane_counts,
                              const int *lane_width, int nq, int rrf_k, int out_k, int64_t *d_out_ids,
                              double *d_out_scores, uint32_t *d_out_lanes, int32_t *d_out_counts, void *stream) {
-    if (n_lanes <= 0 || n_lanes > FUSE_MAX_LANES) return ffail("rrf_fuse: n_lanes must be in [1, 8]");
+    if (n_lanes <= 0 || n_lanes > FUSE_MAX_LANES) return fail(CRAG_EINVAL, "rrf_fuse: n_lanes must be in [1, 8]");
     if (!d_lane_ids || !d_lane_counts || !lane_width || !d_out_ids || !d_out_scores || !d_out_lanes || !d_out_counts)
-        return ffail("rrf_fuse: NULL pointer");
-    if (nq < 0 || out_k <= 0 || rrf_k < 0) return ffail("rrf_fuse: bad sizes");
+        return fail(CRAG_EINVAL, "rrf_fuse: NULL pointer");
+    if (nq < 0 || out_k <= 0 || rrf_k < 0) return fail(CRAG_EINVAL, "rrf_fuse: bad sizes");
     if (nq == 0) return CRAG_OK;
     FuseParams p;
     int total = 0;
     for (int l = 0; l < n_lanes; ++l) {
         // (a lane of width 0 has no keys to point to -- an empty tensor's address is NULL -- and the kernel reads none)
-        if ((!d_lane_ids[l] && lane_width[l] != 0) || !d_lane_counts[l] || lane_width[l] < 0) return ffail("rrf_fuse: bad lane");
+        if ((!d_lane_ids[l] && lane_width[l] != 0) || !d_lane_counts[l] || lane_width[l] < 0) return fail(CRAG_EINVAL, "rrf_fuse: bad lane");
         p.lane_ids[l] = d_lane_ids[l];
         p.lane_counts[l] = d_lane_counts[l];
         p.width[l] = lane_width[l];
         total += lane_width[l];
     }
-    if (total > FUSE_MAX_ITEMS) return ffail("rrf_fuse: more than 1024 items per query");
+    if (total > FUSE_MAX_ITEMS) return fail(CRAG_EINVAL, "rrf_fuse: more than 1024 items per query");
     p.n_lanes = n_lanes;
     p.nq = nq;
     p.rrf_k = rrf_k;
@@ -250,14 +242,7 @@ extern "C" int crag_rrf_fuse(int n_lanes, const int64_t *const *d_lane_ids, cons
     p.out_lanes = d_out_lanes;
     p.out_counts = d_out_counts;
     hipLaunchKernelGGL(rrf_fuse_kernel, dim3((unsigned)nq), dim3(FUSE_THREADS), 0, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[200];
-        snprintf(buf, sizeof(buf), "rrf_fuse launch failed: %s", hipGetErrorString(e));
-        crag_set_error_(buf);
-        return CRAG_EHIP;
-    }
-    return CRAG_OK;
+    return launch_ok("rrf_fuse");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -428,10 +413,10 @@ extern "C" int crag_tech_lane(const int32_t *d_order, const int64_t *d_row_ptr, 
                               int32_t *d_out_counts, void *stream) {
     if (!d_order || !d_row_ptr || !d_tokens || !d_query_tokens || !d_query_token_counts || !d_bitmap_scratch ||
         !d_out_ids || !d_out_counts)
-        return ffail("tech_lane: NULL pointer");
-    if (nq < 0 || nq > TECH_MAX_Q || k <= 0 || n_rows < 0) return ffail("tech_lane: need 0 <= nq <= 64, k > 0");
+        return fail(CRAG_EINVAL, "tech_lane: NULL pointer");
+    if (nq < 0 || nq > TECH_MAX_Q || k <= 0 || n_rows < 0) return fail(CRAG_EINVAL, "tech_lane: need 0 <= nq <= 64, k > 0");
     if (!tech_mask_stride_ok(d_row_mask, mask_stride, n_rows))
-        return ffail("tech_lane: mask_stride must be 0 or a multiple of 4 >= ceil(n_rows/32)*4");
+        return fail(CRAG_EINVAL, "tech_lane: mask_stride must be 0 or a multiple of 4 >= ceil(n_rows/32)*4");
     if (nq == 0) return CRAG_OK;
     TechParams p;
     p.order = d_order;
@@ -454,14 +439,7 @@ extern "C" int crag_tech_lane(const int32_t *d_order, const int64_t *d_row_ptr, 
     if (blocks > 512) blocks = 512;  // persistent blocks (two per CU): the LDS token table is built once per block
     hipLaunchKernelGGL(tech_match_kernel, dim3((unsigned)blocks), dim3(TECH_MATCH_THREADS), 0, (hipStream_t)stream, p);
     hipLaunchKernelGGL(tech_select_kernel, dim3((unsigned)nq), dim3(256), 0, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[200];
-        snprintf(buf, sizeof(buf), "tech_lane launch failed: %s", hipGetErrorString(e));
-        crag_set_error_(buf);
-        return CRAG_EHIP;
-    }
-    return CRAG_OK;
+    return launch_ok("tech_lane");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -506,9 +484,9 @@ extern "C" crag_upload_slot *crag_upload_slot_create(void) {
 // copy has left the pinned buffer, make both buffers at least `bytes` large (a reallocation only when a call needs more
 // than any call before it; hipFree waits for the kernels that may still read the old device twin) and hand them out.
 extern "C" int crag_upload_slot_begin_(crag_upload_slot *s, size_t bytes, void **host, void **dev) {
-    if (!s) return ffail("upload_slot: NULL slot");
+    if (!s) return fail(CRAG_EINVAL, "upload_slot: NULL slot");
     if (s->pending) {
-        if (hipEventSynchronize(s->copied) != hipSuccess) return ffail("upload_slot: waiting for the previous copy failed");
+        if (hipEventSynchronize(s->copied) != hipSuccess) return fail(CRAG_EINVAL, "upload_slot: waiting for the previous copy failed");
         s->pending = false;
     }
     if (bytes > s->bytes) {
@@ -528,10 +506,7 @@ extern "C" int crag_upload_slot_begin_(crag_upload_slot *s, size_t bytes, void *
             if (h) (void)hipHostFree(h);
         }
         (void)hipSetDevice(cur);
-        if (!ok) {
-            crag_set_error_("upload_slot: growing the slot failed");
-            return CRAG_ENOMEM;
-        }
+        if (!ok) return fail(CRAG_ENOMEM, "upload_slot: growing the slot failed");
     }
     *host = s->host;
     *dev = s->dev;
@@ -541,10 +516,8 @@ extern "C" int crag_upload_slot_begin_(crag_upload_slot *s, size_t bytes, void *
 // ONE host-to-device copy of the first `bytes` of the slot on `stream`, and the event that frees the pinned buffer.
 extern "C" int crag_upload_slot_commit_(crag_upload_slot *s, size_t bytes, void *stream) {
     if (hipMemcpyAsync(s->dev, s->host, bytes, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess ||
-        hipEventRecord(s->copied, (hipStream_t)stream) != hipSuccess) {
-        crag_set_error_("upload_slot: upload failed");
-        return CRAG_EHIP;
-    }
+        hipEventRecord(s->copied, (hipStream_t)stream) != hipSuccess)
+        return fail(CRAG_EHIP, "upload_slot: upload failed");
     s->pending = true;
     return CRAG_OK;
 }
@@ -563,13 +536,13 @@ extern "C" int crag_tech_lane_host(const int32_t *d_order, const int64_t *d_row_
                                    const int32_t *h_token_counts, int nq, int k, const uint8_t *d_row_mask,
                                    int64_t mask_stride, crag_upload_slot *slot, uint64_t *d_bitmap_scratch,
                                    int64_t *d_out_ids, int32_t *d_out_counts, void *stream) {
-    if (!slot || !h_token_counts || (!h_token_hashes && nq > 0)) return ffail("tech_lane_host: NULL pointer");
-    if (nq < 0 || nq > TECH_MAX_Q) return ffail("tech_lane_host: need 0 <= nq <= 64");
+    if (!slot || !h_token_counts || (!h_token_hashes && nq > 0)) return fail(CRAG_EINVAL, "tech_lane_host: NULL pointer");
+    if (nq < 0 || nq > TECH_MAX_Q) return fail(CRAG_EINVAL, "tech_lane_host: need 0 <= nq <= 64");
     if (n_rows >= 0 && !tech_mask_stride_ok(d_row_mask, mask_stride, n_rows))   // (before the upload: nothing is enqueued)
-        return ffail("tech_lane_host: mask_stride must be 0 or a multiple of 4 >= ceil(n_rows/32)*4");
+        return fail(CRAG_EINVAL, "tech_lane_host: mask_stride must be 0 or a multiple of 4 >= ceil(n_rows/32)*4");
     if (nq == 0) return CRAG_OK;
     if (slot->pending) {   // the copy that last read the pinned buffer has left it
-        if (hipEventSynchronize(slot->copied) != hipSuccess) return ffail("tech_lane_host: waiting for the upload slot failed");
+        if (hipEventSynchronize(slot->copied) != hipSuccess) return fail(CRAG_EINVAL, "tech_lane_host: waiting for the upload slot failed");
         slot->pending = false;
     }
     uint64_t *qt = (uint64_t *)slot->host;
@@ -577,7 +550,7 @@ extern "C" int crag_tech_lane_host(const int32_t *d_order, const int64_t *d_row_
     const uint64_t *src = h_token_hashes;
     for (int q = 0; q < nq; ++q) {   // distinct hashes, first occurrence kept (the SQL `&&` is a set overlap)
         const int n = h_token_counts[q];
-        if (n < 0) return ffail("tech_lane_host: negative token count");
+        if (n < 0) return fail(CRAG_EINVAL, "tech_lane_host: negative token count");
         uint64_t *row = qt + (size_t)q * 32;
         int m = 0;
         for (int i = 0; i < n; ++i) {
@@ -585,10 +558,8 @@ extern "C" int crag_tech_lane_host(const int32_t *d_order, const int64_t *d_row_
             bool seen = false;
             for (int j = 0; j < m; ++j) seen = seen || row[j] == h;
             if (seen) continue;
-            if (m == 32) {
-                crag_set_error_("tech_lane_host: more than 32 distinct tokens in a query (the caller splits it into passes)");
-                return CRAG_E2BIG;
-            }
+            if (m == 32)
+                return fail(CRAG_E2BIG, "tech_lane_host: more than 32 distinct tokens in a query (the caller splits it into passes)");
             row[m++] = h;
         }
         qn[q] = m;
@@ -596,10 +567,8 @@ extern "C" int crag_tech_lane_host(const int32_t *d_order, const int64_t *d_row_
     }
     if (hipMemcpyAsync(slot->dev, slot->host, SLOT_QT_BYTES + (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice,
                        (hipStream_t)stream) != hipSuccess ||
-        hipEventRecord(slot->copied, (hipStream_t)stream) != hipSuccess) {
-        crag_set_error_("tech_lane_host: upload failed");
-        return CRAG_EHIP;
-    }
+        hipEventRecord(slot->copied, (hipStream_t)stream) != hipSuccess)
+        return fail(CRAG_EHIP, "tech_lane_host: upload failed");
     slot->pending = true;
     return crag_tech_lane(d_order, d_row_ptr, d_tokens, d_ids, n_rows, (const uint64_t *)slot->dev,
                           (const int32_t *)((const char *)slot->dev + SLOT_QT_BYTES), nq, k, d_row_mask, mask_stride,

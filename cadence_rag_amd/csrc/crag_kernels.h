@@ -1,4 +1,5 @@
-// crag_kernels.h — parameter blocks and launchers shared by crag_search.hip and crag_api.hip.
+// crag_kernels.h — parameter blocks and launchers shared by the kernel units (crag_search.hip, crag_edit.hip, ...) and
+// the host units of the C ABI (crag_api.hip, crag_api_search.hip, crag_api_store.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -56,7 +57,7 @@ struct MergeParams {
 // per-query bound record: 128 class maxima (4 sets x 32 row classes), padded to five 128-byte lines so that the
 // records of two queries never share a line
 constexpr int PF_BOUND_CELLS = 160;
-constexpr int PF_STAT_WS = 8;                 // search workspaces per index (crag_api.hip MAX_WS): a block of records each
+constexpr int PF_STAT_WS = 8;                 // search workspaces per index (crag_index.h MAX_WS): a block of records each
 constexpr int PF_STAT_SLOTS = 2048;           // per-query statistics records (summed on the host when read)
 constexpr int PF_MIN_ROWS_PER_GROUP = 128;    // below this many rows per workgroup the plain fp32 scan is used
 

@@ -1,5 +1,5 @@
 """Developer probe: top-50 / top-100 searches, 64 queries over 100 000 and 1M rows: step, scan kernel and the rest
-(prep + selection launch).  [Used to compare 2 / 4 / 8 selection blocks per query (crag_api.hip: fin.rsplit) and the
+(prep + selection launch).  [Used to compare 2 / 4 / 8 selection blocks per query (crag_search_plan.h: rsplit) and the
 selection's k-th search variants.]"""
 import os, sys, time, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
