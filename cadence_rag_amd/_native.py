@@ -19,6 +19,7 @@ CRAG_MAX_K = 128
 CRAG_DIM = 1024
 CRAG_DEDUPE_MAX_WIDTH = 256
 CRAG_SUBSET_MAX_WIDTH = 4096
+CRAG_GROUP_MAX_PER = 8
 CRAG_FILTER_MAX_QUERIES = 64
 
 # every symbol include/crag_dense.h declares: name -> (restype, argtypes)
@@ -68,6 +69,9 @@ SIGNATURES = {
     "crag_index_search_ids_scratch_bytes": (_c.c_int64, [_c.c_int, _c.c_int]),
     "crag_index_search_ids_async": (_c.c_int, [_P, _P, _c.c_int, _P, _P, _c.c_int, _c.c_int64, _c.c_int, _P, _P, _P, _P, _P,
                                                _c.c_int64, _P]),
+    "crag_index_search_grouped_scratch_bytes": (_c.c_int64, [_c.c_int, _c.c_int64, _c.c_int]),
+    "crag_index_search_grouped_async": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _P, _c.c_int64, _c.c_int, _P, _c.c_int64,
+                                                   _P, _P, _P, _P, _P, _c.c_int64, _P]),
     "crag_index_phase_trace": (_c.c_int, [_P, _c.POINTER(_c.c_uint64)]),
     "crag_index_prefilter_stats": (_c.c_int, [_P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64),
                                               _c.POINTER(_c.c_int64)]),

@@ -50,6 +50,10 @@ class Settings:
     # rules", PHASED_PLAN.md:299-303): a fused row is dropped when a kept, higher-ranked row of its side has at least
     # this cosine with it.  0.0 = off
     evidence_dedupe_cosine: float = 0.0
+    # per-call cap of the chunk dense lane (the reference's planned "per-call diversity caps", PHASED_PLAN.md:299-303):
+    # at most this many chunks of one call among the lane's rows, applied over the whole table (the grouped search), so
+    # that one long call cannot fill the lane while _pack keeps DEFAULT_MAX_QUOTES_PER_CALL of it.  0 = off
+    dense_per_call_cap: int = 0
 
     def __post_init__(self) -> None:
         if self.rerank_device < 0:

@@ -1,6 +1,7 @@
 // crag_api_search.hip — the search calls of the C ABI: the launch sequence prep_queries -> scan -> selection on a
 // per-stream workspace (what each search takes is decided in crag_search_plan.h), the pipelined form and its join, and
-// the calls that work on ranked lists (dedupe, listed rows).  No exceptions cross the ABI.
+// the calls that work on ranked lists (dedupe, listed rows) and the search with a cap per group.  No exceptions cross
+// the ABI.
 
 #include "crag_index.h"
 
@@ -460,6 +461,61 @@ int crag_index_search_ids_async(crag_index *ix, const float *d_queries, int nq, 
     p.out_counts = d_out_counts;
     p.out_slot_scores = d_out_slot_scores;
     HIP_TRY(crag::launch_subset(p, (hipStream_t)stream));
+    return CRAG_OK;
+}
+
+int64_t crag_index_search_grouped_scratch_bytes(int nq, int64_t n_groups, int per_group) {
+    return crag::group_scratch_bytes(nq, n_groups, per_group);
+}
+
+int crag_index_search_grouped_async(crag_index *ix, const float *d_queries, int nq, int k, const int32_t *d_row_group,
+                                    int64_t n_groups, int per_group, const uint8_t *d_row_mask, int64_t mask_stride,
+                                    int64_t *d_out_ids, float *d_out_scores, int32_t *d_out_groups, int32_t *d_out_counts,
+                                    void *d_scratch, int64_t scratch_bytes, void *stream) {
+    if (!ix) return fail(CRAG_EINVAL, "search_grouped: index is NULL");
+    if (nq < 0 || nq > 65535) return fail(CRAG_EINVAL, "search_grouped: nq must be in [0, 65535] (got %d)", nq);
+    if (k < 1 || k > CRAG_MAX_K) return fail(CRAG_EINVAL, "search_grouped: k must be in [1, %d] (got %d)", CRAG_MAX_K, k);
+    if (per_group < 1 || per_group > CRAG_GROUP_MAX_PER)
+        return fail(CRAG_EINVAL, "search_grouped: per_group must be in [1, %d] (got %d)", CRAG_GROUP_MAX_PER, per_group);
+    if (n_groups < 1 || n_groups >= ((int64_t)1 << 31))
+        return fail(CRAG_EINVAL, "search_grouped: n_groups must be in [1, 2^31) (got %lld)", (long long)n_groups);
+    if (!d_queries || !d_row_group || !d_out_ids || !d_out_scores || !d_out_counts || !d_scratch)
+        return fail(CRAG_EINVAL, "search_grouped: queries / row_group / out_ids / out_scores / out_counts / scratch must not be NULL");
+    if (d_row_mask) {   // what check_search_args refuses
+        const int64_t need = ((ix->size + 31) / 32) * 4;
+        if (mask_stride != 0 && (mask_stride % 4 != 0 || mask_stride < need))
+            return fail(CRAG_EINVAL, "search_grouped: mask_stride must be 0 or a multiple of 4 >= %lld (got %lld)",
+                        (long long)need, (long long)mask_stride);
+        if (((uintptr_t)d_row_mask) & 3) return fail(CRAG_EINVAL, "search_grouped: row_mask must be 4-byte aligned");
+    }
+    if (scratch_bytes < crag::group_scratch_bytes(nq, n_groups, per_group) || ((uintptr_t)d_scratch & 7))
+        return fail(CRAG_EINVAL,
+                    "search_grouped: scratch too small or not 8-byte aligned (crag_index_search_grouped_scratch_bytes)");
+    if (nq == 0) return CRAG_OK;
+    std::lock_guard<std::mutex> lk(ix->mu);
+    DeviceGuard guard(ix->device);
+    crag::GroupParams p;
+    p.corpus = ix->corpus;
+    p.inv_norm = ix->inv_norm;
+    p.stored = ix->ids;
+    p.size = ix->size;
+    p.piece_shift = crag::crag_piece_shift(ix->corpus16 != nullptr);
+    p.queries = d_queries;
+    p.nq = nq;
+    p.dim = ix->dim;
+    p.k = k;
+    p.row_group = d_row_group;
+    p.n_groups = n_groups;
+    p.per_group = per_group;
+    p.mask = (const uint32_t *)d_row_mask;
+    p.mask_stride_w = mask_stride / 4;
+    p.table = (uint64_t *)d_scratch;
+    p.qinv = (float *)(p.table + (size_t)nq * (size_t)n_groups * (size_t)per_group);
+    p.out_ids = d_out_ids;
+    p.out_scores = d_out_scores;
+    p.out_groups = d_out_groups;
+    p.out_counts = d_out_counts;
+    HIP_TRY(crag::launch_grouped(p, (hipStream_t)stream));
     return CRAG_OK;
 }
 

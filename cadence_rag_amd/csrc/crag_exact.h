@@ -1,7 +1,7 @@
 // crag_exact.h -- the exact-score arithmetic of the dense lane, in one place: the 64-bit candidate key, the canonical
 // 1/||q||, one 128-dim slice of the exact fp32 dot product and the score -> key expression.  crag_search.hip (the scans
-// and the selection kernel) and crag_subset.hip (the search over id lists) include it, so a (query, row) pair has the same
-// score bits on every path.  Device code only.
+// and the selection kernel), crag_subset.hip (the search over id lists) and crag_group.hip (the search with a cap per
+// group) include it, so a (query, row) pair has the same score bits on every path.  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,6 +25,25 @@ __device__ __forceinline__ float ord2f(uint32_t u) {
 }
 __device__ __forceinline__ uint64_t mk64(uint32_t hi, uint32_t lo) {
     return ((uint64_t)hi << 32) | lo;
+}
+
+// Bitonic sort of P keys in LDS (P a power of two), descending, by the SCAN_THREADS threads of a workgroup; the keys are
+// in order behind the barrier the last pass ends with.  (subset_select_kernel, group_select_kernel)
+__device__ __forceinline__ void sort_keys_desc(uint64_t *keys, int P) {
+    const int tid = threadIdx.x;
+    for (int k2 = 2; k2 <= P; k2 <<= 1)
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (P >> 1); t += SCAN_THREADS) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+                const uint64_t a = keys[i], b = keys[l];
+                const bool desc = (i & k2) == 0;
+                if (desc ? a < b : a > b) {
+                    keys[i] = b;
+                    keys[l] = a;
+                }
+            }
+            __syncthreads();
+        }
 }
 
 // ---- the canonical 1/||q||: ONE piece of arithmetic for every kernel that needs a query's norm -------------------
@@ -96,6 +115,59 @@ __device__ __forceinline__ float exact_slice_dot(const f32x4 *qslice /* [16][2] 
             acc = __builtin_fmaf(q1[cc], c1[s][cc], acc);
         }
     }
+    return acc;
+}
+
+// exact_slice_dot in two halves, for a kernel that scores one row against many queries (crag_group.hip): the fetch of
+// the row's 32 float4 -- the same addresses, c0[s] / c1[s] = float4 2s / 2s + 1 of the slice -- and the fmaf chain in
+// the same order over a slice that is already in registers.  exact_slice_fma(q, fetched row) is exact_slice_dot(q, row)
+// bit for bit.
+template <int PS>
+__device__ __forceinline__ void exact_slice_fetch(const f32x4 *ctile /* tile base + slice */, int jrow, f32x4 (&c0)[16],
+                                                  f32x4 (&c1)[16]) {
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        c0[s] = ctile[(((2 * s) >> PS) * 32 + jrow) * (1 << PS) + ((2 * s) & ((1 << PS) - 1))];
+        c1[s] = ctile[(((2 * s) >> PS) * 32 + jrow) * (1 << PS) + ((2 * s) & ((1 << PS) - 1)) + 1];
+    }
+}
+
+// (the query slice is read from LDS eight float4 -- four steps s -- ahead of the chain that uses them, in two register
+// sets used in turn: a kernel that keeps a whole row slice in registers runs at two waves per SIMD, where a read that the
+// chain waits for costs its whole latency; the scheduling fences keep the compiler from sinking the reads to their uses)
+__device__ __forceinline__ void slice_query_read(const f32x4 *qslice, int h, f32x4 (&q)[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) q[i] = qslice[8 * h + i];
+}
+__device__ __forceinline__ float slice_query_fma(float acc, int h, const f32x4 (&q)[8], const f32x4 (&c0)[16],
+                                                 const f32x4 (&c1)[16]) {
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) {
+        const f32x4 q0 = q[2 * s4], q1 = q[2 * s4 + 1];
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) {
+            acc = __builtin_fmaf(q0[cc], c0[4 * h + s4][cc], acc);
+            acc = __builtin_fmaf(q1[cc], c1[4 * h + s4][cc], acc);
+        }
+    }
+    return acc;
+}
+__device__ __forceinline__ float exact_slice_fma(const f32x4 *qslice /* [16][2] float4 in LDS */, const f32x4 (&c0)[16],
+                                                 const f32x4 (&c1)[16]) {
+    f32x4 qa[8], qb[8];
+    slice_query_read(qslice, 0, qa);
+    slice_query_read(qslice, 1, qb);
+    __builtin_amdgcn_sched_barrier(0);
+    float acc = slice_query_fma(0.f, 0, qa, c0, c1);   // s = 0..3
+    __builtin_amdgcn_sched_barrier(0);
+    slice_query_read(qslice, 2, qa);
+    __builtin_amdgcn_sched_barrier(0);
+    acc = slice_query_fma(acc, 1, qb, c0, c1);         // s = 4..7
+    __builtin_amdgcn_sched_barrier(0);
+    slice_query_read(qslice, 3, qb);
+    __builtin_amdgcn_sched_barrier(0);
+    acc = slice_query_fma(acc, 2, qa, c0, c1);         // s = 8..11
+    acc = slice_query_fma(acc, 3, qb, c0, c1);         // s = 12..15
     return acc;
 }
 

@@ -254,4 +254,29 @@ struct SubsetParams {
 int64_t subset_scratch_bytes(int nq, int width);
 hipError_t launch_subset(const SubsetParams &p, hipStream_t st);
 
+// ---- exact top-k under "at most per_group rows per group" (crag_group.hip) ----
+struct GroupParams {
+    const float *corpus;        // tile32 layout
+    const float *inv_norm;
+    const int64_t *stored;      // [size] ids, ascending with the position
+    int64_t size;
+    int piece_shift;
+    const float *queries;       // [nq, dim] row-major fp32, raw
+    int nq, dim, k;
+    const int32_t *row_group;   // [size] group number by row position; outside [0, n_groups): the row is ignored
+    int64_t n_groups;
+    int per_group;              // <= CRAG_GROUP_MAX_PER
+    const uint32_t *mask;       // nullable; 32 rows per word
+    int64_t mask_stride_w;      // words between consecutive queries' masks (0 = shared)
+    uint64_t *table;            // scratch [nq][n_groups][per_group] keys, best first, 0 = empty
+    float *qinv;                // scratch [nq] the canonical 1/||q|| (0: zero / non-finite query)
+    int64_t *out_ids;           // [nq, k], -1 padded
+    float *out_scores;          // [nq, k], NaN padded
+    int32_t *out_groups;        // nullable [nq, k], -1 padded
+    int32_t *out_counts;        // [nq]
+};
+// the table, then the 1/||q|| (padded to 8 bytes)
+int64_t group_scratch_bytes(int nq, int64_t n_groups, int per_group);
+hipError_t launch_grouped(const GroupParams &p, hipStream_t st);
+
 }  // namespace crag

@@ -110,20 +110,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void subset_select_kernel(SubsetParam
     const uint64_t *mine = p.keys + (size_t)q * p.width;
     for (int i = tid; i < P; i += SCAN_THREADS) keys[i] = i < count ? mine[i] : 0ull;
     __syncthreads();
-    // bitonic sort, descending
-    for (int k2 = 2; k2 <= P; k2 <<= 1)
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (P >> 1); t += SCAN_THREADS) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-                const uint64_t a = keys[i], b = keys[l];
-                const bool desc = (i & k2) == 0;
-                if (desc ? a < b : a > b) {
-                    keys[i] = b;
-                    keys[l] = a;
-                }
-            }
-            __syncthreads();
-        }
+    sort_keys_desc(keys, P);   // bitonic, descending
     // the distinct non-zero keys, in order: thread t owns the contiguous run [t * per, t * per + per)
     const int per = (P + SCAN_THREADS - 1) / SCAN_THREADS, i0 = tid * per;
     int n_mine = 0;

@@ -367,6 +367,93 @@ class DenseIndex:
         res = (out_ids.cpu().numpy(), out_sc.cpu().numpy(), out_ct.cpu().numpy())
         return res + (slot.cpu().numpy(),) if slot_scores else res
 
+    # -- exact top-k under a cap per group (crag_index_search_grouped_async) ------------------------
+    GROUPED_SCRATCH_LIMIT = 256 << 20   # search_grouped splits its queries so that the scratch stays at or below this
+
+    @staticmethod
+    def search_grouped_scratch_bytes(nq: int, n_groups: int, per_group: int) -> int:
+        return int(_native.load().crag_index_search_grouped_scratch_bytes(int(nq), int(n_groups), int(per_group)))
+
+    def search_grouped_async(self, d_queries, k: int, d_row_group, n_groups: int, per_group: int, d_out_ids,
+                             d_out_scores, d_out_counts, d_out_groups=None, d_row_mask=None, mask_stride: int = 0,
+                             scratch=None, stream: int = 0) -> None:
+        """The search of `search_async` with at most `per_group` rows per group, enqueued on `stream`: d_row_group int32
+        [size] by row position (a number outside [0, n_groups): the row is ignored).  Per query the eligible rows are
+        walked best first and a row is kept iff its group holds fewer than per_group kept rows, up to k; scores are the
+        bits search_async returns.  d_out_groups int32 [nq, k] (optional, -1 pad).  scratch: a uint8 CUDA tensor of
+        search_grouped_scratch_bytes(nq, n_groups, per_group) bytes, one per stream in use, contents arbitrary
+        (default: allocated here).  Arguments are torch CUDA tensors."""
+        nq = int(d_queries.shape[0])
+        if scratch is None:
+            scratch = torch.empty(self.search_grouped_scratch_bytes(nq, n_groups, per_group), dtype=torch.uint8,
+                                  device=d_queries.device)
+        _native.check(self._lib.crag_index_search_grouped_async(
+            self._h, d_queries.data_ptr(), nq, int(k), d_row_group.data_ptr(), int(n_groups), int(per_group),
+            None if d_row_mask is None else d_row_mask.data_ptr(), int(mask_stride), d_out_ids.data_ptr(),
+            d_out_scores.data_ptr(), None if d_out_groups is None else d_out_groups.data_ptr(), d_out_counts.data_ptr(),
+            scratch.data_ptr(), int(scratch.numel()) * scratch.element_size(), ctypes.c_void_p(stream)),
+            "crag_index_search_grouped_async")
+
+    def search_grouped(self, queries, k: int, row_group, n_groups: int, per_group: int, row_mask=None):
+        """Host convenience over search_grouped_async.  queries / row_group ([size] int32) / row_mask (packed bits from
+        pack_mask(), [bytes] shared or [nq, bytes] per query) may be numpy arrays or CUDA tensors.  Returns numpy
+        (ids [nq, k], scores [nq, k], groups [nq, k], counts [nq]); the queries are split so that the scratch of one
+        call stays at or below GROUPED_SCRATCH_LIMIT (a single query may exceed it).  Synchronises."""
+        if torch is None:  # pragma: no cover
+            raise _native.NativeLibraryError("DenseIndex.search_grouped stages its buffers with torch")
+        _, nq, keep = _as_f32_2d(queries, self.dim, "queries")
+        k, n_groups, per_group = int(k), int(n_groups), int(per_group)
+        if not 1 <= k <= _native.CRAG_MAX_K:
+            raise ValueError(f"k must be in [1, {_native.CRAG_MAX_K}] (got {k})")
+        if not 1 <= per_group <= _native.CRAG_GROUP_MAX_PER:
+            raise ValueError(f"per_group must be in [1, {_native.CRAG_GROUP_MAX_PER}] (got {per_group})")
+        if not 1 <= n_groups < 1 << 31:
+            raise ValueError(f"n_groups must be in [1, 2^31) (got {n_groups})")
+        if nq == 0 or len(self) == 0:   # nothing to rank: the pads of the C ABI
+            return (np.full((nq, k), -1, dtype=np.int64), np.full((nq, k), np.nan, dtype=np.float32),
+                    np.full((nq, k), -1, dtype=np.int32), np.zeros((nq,), dtype=np.int32))
+        dev = torch.device("cuda", self.device)
+
+        def on_device(x, dtype):
+            t = x if _is_torch(x) else torch.from_numpy(np.ascontiguousarray(x))
+            return t.to(device=dev, dtype=dtype).contiguous()
+
+        d_q = on_device(keep, torch.float32)
+        d_grp = on_device(row_group, torch.int32).reshape(-1)
+        if int(d_grp.numel()) != len(self):
+            raise ValueError(f"row_group needs one entry per stored row ({len(self)}, got {int(d_grp.numel())})")
+        d_mask, stride = None, 0
+        if row_mask is not None:
+            d_mask = on_device(row_mask, torch.uint8)
+            need = ((len(self) + 31) // 32) * 4
+            if d_mask.shape[-1] < need:
+                raise ValueError(f"row_mask needs {need} bytes per row (use pack_mask)")
+            if d_mask.dim() == 2:
+                if d_mask.shape[0] != nq:
+                    raise ValueError("per-query row_mask must have one row per query")
+                stride = int(d_mask.shape[1])
+                if stride % 4:
+                    raise ValueError("row_mask row stride must be a multiple of 4 bytes")
+        out_ids = torch.empty(nq, k, dtype=torch.int64, device=dev)
+        out_sc = torch.empty(nq, k, dtype=torch.float32, device=dev)
+        out_grp = torch.empty(nq, k, dtype=torch.int32, device=dev)
+        out_ct = torch.empty(nq, dtype=torch.int32, device=dev)
+        per_query = self.search_grouped_scratch_bytes(2, n_groups, per_group) - \
+            self.search_grouped_scratch_bytes(1, n_groups, per_group)
+        step = max(1, min(65535, self.GROUPED_SCRATCH_LIMIT // max(per_query + 8, 1)))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        scratch = None
+        for q0 in range(0, nq, step):
+            q1 = min(nq, q0 + step)
+            if scratch is None:
+                scratch = torch.empty(self.search_grouped_scratch_bytes(q1 - q0, n_groups, per_group), dtype=torch.uint8,
+                                      device=dev)
+            self.search_grouped_async(d_q[q0:q1], k, d_grp, n_groups, per_group, out_ids[q0:q1], out_sc[q0:q1],
+                                      out_ct[q0:q1], out_grp[q0:q1],
+                                      d_row_mask=None if d_mask is None else (d_mask[q0:q1] if stride else d_mask),
+                                      mask_stride=stride, scratch=scratch, stream=stream)
+        return out_ids.cpu().numpy(), out_sc.cpu().numpy(), out_grp.cpu().numpy(), out_ct.cpu().numpy()
+
     # -- profiling / reporting -------------------------------------------------------------
     def profile_enable(self, every: int = 1) -> None:
         """Record HIP events around the scan/merge kernels of every `every`-th search (0 = off)."""

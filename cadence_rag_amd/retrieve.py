@@ -432,12 +432,18 @@ class DenseTable:
 
     def fetch_dense(self, query_embedding, filters: Optional[RetrieveFilters],
                     call_ids: Optional[Sequence[UUID]], mode: str, limit: int,
-                    select: Sequence[str]) -> List[Dict[str, Any]]:
-        """ORDER BY embedding <=> q LIMIT :limit, rows as mappings with `select` columns + score."""
+                    select: Sequence[str], per_call: Optional[int] = None) -> List[Dict[str, Any]]:
+        """ORDER BY embedding <=> q LIMIT :limit, rows as mappings with `select` columns + score.  per_call: at most
+        that many rows of one call among them -- the best rows under the cap over the WHOLE table (the grouped search,
+        crag_index_search_grouped_async, over the filter columns' call numbers), not a cut of the plain top-`limit`."""
         del mode  # the HBM scan is always exact; `mode` only labels what pgvector would have done
         if len(self) == 0 or limit <= 0:
             return []
         q = _parse_vector(query_embedding)
+        if per_call:
+            # (the listed-rows route below has no cap: every capped request takes the grouped search)
+            ids, scores, _, counts = self._search_per_call(q, filters, call_ids, int(limit), int(per_call))
+            return self._dense_rows(ids, scores, counts, select)
         rows: List[Dict[str, Any]] = []
         # the reference's "exact" dense mode (retrieve.py:277-287): a call-scoped request whose calls hold few rows reads
         # those rows only (crag_index_search_ids_async) -- the same rows and score bits as the masked scan below
@@ -460,6 +466,34 @@ class DenseTable:
             row["score"] = float(sc)
             rows.append(row)
         return rows
+
+    def _search_per_call(self, q: np.ndarray, filters, call_ids, limit: int, per_call: int):
+        """The grouped search of one query under the request's filters: group = the row's call number."""
+        cols = self.filter_columns()
+        return self.index.search_grouped(q[None, :], min(int(limit), _native_max_k()), cols.d_call_slot, cols.n_calls,
+                                         per_call, row_mask=self.filter_mask_device(filters, call_ids))
+
+    def _dense_rows(self, ids, scores, counts, select: Sequence[str]) -> List[Dict[str, Any]]:
+        pos_of = self._positions()
+        rows: List[Dict[str, Any]] = []
+        for rid, sc in zip(ids[0, :counts[0]], scores[0, :counts[0]]):
+            pos = pos_of[int(rid)]
+            row = {name: self.columns[name][pos] for name in select}
+            row["score"] = float(sc)
+            rows.append(row)
+        return rows
+
+    def shortlist_calls(self, query_embedding, filters: Optional[RetrieveFilters],
+                        call_ids: Optional[Sequence[UUID]], n: int) -> List[Tuple[Any, int, float]]:
+        """The call shortlist of the hierarchical strategy (APP_SPEC.md 9.2): the `n` calls whose best row scores
+        highest under the request's filters, as [(call_id, id of that row, its score)], best first -- the grouped search
+        with one row per call and k = n (at most CRAG_MAX_K calls)."""
+        if len(self) == 0 or n <= 0:
+            return []
+        ids, scores, _, counts = self._search_per_call(_parse_vector(query_embedding), filters, call_ids, int(n), 1)
+        pos_of = self._positions()
+        return [(self.call_ids[pos_of[int(rid)]], int(rid), float(sc))
+                for rid, sc in zip(ids[0, :counts[0]], scores[0, :counts[0]])]
 
     @classmethod
     def from_rows(cls, name: str, id_field: str, rows, *, select: Sequence[str], dim: Optional[int] = None,
@@ -586,6 +620,12 @@ def _naive_utc(dt: datetime) -> datetime:
 
 CHUNK_SELECT = ("chunk_id", "call_id", "speaker", "start_ts_ms", "end_ts_ms", "text")
 ARTIFACT_SELECT = ("artifact_chunk_id", "artifact_id", "call_id", "kind", "content")
+
+
+def _dense_per_call_cap() -> int:
+    """Settings.dense_per_call_cap as the grouped search takes it: 0 (off) .. CRAG_GROUP_MAX_PER."""
+    from ._native import CRAG_GROUP_MAX_PER
+    return min(max(int(settings.dense_per_call_cap or 0), 0), CRAG_GROUP_MAX_PER)
 
 
 def _estimate_dense_candidates(table: DenseTable, table_name: str, filters: Optional[RetrieveFilters],
@@ -763,6 +803,10 @@ class GpuRetrieveBackend(RetrieveBackend):
         return _estimate_dense_candidates(self.tables[table_name], table_name, filters, call_ids)
 
     def fetch_chunks_dense(self, query_embedding, filters, call_ids, mode, limit):
+        cap = _dense_per_call_cap()   # (the artifact side has no per-call quota in _pack: it stays uncapped)
+        if cap:
+            return self.tables["chunks"].fetch_dense(query_embedding, filters, call_ids, mode, limit, CHUNK_SELECT,
+                                                     per_call=cap)
         return _fetch_chunks_dense(self.tables["chunks"], query_embedding, filters, call_ids, mode, limit)
 
     def fetch_artifacts_dense(self, query_embedding, filters, call_ids, mode, limit):
@@ -1021,6 +1065,8 @@ def _retrieval_notes(tokens: List[str], dense: _DenseState, rerank: Optional[_Re
     if dedupe is not None and dedupe.on:   # likewise
         notes["dedupe_cosine"] = dedupe.cosine
         notes["dedupe_dropped"] = dict(dedupe.dropped)
+    if _dense_per_call_cap():   # likewise
+        notes["dense_per_call_cap"] = _dense_per_call_cap()
     return notes
 
 

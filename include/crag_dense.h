@@ -237,6 +237,41 @@ int crag_index_search_ids_async(crag_index *ix, const float *d_queries, int nq, 
                                 float *d_out_scores, int32_t *d_out_counts, float *d_out_slot_scores, void *d_scratch,
                                 int64_t scratch_bytes, void *stream);
 
+/* Exact cosine top-k under a cap per group ("grouping search" / collapse with inner hits): per query the eligible rows
+ * are ranked by (score descending, id ascending) -- scores and eligibility of crag_index_search: mask bit set, finite
+ * non-zero row norm, finite non-zero query --, the ranking is walked, a row is kept iff its group holds fewer than
+ * per_group kept rows, and the walk stops at k.  Equivalently: the top-k of the union of every group's own top-per_group.
+ * The cap holds over the whole table, not over a prefix of the ranking.
+ * Stands in for: the per-call quota the reference applies only when it packs evidence -- _pack keeps at most
+ * DEFAULT_MAX_QUOTES_PER_CALL = 2 quotes per call (retrieve.py:829) of whatever `ORDER BY embedding <=> q LIMIT 50`
+ * (retrieve.py:339-353) returned, so one long call can fill the dense lane -- and for what the reference plans but has
+ * no code for: PHASED_PLAN.md:299-303 "enforce per-call diversity caps", IMPLEMENTATION_PLAN.md:150-158, and the
+ * hierarchical strategy of APP_SPEC.md 9.2 / 9.5 (shortlist calls by their best chunk: per_group = 1, group = call).
+ *   d_queries   [nq, dim] fp32, raw
+ *   d_row_group [size] int32 by row POSITION: the row's group number.  A row whose number lies outside [0, n_groups) is
+ *               ignored; its number is never used as an index.  The caller keeps the column in step with edits, as it does
+ *               for masks (cadence_rag_amd.filters.FilterColumns.d_call_slot / n_calls is such a column).
+ *   d_row_mask / mask_stride  exactly as in crag_index_search (nullable; shared or per query)
+ *   d_out_ids [nq, k] (-1 pad), d_out_scores [nq, k] (NaN pad), d_out_groups nullable [nq, k] (-1 pad), d_out_counts [nq]
+ *   d_scratch   crag_index_search_grouped_scratch_bytes(nq, n_groups, per_group) bytes (8 per (query, group, slot) + 4 per
+ *               query), 8-byte aligned, owned by the caller, one per stream in use.  The call clears whatever it reads of
+ *               it: a dirty or reused scratch is fine.
+ * The score of a (query, row) pair is the same bits crag_index_search_async returns for that pair; it depends on the pair
+ * alone: not on k, per_group, nq, the grouping, the mask form, the row's position or the row layout.  The outputs are a
+ * function of the inputs alone, bit for bit, from run to run.
+ * All pointers DEVICE; three launches on `stream`, no host synchronisation, no allocation, no workspace of the index.
+ * Ordering against edits as for crag_index_search_ids_async.  An empty index is valid: every count is 0.
+ * CRAG_EINVAL with a message that contains "search_grouped", checked before any HIP call, nothing enqueued: NULL index
+ * or required pointer, nq < 0 (or > 65535), k outside [1, CRAG_MAX_K], per_group outside [1, CRAG_GROUP_MAX_PER],
+ * n_groups < 1 or >= 2^31, a mask stride crag_index_search refuses, scratch too small or not 8-byte aligned.
+ * nq == 0 is CRAG_OK. */
+#define CRAG_GROUP_MAX_PER 8
+int64_t crag_index_search_grouped_scratch_bytes(int nq, int64_t n_groups, int per_group);
+int crag_index_search_grouped_async(crag_index *ix, const float *d_queries, int nq, int k, const int32_t *d_row_group,
+                                    int64_t n_groups, int per_group, const uint8_t *d_row_mask, int64_t mask_stride,
+                                    int64_t *d_out_ids, float *d_out_scores, int32_t *d_out_groups, int32_t *d_out_counts,
+                                    void *d_scratch, int64_t scratch_bytes, void *stream);
+
 /* Merge per-shard results (the multi-GPU exchange step: each rank's [nq, k] top-k after an
  * RCCL all-gather) into the global top-k.  All pointers DEVICE.
  *   d_ids/d_scores/d_counts  [n_lists, nq, k] / [n_lists, nq, k] / [n_lists, nq]
