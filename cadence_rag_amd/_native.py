@@ -21,6 +21,10 @@ CRAG_DEDUPE_MAX_WIDTH = 256
 CRAG_SUBSET_MAX_WIDTH = 4096
 CRAG_GROUP_MAX_PER = 8
 CRAG_FILTER_MAX_QUERIES = 64
+CRAG_ATTR_MAX_QUERIES = 64
+CRAG_ATTR_MAX_CLAUSES = 8
+CRAG_ATTR_MAX_KEYS = 512
+CRAG_E2BIG = -5
 
 # every symbol include/crag_dense.h declares: name -> (restype, argtypes)
 _c = ctypes
@@ -56,6 +60,8 @@ SIGNATURES = {
     "crag_bm25_lane_host": (_c.c_int, [_P, _P, _P, _P, _P, _c.c_int64, _c.c_int64, _c.c_float, _P, _P, _P, _c.c_int, _c.c_int,
                                        _P, _c.c_int64, _P, _P, _c.c_int64, _P, _P, _P, _P]),
     "crag_filter_masks_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P, _P, _c.c_int, _P, _P, _c.c_int64, _P]),
+    "crag_attr_masks_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int64, _P, _P,
+                                        _c.c_int64, _P]),
     "crag_index_profile_enable": (_c.c_int, [_P, _c.c_int]),
     "crag_index_profile_read": (_c.c_int, [_P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_double),
                                            _c.POINTER(_c.c_double)]),

@@ -5,17 +5,26 @@ The filter columns of a table live in HBM beside its vectors (FilterColumns: cal
 dense number of the row's call, 12 bytes per row); a request's predicates are compiled on the host into two date bounds
 per query and, transposed, one 64-bit query set per CALL (compile_predicates: its cost is in the number of calls and
 listed ids, never in the number of rows); the kernel evaluates them for every row and writes the packed masks the lanes
-take.  DenseTable.filter_mask stays the public host form of the same predicate."""
+take.  DenseTable.filter_mask stays the public host form of the same predicate.
+
+Row-level predicates -- entity, speaker and kind -- go the same way through a second kernel
+(crag_attr_masks_host): a row's attributes are (namespace, value) pairs, namespace one of "speaker", "kind",
+"entity:" + LABEL; a table's AttributeColumns hold them as a CSR of dictionary ids in HBM (8 bytes per row + 4 per
+attribute); compile_attr_predicates turns a request's entity_filters / speakers / kinds into clauses of keys (a cost in
+keys, never in rows), and a row passes iff every clause is hit by one of its attributes.  A namespace a table lacks is
+NULL there and fails every clause over it, so a `speakers` filter returns no artifact rows."""
 from __future__ import annotations
 
 import ctypes
-from typing import Any, Dict, Optional, Sequence, Tuple
+from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _native
 
 MAX_QUERIES = _native.CRAG_FILTER_MAX_QUERIES
+MAX_CLAUSES = _native.CRAG_ATTR_MAX_CLAUSES
+MAX_KEYS = _native.CRAG_ATTR_MAX_KEYS
 NO_LOWER = np.iinfo(np.int64).min   # date_from of a query without a lower bound; also a row's NULL / NaT timestamp
 NO_UPPER = np.iinfo(np.int64).max   # date_to of a query without an upper bound
 
@@ -166,3 +175,192 @@ def compile_predicates(columns: FilterColumns, call_tags: Dict[Any, Sequence[str
 def is_unfiltered(qset: Optional[np.ndarray], date_from: np.ndarray, date_to: np.ndarray) -> bool:
     """No query of the compiled batch restricts anything (for one query: DenseTable.filter_mask returns None)."""
     return qset is None and bool(np.all(date_from == NO_LOWER)) and bool(np.all(date_to == NO_UPPER))
+
+
+# ---- row-level predicates: entity, speaker, kind (crag_attr_masks_host, DESIGN.md 4.13) -----------------------------
+Attr = Tuple[str, str]   # (namespace, normalised value)
+
+
+def normalize_attr(value) -> Optional[str]:
+    """The one normal form of an attribute value, used on the row side and the query side: whitespace runs collapsed
+    to one space, ends stripped, casefolded.  None or an empty value is no attribute: None."""
+    if value is None:
+        return None
+    return " ".join(str(value).split()).casefold() or None
+
+
+def entity_namespace(label) -> str:
+    return "entity:" + str(label if label is not None else "").strip().upper()
+
+
+def _entity_pair(entity) -> Tuple[Any, Any]:
+    if isinstance(entity, dict):
+        return entity.get("label"), entity.get("value")
+    label, value = entity
+    return label, value
+
+
+def row_attributes(n: int, speakers: Optional[Sequence[Any]], kinds: Optional[Sequence[Any]],
+                   entities: Optional[Sequence[Iterable[Any]]]) -> List[List[Attr]]:
+    """The attributes of n rows from their `speaker` entries, `kind` entries and entity lists ((label, value) pairs or
+    {"label", "value"} dicts); an argument that is None is a namespace the table lacks."""
+    rows: List[List[Attr]] = [[] for _ in range(n)]
+    for namespace, column in (("speaker", speakers), ("kind", kinds)):
+        if column is None:
+            continue
+        if len(column) != n:
+            raise ValueError(f"the {namespace} column must have one entry per row")
+        for attrs, raw in zip(rows, column):
+            value = normalize_attr(raw)
+            if value is not None:
+                attrs.append((namespace, value))
+    if entities is not None:
+        if len(entities) != n:
+            raise ValueError("entities must have one entry per row")
+        for attrs, listed in zip(rows, entities):
+            for entity in listed or ():
+                label, raw = _entity_pair(entity)
+                value = normalize_attr(raw)
+                if value is not None:
+                    attrs.append((entity_namespace(label), value))
+    return rows
+
+
+def attr_clauses(filters) -> List[List[Attr]]:
+    """The clauses of one request: each entity_filters entry is a clause of one key, `speakers` is one clause of all its
+    keys, `kinds` likewise; a falsy field is not applied (as call_tags).  A value that normalises to nothing is no key,
+    so its clause may be left without any and then admits nothing.  More than 8 clauses: ValueError."""
+    clauses: List[List[Attr]] = []
+    if not filters:
+        return clauses
+    for entity in getattr(filters, "entity_filters", None) or ():
+        label, raw = _entity_pair(entity)
+        value = normalize_attr(raw)
+        clauses.append([] if value is None else [(entity_namespace(label), value)])
+    for namespace, field in (("speaker", "speakers"), ("kind", "kinds")):
+        listed = getattr(filters, field, None)
+        if listed:
+            values = [normalize_attr(v) for v in listed]
+            clauses.append([(namespace, v) for v in values if v is not None])
+    if len(clauses) > MAX_CLAUSES:
+        raise ValueError(f"a request holds at most {MAX_CLAUSES} attribute clauses (got {len(clauses)})")
+    return clauses
+
+
+class AttributeColumns:
+    """The attribute columns of one DenseTable: a dictionary `id_of` from (namespace, value) to an int32 id, numbered by
+    first appearance (exact strings, no hashing: the BM25 vocabulary's idiom), and the rows' ids as a CSR by row position
+    (`attr_ptr` int64 [n + 1], `attr_ids` int32; duplicates inside a row are kept), built in ONE host pass per table
+    generation.  `row_attrs`: per row an iterable of (namespace, value) pairs already in normal form (row_attributes).
+    With a `device` the two arrays are uploaded (8 bytes per row + 4 per attribute of HBM); without one the object is
+    plain arrays, which is all compile_attr_predicates needs."""
+
+    def __init__(self, row_attrs: Sequence[Iterable[Attr]], device=None, generation: Optional[int] = None) -> None:
+        id_of: Dict[Attr, int] = {}
+        number = id_of.setdefault
+        self.n = len(row_attrs)
+        ptr = np.zeros(self.n + 1, dtype=np.int64)
+        ids: List[int] = []
+        for i, attrs in enumerate(row_attrs):
+            ids.extend(number(a, len(id_of)) for a in attrs)
+            ptr[i + 1] = len(ids)
+        self.attr_ptr = ptr
+        self.attr_ids = np.asarray(ids, dtype=np.int32)
+        self.id_of = id_of
+        self.n_attrs = len(id_of)
+        self.generation = generation
+        self.device = device
+        self.d_attr_ptr = self.d_attr_ids = None
+        self._slots: dict = {}
+        if device is not None:
+            import torch
+            self.d_attr_ptr = torch.from_numpy(self.attr_ptr).to(device)
+            # (never empty: a row list without attributes still hands the kernel a valid address)
+            self.d_attr_ids = torch.from_numpy(self.attr_ids if self.attr_ids.size else np.zeros(1, dtype=np.int32)).to(device)
+
+    _slot = FilterColumns._slot
+    close = FilterColumns.close
+    __del__ = FilterColumns.__del__
+
+    def masks(self, compiled: Tuple[np.ndarray, np.ndarray, np.ndarray], in_mask=None, in_stride: int = 0,
+              stride: Optional[int] = None, out=None, stream: Optional[int] = None, nq: Optional[int] = None):
+        """Enqueue the kernel for compiled clauses (compile_attr_predicates) on `stream` (default: torch's current
+        stream): a uint8 CUDA tensor [nq, stride], every byte written.  `in_mask`: a uint8 CUDA tensor ANDed in -- one
+        run shared by all queries (in_stride 0) or one run of in_stride bytes per query; it may be `out` itself with
+        in_stride == stride (in place).  A batch that lists more than 512 distinct keys (CRAG_E2BIG) is split by queries
+        into row slices of `out`; a single query above 512 keys is a ValueError.  `nq`: the number of queries, by default
+        the rows of `out`, else the number up to the last query that has a clause.  No host synchronisation."""
+        import torch
+        if self.device is None:
+            raise _native.NativeLibraryError("these AttributeColumns were built without a device")
+        keys, key_sets, clause_sets = compiled
+        clause_sets = np.ascontiguousarray(clause_sets, dtype=np.uint64)
+        if nq is None:
+            nq = max(int(w).bit_length() for w in clause_sets) if out is None else int(out.shape[0])
+        nq = int(nq)
+        if not 1 <= nq <= MAX_QUERIES:
+            raise ValueError(f"an attribute batch holds 1 to {MAX_QUERIES} queries")
+        stride = mask_bytes(self.n) if stride is None else int(stride)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        if out is None:
+            from .fusion import _on_stream
+            with _on_stream(stream, self.device):
+                out = torch.empty((nq, stride), dtype=torch.uint8, device=self.device)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != (nq, stride) or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 [{nq}, {stride}] tensor")
+        if stride == 0:   # an empty table: the runs are empty
+            return out
+        self._run(np.ascontiguousarray(keys, dtype=np.int32), np.ascontiguousarray(key_sets, dtype=np.uint64).reshape(-1, MAX_CLAUSES),
+                  clause_sets, 0, nq, None if in_mask is None else in_mask.data_ptr(), int(in_stride), out.data_ptr(), stride, stream)
+        return out
+
+    def _run(self, keys, key_sets, clause_sets, q0: int, nq: int, in_ptr, in_stride: int, out_ptr: int, stride: int,
+             stream: int) -> None:
+        """Queries [q0, q0 + nq) of the compiled batch into their rows of the output."""
+        span = np.uint64((1 << nq) - 1)
+        sets = (key_sets >> np.uint64(q0)) & span
+        listed = sets.any(axis=1)
+        k, s = np.ascontiguousarray(keys[listed]), np.ascontiguousarray(sets[listed])
+        c = np.ascontiguousarray((clause_sets >> np.uint64(q0)) & span)
+        rc = _native.load().crag_attr_masks_host(
+            self.d_attr_ptr.data_ptr() if self.n else None, self.d_attr_ids.data_ptr() if self.n else None, self.n,
+            self.n_attrs, k.ctypes.data if k.size else None, s.ctypes.data if k.size else None, int(k.size), c.ctypes.data,
+            nq, None if in_ptr is None else in_ptr + q0 * in_stride, in_stride, self._slot(stream), out_ptr + q0 * stride,
+            stride, ctypes.c_void_p(stream))
+        if rc != _native.CRAG_E2BIG:
+            _native.check(rc, "crag_attr_masks_host")
+            return
+        if nq == 1:
+            raise ValueError(f"one query lists {int(k.size)} distinct attribute keys, a call takes {MAX_KEYS}")
+        half = nq // 2
+        self._run(keys, key_sets, clause_sets, q0, half, in_ptr, in_stride, out_ptr, stride, stream)
+        self._run(keys, key_sets, clause_sets, q0 + half, nq - half, in_ptr, in_stride, out_ptr, stride, stream)
+
+
+def compile_attr_predicates(columns: AttributeColumns, batch: Sequence[Tuple[Any, Optional[Sequence[Any]]]]
+                            ) -> Optional[Tuple[np.ndarray, np.ndarray, np.ndarray]]:
+    """batch: up to 64 (filters, call_ids) pairs, the arguments of DenseTable.filter_mask (the call ids play no part).
+    None when no query has an attribute clause, else (keys, key_sets, clause_sets), the host arguments of
+    crag_attr_masks_host: int32 [n_keys] strictly ascending dictionary ids, uint64 [n_keys, 8] with bit q of word (j, c)
+    set iff clause c of query q lists key j, uint64 [8] with bit q of word c set iff query q has a clause c.  A key the
+    dictionary does not hold is dropped from its clause; a clause left without keys admits nothing.  The cost is in the
+    number of keys, never rows; no GPU is needed."""
+    nq = len(batch)
+    if nq > MAX_QUERIES:
+        raise ValueError(f"a filter batch holds at most {MAX_QUERIES} queries (got {nq}): the caller splits it")
+    clause_sets = np.zeros(MAX_CLAUSES, dtype=np.uint64)
+    sets: Dict[int, List[int]] = {}
+    id_of = columns.id_of
+    for q, (filters, _call_ids) in enumerate(batch):
+        for c, clause in enumerate(attr_clauses(filters)):
+            clause_sets[c] |= np.uint64(1 << q)
+            for key in clause:
+                j = id_of.get(key)
+                if j is not None:
+                    sets.setdefault(j, [0] * MAX_CLAUSES)[c] |= 1 << q
+    if not clause_sets.any():
+        return None
+    keys = np.asarray(sorted(sets), dtype=np.int32)
+    key_sets = np.asarray([sets[int(j)] for j in keys], dtype=np.uint64).reshape(-1, MAX_CLAUSES)
+    return keys, key_sets, clause_sets

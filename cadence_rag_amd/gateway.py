@@ -12,7 +12,7 @@ retrieve.retrieve_evidence and the backend registered with retrieve.set_backend(
 from __future__ import annotations
 
 from datetime import datetime
-from typing import List, Literal, Optional
+from typing import Dict, List, Literal, Optional
 from uuid import UUID
 
 from fastapi import FastAPI, HTTPException
@@ -108,6 +108,10 @@ class RetrieveFiltersModel(BaseModel):
     external_id: Optional[str] = None
     external_source: Optional[str] = None
     call_tags: Optional[List[str]] = None
+    # row-level filters: [{"label": ..., "value": ...}] ANDed; any of `speakers`; any of `kinds`
+    entity_filters: Optional[List[Dict[str, str]]] = None
+    speakers: Optional[List[str]] = None
+    kinds: Optional[List[str]] = None
 
 
 class RetrieveRequestModel(BaseModel):

@@ -34,6 +34,12 @@ class RetrieveFilters:
     external_id: Optional[str] = None
     external_source: Optional[str] = None
     call_tags: Optional[List[str]] = None
+    # row-level filters, planned by the reference (PHASED_PLAN.md:355-380, APP_SPEC.md:616-619) and its own here
+    # (DESIGN.md 4.13): every {"label", "value"} entry must be among the row's entities; the row's speaker is one of
+    # `speakers`; its kind is one of `kinds`
+    entity_filters: Optional[List[Dict[str, str]]] = None
+    speakers: Optional[List[str]] = None
+    kinds: Optional[List[str]] = None
 
 
 def _resolve_call_ids(calls: Sequence[Dict[str, Any]], filters: Optional[RetrieveFilters]
@@ -89,7 +95,13 @@ def _dense_has_scoping(filters: Optional[RetrieveFilters], call_ids: Optional[Se
         return True
     if not filters:
         return False
-    return bool(filters.date_from or filters.date_to or filters.call_tags)
+    return bool(filters.date_from or filters.date_to or filters.call_tags or _has_attr_filters(filters))
+
+
+def _has_attr_filters(filters: Optional[RetrieveFilters]) -> bool:
+    """The request carries a row-level clause (entity_filters, speakers or kinds; a falsy field is not applied)."""
+    return bool(filters) and bool(getattr(filters, "entity_filters", None) or getattr(filters, "speakers", None)
+                                  or getattr(filters, "kinds", None))
 
 
 def _choose_dense_mode(estimated_rows: int, filters: Optional[RetrieveFilters],
@@ -127,6 +139,10 @@ class DenseTable:
         # per-row tech_tokens (the `tech_tokens text[]` column), kept once a tech lane was built so that the lane
         # can be rebuilt when the table changes; None = not tracked
         self.tech_tokens: Optional[List[List[str]]] = None
+        # per-row entities ((label, value) pairs), tracked from the first batch that carries `columns["entities"]`;
+        # None = never tracked: the entity namespaces are NULL in this table
+        self.entities: Optional[List[List[Tuple[Any, Any]]]] = None
+        self._attr_cols = None
         # device filter columns (cadence_rag_amd.filters), built on first use per generation, and the one mask the
         # lanes of a request share
         self._filter_cols = None
@@ -138,7 +154,9 @@ class DenseTable:
     def close(self) -> None:
         if self._filter_cols is not None:
             self._filter_cols.close()
-        self._filter_cols = self._mask_memo = None
+        if getattr(self, "_attr_cols", None) is not None:
+            self._attr_cols.close()
+        self._filter_cols = self._attr_cols = self._mask_memo = None
         self.index.close()
 
     def _take_tokens(self, columns: Dict[str, Sequence[Any]], n: int) -> Tuple[Dict[str, Sequence[Any]], List[List[str]]]:
@@ -152,13 +170,40 @@ class DenseTable:
             raise ValueError("tech_tokens must have one entry per vector")
         return columns, toks
 
+    def _take_entities(self, columns: Dict[str, Sequence[Any]], n: int
+                       ) -> Tuple[Dict[str, Sequence[Any]], Optional[List[List[Tuple[Any, Any]]]]]:
+        """Split an optional "entities" entry off the SELECTed columns the way `_take_tokens` splits "tech_tokens": per
+        row a list of (label, value) pairs or {"label", "value"} dicts (the chunk_entities / artifact_entities join).
+        None when the batch carries none."""
+        if "entities" not in columns:
+            return columns, None
+        from .filters import _entity_pair
+        columns = dict(columns)
+        ents = [[tuple(_entity_pair(e)) for e in (listed or ())] for listed in columns.pop("entities")]
+        if len(ents) != n:
+            raise ValueError("entities must have one entry per vector")
+        return columns, ents
+
+    def _new_entities(self, n_old: int, ents: Optional[List[List[Tuple[Any, Any]]]], n: int
+                      ) -> Optional[List[List[Tuple[Any, Any]]]]:
+        """The entities n new rows contribute, or None while the table tracks none: tracking starts with the first batch
+        that carries them (the n_old stored rows then hold []), a later batch without them contributes [] per row."""
+        if ents is not None and self.entities is None:
+            self.entities = [[] for _ in range(n_old)]
+        if self.entities is None:
+            return None
+        return ents if ents is not None else [[] for _ in range(n)]
+
     def add(self, vectors, columns: Dict[str, Sequence[Any]], call_started_at: Optional[Sequence[Any]] = None,
             call_tags: Optional[Dict[Any, Sequence[str]]] = None) -> None:
         """Append rows whose ids are ascending and above every stored id (the C ABI's contract); the
         index grows when its capacity is exhausted.  Rows that may arrive out of id order go through
-        `insert`.  `columns` may carry "tech_tokens" (per-row token lists) for the exact-token lane."""
+        `insert`.  `columns` may carry "tech_tokens" (per-row token lists) for the exact-token lane and "entities"
+        (per-row lists of (label, value) pairs or {"label", "value"} dicts) for the entity filters."""
         n = len(columns[self.id_field])
         columns, toks = self._take_tokens(columns, n)
+        columns, ents = self._take_entities(columns, n)
+        n_old = len(self.call_ids)
         if any(len(v) != n for v in columns.values()):
             raise ValueError("all columns must have one entry per vector")
         ids = np.asarray(columns[self.id_field], dtype=np.int64)
@@ -174,6 +219,9 @@ class DenseTable:
             self.call_tags.update(call_tags)
         if self.tech_tokens is not None:
             self.tech_tokens.extend(toks)
+        ents = self._new_entities(n_old, ents, n)
+        if ents is not None:
+            self.entities.extend(ents)
         self._pos_of_id = None
         self.generation += 1
 
@@ -220,6 +268,7 @@ class DenseTable:
         if (old_ids.size == 0 or new_ids.min() > old_ids[-1]) and np.all(np.diff(new_ids) > 0):
             return self.add(vectors, columns, call_started_at, call_tags)
         columns, toks = self._take_tokens(columns, n)
+        columns, ents = self._take_entities(columns, n)
         if any(len(v) != n for v in columns.values()):
             raise ValueError("all columns must have one entry per vector")
         all_ids = np.concatenate([old_ids, new_ids])
@@ -250,6 +299,10 @@ class DenseTable:
         if self.tech_tokens is not None:
             merged_t = self.tech_tokens + toks
             self.tech_tokens = [merged_t[i] for i in order]
+        ents = self._new_entities(int(old_ids.size), ents, n)
+        if ents is not None:
+            merged_e = self.entities + ents
+            self.entities = [merged_e[i] for i in order]
         self._pos_of_id = None
         self.generation += 1
 
@@ -262,12 +315,14 @@ class DenseTable:
         self.call_started_at = self.call_started_at[keep]
         if self.tech_tokens is not None:
             self.tech_tokens = [self.tech_tokens[i] for i in kept]
+        if getattr(self, "entities", None) is not None:
+            self.entities = [self.entities[i] for i in kept]
         self._pos_of_id = None
         self.generation += 1   # row positions moved: the exact-token lane and the BM25 lane rebuild
 
     def delete(self, ids) -> int:
         """Remove the rows with these ids (absent ids are ignored) from the index, in place, and from the
-        columns, call ids, timestamps and tech tokens.  Returns the number of rows removed.  `call_tags`
+        columns, call ids, timestamps, tech tokens and entities.  Returns the number of rows removed.  `call_tags`
         entries of calls that have no rows left may stay."""
         old_ids = np.asarray(self.columns.get(self.id_field, []), dtype=np.int64)
         keep = ~np.isin(old_ids, np.asarray(list(ids), dtype=np.int64))
@@ -296,7 +351,8 @@ class DenseTable:
     def sink(self, row_columns):
         """Backfill sink (embedding_pipeline.BackfillStore.update_embeddings -> HBM): an object whose
         `add(vectors, ids=...)` asks `row_columns(ids)` for the rows' SELECTed columns — a dict of column
-        lists that may also carry "call_started_at" and "tech_tokens" — and inserts them here, so that the
+        lists that may also carry "call_started_at", "tech_tokens" and "entities" (per-row lists of (label, value) pairs
+        or {"label", "value"} dicts, the rows' chunk_entities / artifact_entities) — and inserts them here, so that the
         host-side columns, the filter masks, the exact-token lane and the index stay one table.  `vectors` may be
         host lists / arrays or a CUDA tensor (DeviceSinkStore)."""
         table = self
@@ -332,7 +388,22 @@ class DenseTable:
                 tags = set(filters.call_tags)
                 ok_calls = {c for c, t in self.call_tags.items() if tags.intersection(t or ())}
                 land(np.fromiter((c in ok_calls for c in self.call_ids), dtype=bool, count=n))
+            if _has_attr_filters(filters):
+                # row-level clauses: AND across clauses, OR inside one; a namespace this table lacks is
+                # NULL and fails every clause over it
+                from .filters import attr_clauses
+                rows = [frozenset(attrs) for attrs in self._row_attrs()]
+                for clause in attr_clauses(filters):
+                    wanted_attrs = frozenset(clause)
+                    land(np.fromiter((not wanted_attrs.isdisjoint(attrs) for attrs in rows), dtype=bool, count=n))
         return keep
+
+    def _row_attrs(self):
+        """Per row its attributes as (namespace, value) pairs in normal form: the `speaker` entry, the `kind` entry (where
+        the table has the column) and the tracked entities."""
+        from .filters import row_attributes
+        return row_attributes(len(self), self.columns.get("speaker"), self.columns.get("kind"),
+                              getattr(self, "entities", None))
 
     def _call_positions(self) -> Dict[Any, np.ndarray]:
         """call id -> the ascending positions of its rows, built in one host pass per (generation, length), the way
@@ -351,10 +422,10 @@ class DenseTable:
         """np.flatnonzero(filter_mask(filters, call_ids)) for a call-scoped request, without a pass over all rows:
         the rows of the scoped calls come from the call -> positions map, the date and tag predicates are applied to
         those positions only.  None when the route does not apply: `filters` is falsy (filter_mask honours call_ids
-        only under truthy filters), call_ids is None, or the scoped calls together hold more than `limit` rows.
-        Host only."""
-        if not filters or call_ids is None:
-            return None
+        only under truthy filters), call_ids is None, the request carries an attribute clause (entity_filters, speakers,
+        kinds), or the scoped calls together hold more than `limit` rows.  Host only."""
+        if not filters or call_ids is None or _has_attr_filters(filters):
+            return None   # (a row-level clause: the masked scan answers, same rows and score bits by construction)
         by_call = self._call_positions()
         parts = [by_call[c] for c in set(call_ids) if c in by_call]
         if sum(int(p.size) for p in parts) > int(limit):
@@ -388,6 +459,24 @@ class DenseTable:
                                                      generation=self.generation)
         return cols
 
+    def attribute_columns(self):
+        """The table's device attribute columns (filters.AttributeColumns: the rows' speaker, kind and entities as a CSR
+        of dictionary ids in HBM, 8 bytes per row + 4 per attribute), built in one host pass on first use and again when
+        `generation` or the length changed, like `filter_columns`.  Only a request with an attribute clause builds
+        them."""
+        import torch
+
+        from .filters import AttributeColumns
+        cols = getattr(self, "_attr_cols", None)
+        if cols is None or cols.generation != self.generation or cols.n != len(self):
+            if cols is not None:
+                torch.cuda.synchronize(self.index.device)   # a mask kernel in flight may still read the old columns
+                cols.close()
+            self._mask_memo = None
+            cols = self._attr_cols = AttributeColumns(self._row_attrs(), device=torch.device("cuda", self.index.device),
+                                                      generation=self.generation)
+        return cols
+
     def filter_masks_device(self, batch: Sequence[Tuple[Optional[RetrieveFilters], Optional[Sequence[UUID]]]],
                             stream: Optional[int] = None):
         """Per-query masks for a batch of up to 64 (filters, call_ids) pairs -- the arguments of `filter_mask` --
@@ -395,12 +484,24 @@ class DenseTable:
         mask_stride=) and the lanes take.  An unfiltered query gets all ones up to len(self).  Enqueued on `stream`
         (default: torch's current stream) without a host synchronisation: a consumer on another stream orders itself
         behind it.  More than 64 queries: ValueError, the caller splits."""
-        from .filters import compile_predicates
+        from .filters import compile_attr_predicates, compile_predicates, is_unfiltered
         batch = list(batch)
         if not batch:
             raise ValueError("filter_masks_device needs at least one query")
         cols = self.filter_columns()
-        out = cols.masks(*compile_predicates(cols, self.call_tags, batch), stream=stream)
+        compiled = compile_predicates(cols, self.call_tags, batch)
+        if not any(_has_attr_filters(f) for f, _ in batch):
+            out = cols.masks(*compiled, stream=stream)
+            return out, int(out.shape[1])
+        # attribute clauses: their kernel runs in place behind the filter kernel on the same stream, or alone (no input
+        # mask) when no query carries a call or date predicate
+        acols = self.attribute_columns()
+        attrs = compile_attr_predicates(acols, batch)
+        if is_unfiltered(*compiled):
+            out = acols.masks(attrs, stream=stream, nq=len(batch))
+        else:
+            out = cols.masks(*compiled, stream=stream)
+            acols.masks(attrs, in_mask=out, in_stride=int(out.shape[1]), stride=int(out.shape[1]), out=out, stream=stream)
         return out, int(out.shape[1])
 
     def filter_mask_device(self, filters: Optional[RetrieveFilters], call_ids: Optional[Sequence[UUID]]):
@@ -409,19 +510,37 @@ class DenseTable:
         return (the producing stream is synchronised once), so the synchronous entries of the index, which run on a
         stream of their own, may read it; the lanes of one request ask for the same predicates eight times and get the
         same tensor (a one-entry memo per table, dropped with the generation).  `call_tags` that change reach the memo
-        through `add` / `insert`, which bump the generation."""
+        through `add` / `insert`, which bump the generation.  A request with row-level clauses (entity_filters, speakers,
+        kinds) also runs the attribute kernel (crag_attr_masks_host); one without them never builds the attribute columns."""
         import torch
 
-        from .filters import compile_predicates
-        if not filters or not (filters.date_from or filters.date_to or call_ids is not None or filters.call_tags):
+        from .filters import compile_attr_predicates, compile_predicates
+        by_attr = _has_attr_filters(filters)
+        by_call = bool(filters) and bool(filters.date_from or filters.date_to or call_ids is not None or filters.call_tags)
+        if not by_call and not by_attr:
             return None
         cols = self.filter_columns()
         key = (cols.generation, cols.n, filters.date_from, filters.date_to,
                None if call_ids is None else tuple(call_ids), tuple(filters.call_tags or ()))
+        if by_attr:
+            key += (tuple((e.get("label"), e.get("value")) if isinstance(e, dict) else tuple(e)
+                          for e in getattr(filters, "entity_filters", None) or ()),
+                    tuple(getattr(filters, "speakers", None) or ()), tuple(getattr(filters, "kinds", None) or ()))
         if self._mask_memo is not None and self._mask_memo[0] == key:
             return self._mask_memo[1]
-        compiled = compile_predicates(cols, self.call_tags, [(filters, call_ids)])
-        mask = cols.masks(*compiled)[0]
+        if by_attr:
+            # the attribute kernel runs in place behind the filter kernel on the same stream; without a call or date
+            # predicate it runs alone, with no input mask (one launch, not two)
+            acols = self.attribute_columns()
+            attrs = compile_attr_predicates(acols, [(filters, call_ids)])
+            if by_call:
+                run = cols.masks(*compile_predicates(cols, self.call_tags, [(filters, call_ids)]))
+                acols.masks(attrs, in_mask=run, in_stride=int(run.shape[1]), stride=int(run.shape[1]), out=run)
+            else:
+                run = acols.masks(attrs, nq=1)
+            mask = run[0]
+        else:
+            mask = cols.masks(*compile_predicates(cols, self.call_tags, [(filters, call_ids)]))[0]
         torch.cuda.current_stream(cols.device).synchronize()
         self._mask_memo = (key, mask)
         return mask
@@ -503,7 +622,9 @@ class DenseTable:
             SELECT <select>, call_started_at, tech_tokens, embedding FROM <name>
             WHERE embedding IS NOT NULL ORDER BY <id_field>
         with `embedding` in any of pgvector's forms (text literal '[v,...]', binary send/recv bytes, or a
-        sequence of floats).  Returns the table and the per-row tech_tokens (for build_tech_lane).  Rows must
+        sequence of floats).  A row may also carry "entities": its (label, value) pairs or {"label", "value"} dicts
+        (the join to chunk_entities / artifact_entities), which the table keeps for the entity filters as it keeps
+        "speaker" and "kind" among the SELECTed columns.  Returns the table and the per-row tech_tokens (for build_tech_lane).  Rows must
         come in ascending id order so that equal scores resolve to the lower id, as ORDER BY does.  The
         index is allocated with `headroom` spare capacity for the rows ingest / backfill add later (it
         also grows on demand, see `_reserve`)."""
@@ -534,6 +655,8 @@ class DenseTable:
                 last_id = rid
                 tokens.append(list(row.get("tech_tokens") or []))
             cols = {c: [row[c] for row in part] for c in select}
+            if any("entities" in row for row in part):
+                cols["entities"] = [row.get("entities") or [] for row in part]
             table.add(vecs, cols, call_started_at=[row.get("call_started_at") for row in part],
                       call_tags=call_tags if lo == 0 else None)
         return table, tokens

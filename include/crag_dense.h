@@ -389,6 +389,51 @@ int crag_filter_masks_host(const int64_t *d_started_us, const int32_t *d_call_sl
                            const uint64_t *h_call_qset, const int64_t *h_date_from, const int64_t *h_date_to, int nq,
                            crag_upload_slot *slot, uint8_t *d_out_mask, int64_t mask_stride, void *stream);
 
+/* Attribute row masks for up to 64 queries: row-level filters by entity, speaker and kind, built on the device from a
+ * device-resident CSR of per-row attribute ids.  The reference plans these filters and has no code for
+ * them: PHASED_PLAN.md:355-380 (RetrieveFilters.entity_filters = [{label, value}], "implemented in SQL using joins to
+ * entities/mentions"), APP_SPEC.md:311-341 (entities, chunk_entities, artifact_entities), APP_SPEC.md:616-619 (entity
+ * constraints; the who_said intent is a speaker constraint).  The rule is this tree's own.
+ *   d_attr_ptr [n_rows+1] int64, d_attr_ids [d_attr_ptr[n_rows]] int32: CSR by row POSITION; the ids are those of the
+ *                         table's attribute dictionary (exact strings numbered by first appearance, no hashing).
+ *                         Duplicates inside a row are allowed.  An id outside [0, n_attrs) matches nothing and is never
+ *                         used as an index.
+ *   h_keys [n_keys] HOST  the distinct attribute ids any query lists: strictly ascending, in [0, n_attrs)
+ *   h_key_sets [n_keys][8] HOST: bit q of word (j, c) set <=> clause c of query q lists key j
+ *   h_clause_sets [8] HOST: bit q of word c set <=> query q has a clause c.  A clause bit with no key anywhere admits
+ *                         nothing.
+ *   d_in_mask             nullable (NULL: every row is admitted): masks in the row_mask encoding of crag_index_search,
+ *                         in_stride == 0: one run shared by all queries, otherwise one run per query (a multiple of 4
+ *                         >= ceil(n_rows/32)*4); 4-byte aligned; bits at positions >= n_rows are ignored.
+ *                         d_in_mask == d_out_mask with in_stride == mask_stride is allowed (in place); any other
+ *                         overlap is undefined.
+ * Bit (q, i) is set iff i < n_rows and in(q, i) and, for every c with bit q of clause_sets[c], some attribute a of row i
+ * equals keys[j] with bit q of key_sets[j][c]: AND across a query's clauses, OR inside a clause.
+ * NULL rule: a namespace a table lacks (no speaker column, entities never tracked) has no attribute in any row and no key
+ * in the dictionary, so every clause over it admits nothing -- what SQL does with NULL = ANY(...), and the NaT rule of
+ * crag_filter_masks_host.
+ *   d_out_mask  nq runs of mask_stride bytes in the row_mask encoding of crag_index_search (4-byte aligned); mask_stride a
+ *               multiple of 4 >= ceil(n_rows/32)*4.  EVERY byte of every run is written -- bits at positions >= n_rows
+ *               and the bytes up to mask_stride are 0 --, nothing outside nq * mask_stride bytes is; plain stores, never
+ *               OR: the buffer may be uninitialised and reused.  The output depends on the input alone, whatever the
+ *               launch geometry.
+ *   slot        an upload slot as for crag_tech_lane_host: ONE host-to-device copy per call (keys + their sets)
+ * Everything is enqueued on `stream`, no host synchronisation.
+ * CRAG_EINVAL with a message that contains "attr_masks_host", checked before any HIP call, nothing enqueued: NULL
+ * required pointer, nq outside 1..64, n_rows outside [0, 2^31), n_attrs < 0, n_keys < 0, keys not strictly ascending or
+ * out of range, a set bit at or above nq, key_sets[j][c] not a subset of clause_sets[c], bad mask_stride or in_stride, a
+ * misaligned output or input mask.
+ * CRAG_E2BIG, nothing enqueued: n_keys > CRAG_ATTR_MAX_KEYS -- the caller splits the batch by queries.
+ * n_rows == 0 is CRAG_OK (the runs are zeroed when mask_stride > 0). */
+#define CRAG_ATTR_MAX_QUERIES 64
+#define CRAG_ATTR_MAX_CLAUSES 8
+#define CRAG_ATTR_MAX_KEYS    512   /* distinct keys per call */
+int crag_attr_masks_host(const int64_t *d_attr_ptr, const int32_t *d_attr_ids, int64_t n_rows, int64_t n_attrs,
+                         const int32_t *h_keys, const uint64_t *h_key_sets, int n_keys,
+                         const uint64_t *h_clause_sets, int nq,
+                         const uint8_t *d_in_mask, int64_t in_stride,
+                         crag_upload_slot *slot, uint8_t *d_out_mask, int64_t mask_stride, void *stream);
+
 /* Live kernel timing for bench.py's roofline: enabled = N > 0 records HIP events around the scan
  * (and merge) kernel of every N-th search, on the stream it is launched on (N = 1: every search;
  * larger N perturbs the timed region less); 0 disables.  crag_index_profile_read sums and clears
