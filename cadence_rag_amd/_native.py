@@ -24,6 +24,9 @@ CRAG_FILTER_MAX_QUERIES = 64
 CRAG_ATTR_MAX_QUERIES = 64
 CRAG_ATTR_MAX_CLAUSES = 8
 CRAG_ATTR_MAX_KEYS = 512
+CRAG_FACET_MAX_QUERIES = 64
+CRAG_FACET_MAX_NAMESPACES = 16
+CRAG_FACET_MAX_TOP = 64
 CRAG_E2BIG = -5
 
 # every symbol include/crag_dense.h declares: name -> (restype, argtypes)
@@ -62,6 +65,9 @@ SIGNATURES = {
     "crag_filter_masks_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P, _P, _c.c_int, _P, _P, _c.c_int64, _P]),
     "crag_attr_masks_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int64, _P, _P,
                                         _c.c_int64, _P]),
+    "crag_facet_workspace_bytes": (_c.c_int64, [_c.c_int64, _c.c_int, _c.c_int64, _c.c_int]),
+    "crag_facet_counts_host": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _c.c_int64, _P, _P, _c.c_int,
+                                          _c.c_int, _c.c_int, _P, _c.c_int64, _P, _P, _P, _P, _P]),
     "crag_index_profile_enable": (_c.c_int, [_P, _c.c_int]),
     "crag_index_profile_read": (_c.c_int, [_P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_double),
                                            _c.POINTER(_c.c_double)]),

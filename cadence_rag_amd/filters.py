@@ -12,7 +12,12 @@ Row-level predicates -- entity, speaker and kind -- go the same
 "entity:" + LABEL; a table's AttributeColumns hold them as a CSR of dictionary ids in HBM (8 bytes per row + 4 per
 attribute); compile_attr_predicates turns a request's entity_filters / speakers / kinds into clauses of keys (a cost in
 keys, never in rows), and a row passes iff every clause is hit by one of its attributes.  A namespace a table lacks is
-NULL there and fails every clause over it, so a `speakers` filter returns no artifact rows."""
+NULL there and fails every clause over it, so a `speakers` filter returns no artifact rows.
+
+Facet counts -- which speakers, kinds and entities the rows under a filter carry, and how many rows hold
+each -- come from a third set of columns, FacetColumns: the same attributes renumbered by (namespace, value) and stored as
+postings (8 bytes per posting + 8 per attribute of HBM), counted by crag_facet_counts_host under the masks the two
+kernels above write.  facets_host is the host form of the rule."""
 from __future__ import annotations
 
 import ctypes
@@ -364,3 +369,178 @@ def compile_attr_predicates(columns: AttributeColumns, batch: Sequence[Tuple[Any
     keys = np.asarray(sorted(sets), dtype=np.int32)
     key_sets = np.asarray([sets[int(j)] for j in keys], dtype=np.uint64).reshape(-1, MAX_CLAUSES)
     return keys, key_sets, clause_sets
+
+
+# ---- facet counts: attribute histograms under a filter (crag_facet_counts_host) ---------------------
+MAX_FACET_NAMESPACES = _native.CRAG_FACET_MAX_NAMESPACES
+MAX_FACET_TOP = _native.CRAG_FACET_MAX_TOP
+FACET_TABLE_BYTES = 256 << 20   # the count table a call allocates by default, at most: a larger batch is split by queries
+
+
+def facet_namespace(name) -> str:
+    """A requested namespace in the form row_attributes produces: "speaker", "kind", or "entity:" + LABEL with the label
+    normalised by entity_namespace."""
+    name = str(name).strip()
+    return entity_namespace(name[len("entity:"):]) if name[:len("entity:")].lower() == "entity:" else name
+
+
+def facets_host(row_attrs: Sequence[Iterable[Attr]], mask_bits, namespaces: Sequence[str], top: int
+                ) -> Tuple[int, Dict[str, Tuple[List[Tuple[str, int]], int]]]:
+    """The host rule of the facet counts, kept as public oracle the way DenseTable.filter_mask is for the masks.
+    row_attrs: per row its (namespace, value) pairs in normal form; mask_bits: per row a truth value, or None for every
+    row.  Returns (rows, {namespace as given: ([(value, count), ...], distinct)}): rows = the rows that pass; count = the
+    passing rows that hold the attribute at least once; the list holds the `top` attributes of the namespace with
+    count > 0 by count descending, then value ascending (str order); distinct = how many there are before the cut."""
+    if not 1 <= int(top) <= MAX_FACET_TOP:
+        raise ValueError(f"top must be in 1..{MAX_FACET_TOP}")
+    wanted = {facet_namespace(ns) for ns in namespaces}
+    tallies: Dict[str, Dict[str, int]] = {ns: {} for ns in wanted}
+    rows = 0
+    for i, attrs in enumerate(row_attrs):
+        if mask_bits is not None and not mask_bits[i]:
+            continue
+        rows += 1
+        for namespace, value in set(attrs):
+            if namespace in wanted:
+                tally = tallies[namespace]
+                tally[value] = tally.get(value, 0) + 1
+    out = {}
+    for ns in namespaces:
+        tally = tallies[facet_namespace(ns)]
+        out[ns] = (sorted(tally.items(), key=lambda kv: (-kv[1], kv[0]))[:int(top)], len(tally))
+    return rows, out
+
+
+class FacetColumns:
+    """The facet columns of one table, built from its AttributeColumns in ONE host pass of numpy sorts per table
+    generation (no loop over rows):
+
+    * facet ids: the dictionary's attributes renumbered by (namespace, value) ascending (Python str order), so that a
+      namespace is one contiguous range `ranges[namespace] = (lo, hi)` and ascending facet id is ascending value -- the
+      tie order of the lists, independent of the dictionary's first-appearance numbering.  `facet_keys[fid]` is the
+      (namespace, value) of a facet id.
+    * postings: the transpose of the CSR -- `post_ptr` int64 [n_attrs + 1], `post_rows` int32 ascending within an
+      attribute, `post_fid` int32 parallel to it (a lane knows its attribute without a search); each (attribute, row)
+      pair once: the duplicates a row may list are removed here.
+
+    HBM with a `device`: 8 bytes per posting (row + facet id) + 8 per attribute.  Without one the object is plain arrays."""
+
+    def __init__(self, attrs: AttributeColumns, device=None, generation: Optional[int] = None) -> None:
+        self.n = int(attrs.n)
+        self.n_attrs = int(attrs.n_attrs)
+        keys = list(attrs.id_of)   # in dictionary order: keys[j] has id j
+        order = sorted(range(self.n_attrs), key=keys.__getitem__)
+        self.facet_keys: List[Attr] = [keys[j] for j in order]
+        fid_of = np.empty(self.n_attrs, dtype=np.int64)
+        fid_of[np.asarray(order, dtype=np.int64)] = np.arange(self.n_attrs, dtype=np.int64)
+        self.ranges: Dict[str, Tuple[int, int]] = {}
+        for fid, (namespace, _value) in enumerate(self.facet_keys):
+            lo, _hi = self.ranges.get(namespace, (fid, fid))
+            self.ranges[namespace] = (lo, fid + 1)
+        row_of = np.repeat(np.arange(self.n, dtype=np.int64), np.diff(attrs.attr_ptr))
+        pairs = np.unique(fid_of[attrs.attr_ids] * max(self.n, 1) + row_of)   # sorted by (facet id, row), each pair once
+        self.post_fid = (pairs // max(self.n, 1)).astype(np.int32)
+        self.post_rows = (pairs % max(self.n, 1)).astype(np.int32)
+        self.n_postings = int(pairs.size)
+        self.post_ptr = np.zeros(self.n_attrs + 1, dtype=np.int64)
+        np.cumsum(np.bincount(self.post_fid, minlength=self.n_attrs), out=self.post_ptr[1:])
+        self.generation = generation
+        self.device = device
+        self.d_post_ptr = self.d_post_rows = self.d_post_fid = None
+        if device is not None:
+            import torch
+            some = lambda a: a if a.size else np.zeros(1, dtype=a.dtype)   # (never empty: a valid address)
+            self.d_post_ptr = torch.from_numpy(self.post_ptr).to(device)
+            self.d_post_rows = torch.from_numpy(some(self.post_rows)).to(device)
+            self.d_post_fid = torch.from_numpy(some(self.post_fid)).to(device)
+
+    def requested(self, namespaces: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
+        """The ranges of the requested namespaces, (lo, hi) int32 arrays; a namespace the table lacks is (0, 0)."""
+        names = [facet_namespace(ns) for ns in namespaces]
+        if len(names) > MAX_FACET_NAMESPACES:
+            raise ValueError(f"a facet call takes at most {MAX_FACET_NAMESPACES} namespaces (got {len(names)})")
+        if len(set(names)) != len(names):
+            raise ValueError("a facet call lists each namespace once")
+        pairs = [self.ranges.get(ns, (0, 0)) for ns in names]
+        return (np.asarray([p[0] for p in pairs], dtype=np.int32), np.asarray([p[1] for p in pairs], dtype=np.int32))
+
+    def counts(self, namespaces: Sequence[str], masks=None, nq: Optional[int] = None, top: int = 10,
+               stream: Optional[int] = None, workspace=None):
+        """Enqueue the facet kernels on `stream` (default: torch's current stream).  `masks`: a uint8 CUDA tensor
+        [nq, stride] in the layout filter_masks_device writes, or None for every row (then `nq`, default 1, is the number
+        of queries).  Returns CUDA tensors (ids int32 [nq, R, top] with -1 beyond a list, counts int32 [nq, R, top] with 0
+        beyond it -- the kernel's uint32, always below 2^31 --, distinct int32 [nq, R], rows int64 [nq]), every element
+        written; R = len(namespaces).  `workspace`: a uint8 CUDA tensor to use as scratch (default: allocated for the
+        call, its count table capped at FACET_TABLE_BYTES); a batch whose count table does not fit it (CRAG_E2BIG) is
+        split by queries, a single query that does not fit is a ValueError.  No host synchronisation."""
+        import torch
+        if self.device is None:
+            raise _native.NativeLibraryError("these FacetColumns were built without a device")
+        lo, hi = self.requested(namespaces)
+        top = int(top)
+        if not 1 <= top <= MAX_FACET_TOP:
+            raise ValueError(f"top must be in 1..{MAX_FACET_TOP}")
+        stride = 0
+        if masks is not None:
+            if masks.dtype != torch.uint8 or masks.dim() != 2 or not masks.is_contiguous():
+                raise ValueError("masks must be a contiguous uint8 [nq, stride] tensor")
+            if nq is not None and int(nq) != int(masks.shape[0]):
+                raise ValueError("nq must be the number of mask runs")
+            nq, stride = int(masks.shape[0]), int(masks.shape[1])
+        nq = 1 if nq is None else int(nq)
+        if not 1 <= nq <= MAX_QUERIES:
+            raise ValueError(f"a facet batch holds 1 to {MAX_QUERIES} queries")
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        n_ranges, width = int(lo.size), int((hi - lo).sum())
+        lib = _native.load()
+        from .fusion import _on_stream
+        with _on_stream(stream, self.device):
+            ids = torch.empty((nq, n_ranges, top), dtype=torch.int32, device=self.device)
+            counts = torch.empty((nq, n_ranges, top), dtype=torch.int32, device=self.device)
+            distinct = torch.empty((nq, n_ranges), dtype=torch.int32, device=self.device)
+            rows = torch.empty((nq,), dtype=torch.int64, device=self.device)
+            if workspace is None:
+                sets = int(lib.crag_facet_workspace_bytes(self.n, 0, 0, 1 if stride else 0))
+                table = int(lib.crag_facet_workspace_bytes(0, nq, width, 0))
+                workspace = torch.empty((sets + max(min(table, FACET_TABLE_BYTES), 4 * width),), dtype=torch.uint8,
+                                        device=self.device)
+        if workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+            raise ValueError("workspace must be a contiguous uint8 tensor")
+
+        def run(q0: int, n: int) -> None:
+            rc = lib.crag_facet_counts_host(
+                self.d_post_ptr.data_ptr(), self.d_post_rows.data_ptr(), self.d_post_fid.data_ptr(), self.n_postings,
+                self.n, self.n_attrs, masks.data_ptr() + q0 * stride if stride else None, stride,
+                lo.ctypes.data if n_ranges else None, hi.ctypes.data if n_ranges else None, n_ranges, n, top,
+                workspace.data_ptr() if workspace.numel() else None, int(workspace.numel()),
+                ids.data_ptr() + q0 * n_ranges * top * 4 if n_ranges else None,
+                counts.data_ptr() + q0 * n_ranges * top * 4 if n_ranges else None,
+                distinct.data_ptr() + q0 * n_ranges * 4 if n_ranges else None, rows.data_ptr() + q0 * 8,
+                ctypes.c_void_p(stream))
+            if rc != _native.CRAG_E2BIG:
+                _native.check(rc, "crag_facet_counts_host")
+                return
+            if n == 1:
+                widths = {ns: int(h - l) for ns, l, h in zip(namespaces, lo, hi)}
+                raise ValueError(f"one query's count table ({4 * width} bytes + the query sets) does not fit a workspace "
+                                 f"of {int(workspace.numel())} bytes; namespace widths: {widths}")
+            run(q0, n // 2)
+            run(q0 + n // 2, n - n // 2)
+
+        run(0, nq)
+        return ids, counts, distinct, rows
+
+    def lists(self, namespaces: Sequence[str], ids, counts, distinct, rows) -> List[Dict[str, Any]]:
+        """The host tensors / arrays of `counts` as per query {"rows", "facets": {namespace as given: {"values":
+        [{"value", "count"}], "distinct"}}}."""
+        ids, counts, distinct, rows = (np.asarray(a) for a in (ids, counts, distinct, rows))
+        out = []
+        for q in range(rows.shape[0]):
+            facets = {}
+            for r, ns in enumerate(namespaces):
+                values = [{"value": self.facet_keys[int(f)][1], "count": int(c)} for f, c in zip(ids[q, r], counts[q, r])
+                          if f >= 0]
+                facets[ns] = {"values": values, "distinct": int(distinct[q, r])}
+            out.append({"rows": int(rows[q]), "facets": facets})
+        return out

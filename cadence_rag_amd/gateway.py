@@ -121,6 +121,9 @@ class RetrieveRequestModel(BaseModel):
     budget: BudgetModel = Field(default_factory=BudgetModel)
     return_style: Literal["evidence_pack_json", "ids_only"] = "evidence_pack_json"
     debug: bool = False
+    # facet counts: namespaces to count over the rows that pass `filters`; a violation is a 422
+    facets: Optional[List[str]] = Field(default=None, max_length=16)
+    facet_top: int = Field(default=10, ge=1, le=64)
 
 
 @app.post("/retrieve")
@@ -130,7 +133,8 @@ def retrieve_endpoint(payload: RetrieveRequestModel) -> dict:
         filters = _retrieve.RetrieveFilters(**payload.filters.model_dump())
     request = _retrieve.RetrieveRequest(
         query=payload.query, intent=payload.intent, filters=filters,
-        budget=_retrieve.Budget(**payload.budget.model_dump()), return_style=payload.return_style, debug=payload.debug)
+        budget=_retrieve.Budget(**payload.budget.model_dump()), return_style=payload.return_style, debug=payload.debug,
+        facets=payload.facets, facet_top=payload.facet_top)
     try:
         return _retrieve.retrieve_evidence(request)
     except RuntimeError as exc:  # no backend registered

@@ -143,6 +143,7 @@ class DenseTable:
         # None = never tracked: the entity namespaces are NULL in this table
         self.entities: Optional[List[List[Tuple[Any, Any]]]] = None
         self._attr_cols = None
+        self._facet_cols = None   # filters.FacetColumns, built by the first facet request of a generation
         # device filter columns (cadence_rag_amd.filters), built on first use per generation, and the one mask the
         # lanes of a request share
         self._filter_cols = None
@@ -156,7 +157,7 @@ class DenseTable:
             self._filter_cols.close()
         if getattr(self, "_attr_cols", None) is not None:
             self._attr_cols.close()
-        self._filter_cols = self._attr_cols = self._mask_memo = None
+        self._filter_cols = self._attr_cols = self._facet_cols = self._mask_memo = None
         self.index.close()
 
     def _take_tokens(self, columns: Dict[str, Sequence[Any]], n: int) -> Tuple[Dict[str, Sequence[Any]], List[List[str]]]:
@@ -476,6 +477,55 @@ class DenseTable:
             cols = self._attr_cols = AttributeColumns(self._row_attrs(), device=torch.device("cuda", self.index.device),
                                                       generation=self.generation)
         return cols
+
+    def facet_columns(self):
+        """The table's device facet columns (filters.FacetColumns: the attributes renumbered by (namespace, value) and
+        stored as postings, 8 bytes per posting + 8 per attribute of HBM), built from `attribute_columns()` on first use
+        and again when `generation` or the length changed.  Only a request that asks for facets builds them."""
+        import torch
+
+        from .filters import FacetColumns
+        cols = getattr(self, "_facet_cols", None)
+        if cols is None or cols.generation != self.generation or cols.n != len(self):
+            if cols is not None:
+                torch.cuda.synchronize(self.index.device)   # a facet kernel in flight may still read the old columns
+            cols = self._facet_cols = FacetColumns(self.attribute_columns(), device=torch.device("cuda", self.index.device),
+                                                   generation=self.generation)
+        return cols
+
+    def facets(self, batch: Sequence[Tuple[Optional[RetrieveFilters], Optional[Sequence[UUID]]]],
+               namespaces: Sequence[str], top: int = 10) -> List[Dict[str, Any]]:
+        """Facet counts for a batch of up to 64 (filters, call_ids) pairs -- the arguments of
+        `filter_mask`: per query {"rows": the rows that pass its filters, "facets": {namespace: {"values": [{"value",
+        "count"}, ...], "distinct": int}}} with the `top` values of each requested namespace ("speaker", "kind",
+        "entity:LABEL", reported as given) by count descending, then value ascending; `distinct` is their number before
+        the cut.  The masks (filter_masks_device) and the counts (crag_facet_counts_host) run on one stream with ONE
+        synchronisation at the end; a batch in which no query filters anything passes no mask."""
+        import torch
+
+        from .filters import MAX_FACET_NAMESPACES, MAX_FACET_TOP, MAX_QUERIES
+        batch = list(batch)
+        names = list(dict.fromkeys(namespaces))
+        if not 1 <= len(batch) <= MAX_QUERIES:
+            raise ValueError(f"a facet batch holds 1 to {MAX_QUERIES} queries (got {len(batch)}): the caller splits it")
+        if len(names) > MAX_FACET_NAMESPACES:
+            raise ValueError(f"a facet request lists at most {MAX_FACET_NAMESPACES} namespaces (got {len(names)})")
+        if not 1 <= int(top) <= MAX_FACET_TOP:
+            raise ValueError(f"top must be in 1..{MAX_FACET_TOP}")
+        fcols = self.facet_columns()
+        stream = torch.cuda.current_stream(fcols.device)
+        masks = None
+        if any(self.filter_mask_applies(f, c) for f, c in batch):
+            masks, _stride = self.filter_masks_device(batch, stream=stream.cuda_stream)
+        out = fcols.counts(names, masks=masks, nq=len(batch), top=int(top), stream=stream.cuda_stream)
+        stream.synchronize()
+        return fcols.lists(names, *(t.cpu().numpy() for t in out))
+
+    @staticmethod
+    def filter_mask_applies(filters: Optional[RetrieveFilters], call_ids: Optional[Sequence[UUID]]) -> bool:
+        """`filter_mask(filters, call_ids)` restricts something (it returns a mask, not None)."""
+        return bool(filters) and bool(filters.date_from or filters.date_to or call_ids is not None or filters.call_tags
+                                      or _has_attr_filters(filters))
 
     def filter_masks_device(self, batch: Sequence[Tuple[Optional[RetrieveFilters], Optional[Sequence[UUID]]]],
                             stream: Optional[int] = None):
@@ -803,6 +853,17 @@ class RetrieveRequest:
     budget: Optional[Budget] = None
     return_style: str = "evidence_pack_json"
     debug: bool = False
+    # facet counts: the namespaces ("speaker", "kind", "entity:LABEL") to count over the rows that pass
+    # `filters`, and how many values of each to list; None or [] asks for none and changes nothing
+    facets: Optional[List[str]] = None
+    facet_top: int = 10
+
+    def __post_init__(self) -> None:
+        from .filters import MAX_FACET_NAMESPACES, MAX_FACET_TOP
+        if self.facets is not None and len(self.facets) > MAX_FACET_NAMESPACES:
+            raise ValueError(f"facets lists at most {MAX_FACET_NAMESPACES} namespaces (got {len(self.facets)})")
+        if not 1 <= int(self.facet_top) <= MAX_FACET_TOP:
+            raise ValueError(f"facet_top must be in 1..{MAX_FACET_TOP} (got {self.facet_top})")
 
 
 def _clip(text: str, max_chars: int) -> str:
@@ -837,6 +898,11 @@ class RetrieveBackend:
         """Near-duplicate suppression of one side's fused ids (best first): per id (slot of the kept id that suppresses
         it, their cosine) or (None, None).  A backend without vectors drops nothing."""
         return [(None, None)] * len(ids)
+
+    def facets(self, table_name, filters, call_ids, namespaces, top):
+        """Facet counts of one table over the rows that pass the request's filters: {"rows": int, "facets": {namespace:
+        {"values": [{"value", "count"}], "distinct": int}}}.  A backend without attributes has none: {}."""
+        return {}
 
 
 class GpuRetrieveBackend(RetrieveBackend):
@@ -934,6 +1000,9 @@ class GpuRetrieveBackend(RetrieveBackend):
 
     def fetch_artifacts_dense(self, query_embedding, filters, call_ids, mode, limit):
         return _fetch_artifacts_dense(self.tables["artifact_chunks"], query_embedding, filters, call_ids, mode, limit)
+
+    def facets(self, table_name, filters, call_ids, namespaces, top):
+        return self.tables[table_name].facets([(filters, call_ids)], namespaces, top)[0]
 
     def dedupe(self, table_name, ids, threshold):
         return self.tables[table_name].dedupe(ids, threshold)
@@ -1208,11 +1277,18 @@ def retrieve_evidence(payload: RetrieveRequest, backend: Optional[RetrieveBacken
     ids_only = payload.return_style == "ids_only"
     budget = payload.budget or Budget()
     query = payload.query.strip()
+    # facet counts over the rows that pass the filters (not over the ranked hits), whatever the query text and the lanes
+    # do; a request without `facets` gets no key
+    facets: Dict[str, Any] = {}
+    if getattr(payload, "facets", None):
+        call_ids = be.resolve_call_ids(payload.filters)
+        facets = {"facets": {s.table: be.facets(s.table, payload.filters, call_ids, list(payload.facets),
+                                                int(payload.facet_top)) for s in _QUERY_ORDER}}
     if not query:
         if ids_only:
-            return {**head, "retrieved_ids": []}
+            return {**head, "retrieved_ids": [], **facets}
         return {**head, "intent": payload.intent, "budget": budget.model_dump(),
-                **{s.out: [] for s in _SIDES}, "notes": {"error": "empty query"}}
+                **{s.out: [] for s in _SIDES}, "notes": {"error": "empty query"}, **facets}
 
     tokens = extract_tech_tokens(query)
     dense = _DenseState()
@@ -1236,6 +1312,7 @@ def retrieve_evidence(payload: RetrieveRequest, backend: Optional[RetrieveBacken
             packed[s.out] = _pack(fused[s.table], s, purse, cap)
         response = {**head, "intent": payload.intent, "budget": budget.model_dump(), **packed,
                     "notes": {"retrieval": _retrieval_notes(tokens, dense, rerank, dedupe)}}
+    response.update(facets)
     if payload.debug:
         response["debug"] = _debug_section(lanes, dense)
         if dedupe.on:

@@ -434,6 +434,55 @@ int crag_attr_masks_host(const int64_t *d_attr_ptr, const int32_t *d_attr_ids, i
                          const uint8_t *d_in_mask, int64_t in_stride,
                          crag_upload_slot *slot, uint8_t *d_out_mask, int64_t mask_stride, void *stream);
 
+/* Facet counts for up to 64 queries: per query and requested namespace, which attributes the rows that pass the query's
+ * mask carry and how many rows hold each -- the "facets can be computed" line of the reference's
+ * "Entities + faceting" phase (PHASED_PLAN.md:355-380), which has no code there.  The rule is this tree's own.
+ *   FACET IDS number the table's attributes by (namespace, value) ascending (cadence_rag_amd.filters.FacetColumns): a
+ *   namespace is one contiguous range [lo, hi) of ids, and ascending id is ascending value inside it.
+ *   d_post_ptr [n_attrs+1] int64, d_post_rows [n_postings] int32, d_post_fid [n_postings] int32: the postings, i.e. the
+ *                         transpose of the CSR of crag_attr_masks_host -- attribute a is held by the row positions
+ *                         d_post_rows[d_post_ptr[a] .. d_post_ptr[a+1]), ascending, each (attribute, row) pair ONCE;
+ *                         d_post_fid[j] is the attribute posting j belongs to.  A posting whose attribute lies outside
+ *                         the range being walked, or whose row lies outside [0, n_rows), counts nothing and is never used
+ *                         as an index; a d_post_ptr value outside [0, n_postings] is clamped.
+ *   d_masks               nullable (NULL: every row passes every query): nq runs of mask_stride bytes in the row_mask
+ *                         encoding of crag_index_search, what crag_filter_masks_host / crag_attr_masks_host write; 4-byte
+ *                         aligned, mask_stride a multiple of 4 >= ceil(n_rows/32)*4.  Bits at positions >= n_rows are
+ *                         ignored.
+ *   h_range_lo, h_range_hi [n_ranges] HOST: the requested namespaces as ranges of facet ids, 0 <= lo <= hi <= n_attrs,
+ *                         pairwise disjoint; lo == hi is a namespace the table lacks.  Attributes outside every range are
+ *                         never read.
+ *   d_workspace           caller-owned, 8-byte aligned, workspace_bytes large: the query sets (8 bytes per row when
+ *                         d_masks is given) followed by the count table nq x W x 4 bytes, W = the sum of hi - lo;
+ *                         crag_facet_workspace_bytes gives the sum.  Its contents before and after are meaningless.
+ * With count(q, a) = the number of i < n_rows with bit (q, i) set (or d_masks NULL) for which row i holds a:
+ *   d_out_ids [nq][n_ranges][top] int32     the facet ids of the range with count > 0, by count descending, then id
+ *                                           ascending; -1 beyond the list
+ *   d_out_counts [nq][n_ranges][top] uint32 their counts; 0 beyond the list
+ *   d_out_distinct [nq][n_ranges] int32     how many attributes of the range have count > 0
+ *   d_out_rows [nq] int64                   the number of set bits below n_rows (n_rows without masks)
+ * Every output byte is written; the outputs are a function of the inputs alone, whatever the launch geometry (integer
+ * adds only).  Everything is enqueued on `stream`, no host synchronisation, no host-to-device copy (the ranges travel as
+ * kernel arguments, which is why this entry takes no upload slot).
+ * CRAG_EINVAL with a message that contains "facet_counts_host", checked before any HIP call, nothing enqueued: nq outside
+ * 1..64, top outside 1..CRAG_FACET_MAX_TOP, n_ranges outside 0..CRAG_FACET_MAX_NAMESPACES, n_rows outside [0, 2^31),
+ * n_attrs or n_postings negative, a range outside [0, n_attrs] or with lo > hi, overlapping ranges, a misaligned mask or
+ * workspace, a bad mask_stride, a NULL required pointer (outputs; ranges when n_ranges > 0; postings when n_postings > 0;
+ * the workspace when it has to hold anything).
+ * CRAG_E2BIG, nothing enqueued: the workspace is smaller than crag_facet_workspace_bytes -- the caller splits the batch
+ * by queries. */
+#define CRAG_FACET_MAX_QUERIES    64
+#define CRAG_FACET_MAX_NAMESPACES 16
+#define CRAG_FACET_MAX_TOP        64
+int64_t crag_facet_workspace_bytes(int64_t n_rows, int nq, int64_t width, int has_masks);
+int crag_facet_counts_host(const int64_t *d_post_ptr, const int32_t *d_post_rows, const int32_t *d_post_fid,
+                           int64_t n_postings, int64_t n_rows, int64_t n_attrs,
+                           const uint8_t *d_masks, int64_t mask_stride,
+                           const int32_t *h_range_lo, const int32_t *h_range_hi, int n_ranges, int nq, int top,
+                           void *d_workspace, int64_t workspace_bytes,
+                           int32_t *d_out_ids, uint32_t *d_out_counts, int32_t *d_out_distinct, int64_t *d_out_rows,
+                           void *stream);
+
 /* Live kernel timing for bench.py's roofline: enabled = N > 0 records HIP events around the scan
  * (and merge) kernel of every N-th search, on the stream it is launched on (N = 1: every search;
  * larger N perturbs the timed region less); 0 disables.  crag_index_profile_read sums and clears
