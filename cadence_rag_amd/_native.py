@@ -28,6 +28,9 @@ CRAG_FACET_MAX_QUERIES = 64
 CRAG_FACET_MAX_NAMESPACES = 16
 CRAG_FACET_MAX_TOP = 64
 CRAG_E2BIG = -5
+CRAG_DECODE_MAX_SEQS = 8
+CRAG_DECODE_SPLIT = 128
+CRAG_LM_HEAD_MAX_BANNED = 64
 
 # every symbol include/crag_dense.h declares: name -> (restype, argtypes)
 _c = ctypes
@@ -119,6 +122,10 @@ SIGNATURES = {
     "crag_enc_attention_prefixed": (_c.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int64, _c.c_int, _c.c_int,
                                                _c.c_float, _P]),
     "crag_enc_rerank_head": (_c.c_int, [_P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_float, _P]),
+    "crag_enc_decode_workspace_bytes": (_c.c_int64, [_c.c_int, _c.c_int, _c.c_int]),
+    "crag_enc_decode_attention": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int,
+                                             _c.c_int, _c.c_float, _c.c_float, _P, _c.c_int64, _P, _P]),
+    "crag_enc_lm_head": (_c.c_int, [_P, _P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_float, _P]),
 }
 
 

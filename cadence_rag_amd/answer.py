@@ -1,0 +1,269 @@
+"""/answer: one-shot answering grounded strictly in the evidence pack, the reference's Phase 5 (PHASED_PLAN.md:312-340),
+with reranker.py's client seam: AnswerClientError, set_llm, llm_enabled, validate_citations, answer_question.
+
+LLM_BASE_URL="" turns answering off; "native" (or "native://...") routes to the in-process generator registered with
+set_llm() (cadence_rag_amd.encoder.generate.Qwen3Generator); an http(s) URL speaks the OpenAI-compatible
+`POST {base}/chat/completions`.  Every failure reaches the caller as AnswerClientError.
+
+The gate: every sentence of an answer must cite at least one evidence id of the pack (`[Q-123]`, `[A-45]`, the
+evidence_id format retrieve._pack emits).  An answer that fails is sent back with the validator's report at most
+ANSWER_MAX_REPAIRS times; if it still fails, the response carries no answer.  No uncited sentence ever leaves.
+"""
+from __future__ import annotations
+
+import re
+import threading
+from dataclasses import dataclass
+from typing import Any, Dict, List, Optional, Protocol, Sequence, Tuple
+
+from . import retrieve as _retrieve
+from .config import settings
+
+INSUFFICIENT = "INSUFFICIENT_EVIDENCE"
+STATUS_OK = "ok"
+STATUS_INSUFFICIENT = "insufficient_evidence"
+STATUS_FAILED = "citation_check_failed"
+
+SYSTEM_RULES = (
+    "You answer questions about recorded calls. Use ONLY the evidence items listed by the user; never use outside "
+    "knowledge. End every sentence with the id of each evidence item that supports it, in square brackets, exactly as "
+    "given, for example [Q-123] or [A-45][Q-7]. A sentence without such an id is not allowed. If the evidence does not "
+    "answer the question, reply with exactly " + INSUFFICIENT + " and nothing else.")
+
+
+class AnswerClientError(RuntimeError):
+    pass
+
+
+class ChatModel(Protocol):
+    """In-process backend: a chat (list of {"role", "content"}) -> the assistant's reply.  A ValueError means the prompt
+    does not fit the context (the caller drops evidence and retries); any other exception is reported as
+    AnswerClientError.  `model_id` names the model."""
+
+    model_id: str
+
+    def generate_text(self, messages: Sequence[Dict[str, str]], max_new_tokens: int) -> str: ...
+
+
+_llm: Optional[ChatModel] = None
+_llm_lock = threading.Lock()  # one GPU submission at a time (FastAPI runs sync endpoints on a threadpool)
+
+
+def set_llm(llm: Optional[ChatModel]) -> None:
+    global _llm
+    _llm = llm
+
+
+def get_llm() -> Optional[ChatModel]:
+    return _llm
+
+
+def llm_enabled() -> bool:
+    return bool(settings.llm_base_url.strip())
+
+
+def _is_native(url: str) -> bool:
+    return url.strip().lower().startswith("native")
+
+
+# ---- the citation gate ------------------------------------------------------------------------------------------
+_CITE = re.compile(r"\[(Q|A)-(\d+)\]")
+# a sentence ends at . ! ? followed by whitespace or the end of the text; a citation group directly behind the
+# terminator ("... text. [Q-12][A-45]") still belongs to that sentence
+_SENTENCE_END = re.compile(r"[.!?]+(?:[ \t]*\[(?:Q|A)-\d+\])*(?=\s|$)")
+_LIST_MARKER = re.compile(r"^\s*(?:[-*•]|\d+[.)])(?:\s+|$)")
+
+
+def _normal_id(letter: str, digits: str) -> str:
+    return f"{letter}-{int(digits)}"
+
+
+def split_sentences(text: str) -> List[str]:
+    """The sentences of an answer: per line (blank lines and bare list markers are none), cut behind . ! ? when
+    whitespace or the end follows, a directly following citation group kept with the sentence before it."""
+    out: List[str] = []
+    for line in text.splitlines():
+        line = _LIST_MARKER.sub("", line, count=1).strip()
+        pos = 0
+        for m in _SENTENCE_END.finditer(line):
+            out.append(line[pos:m.end()].strip())
+            pos = m.end()
+        out.append(line[pos:].strip())
+    # what holds no word outside its citations (an empty rest, a stray bracket) is not a sentence
+    return [s for s in out if re.search(r"\w", _CITE.sub("", s))]
+
+
+def validate_citations(text: str, evidence_ids: Sequence[str]) -> Dict[str, Any]:
+    """{"valid", "sentences", "uncited": [sentence], "unknown_ids": [id], "cited": [id in order of first use]}: a
+    sentence passes when it cites at least one id and every id it cites is in the pack."""
+    known = {str(e) for e in evidence_ids}
+    sentences = split_sentences(text or "")
+    uncited: List[str] = []
+    unknown: List[str] = []
+    cited: List[str] = []
+    for s in sentences:
+        ids = [_normal_id(a, b) for a, b in _CITE.findall(s)]
+        if not ids:
+            uncited.append(s)
+        for i in ids:
+            if i not in known:
+                if i not in unknown:
+                    unknown.append(i)
+            elif i not in cited:
+                cited.append(i)
+    # ids outside any sentence (a line of brackets alone) are checked as well
+    for a, b in _CITE.findall(text or ""):
+        i = _normal_id(a, b)
+        if i not in known and i not in unknown:
+            unknown.append(i)
+    return {"valid": bool(sentences) and not uncited and not unknown, "sentences": len(sentences), "uncited": uncited,
+            "unknown_ids": unknown, "cited": cited}
+
+
+# ---- the LLM call -----------------------------------------------------------------------------------------------
+def _post_json(url: str, headers: Dict[str, str], body: Dict[str, Any], timeout_s: float) -> Tuple[int, str]:
+    """The one place a socket is opened: (status code, response text)."""
+    import httpx  # only needed for the http path
+
+    try:
+        with httpx.Client(timeout=httpx.Timeout(timeout_s)) as client:
+            resp = client.post(url, json=body, headers=headers)
+    except httpx.HTTPError as exc:
+        raise AnswerClientError(f"LLM HTTP request failed: {exc}") from exc
+    return resp.status_code, resp.text
+
+
+def _chat_http(messages: List[Dict[str, str]], max_new_tokens: int) -> Tuple[str, str]:
+    import json
+
+    url = settings.llm_base_url.rstrip("/") + "/chat/completions"
+    headers = {"Authorization": f"Bearer {settings.llm_api_key}"} if settings.llm_api_key else {}
+    body = {"model": settings.llm_model, "messages": messages, "temperature": 0, "max_tokens": int(max_new_tokens)}
+    status, text = _post_json(url, headers, body, settings.llm_timeout_s)
+    if status != 200:
+        raise AnswerClientError(f"LLM service returned {status}: {text.strip()[:400]}")
+    try:
+        payload = json.loads(text)
+        content = payload["choices"][0]["message"]["content"]
+    except (ValueError, KeyError, IndexError, TypeError) as exc:
+        raise AnswerClientError(f"LLM response is not a chat completion: {exc}") from exc
+    if not isinstance(content, str):
+        raise AnswerClientError("LLM response holds no text")
+    return content, str(payload.get("model") or settings.llm_model)
+
+
+def _chat_native(messages: List[Dict[str, str]], max_new_tokens: int) -> Tuple[str, str]:
+    """ValueError (the prompt does not fit) passes through to the caller, which drops evidence."""
+    llm = _llm
+    if llm is None:
+        raise AnswerClientError("native LLM is not loaded (call set_llm)")
+    try:
+        with _llm_lock:
+            text = llm.generate_text(messages, max_new_tokens)
+    except (AnswerClientError, ValueError):
+        raise
+    except Exception as exc:  # noqa: BLE001 - callers rely on a single error type
+        raise AnswerClientError(f"native LLM failed: {exc}") from exc
+    if not isinstance(text, str):
+        raise AnswerClientError("native LLM returned no text")
+    return text, str(getattr(llm, "model_id", None) or settings.llm_model)
+
+
+def chat(messages: List[Dict[str, str]], max_new_tokens: Optional[int] = None) -> Tuple[str, str]:
+    """(reply, model id) from the configured LLM."""
+    if not llm_enabled():
+        raise AnswerClientError("LLM_BASE_URL is not configured")
+    budget = int(max_new_tokens or settings.llm_max_new_tokens)
+    if _is_native(settings.llm_base_url):
+        return _chat_native(messages, budget)
+    return _chat_http(messages, budget)
+
+
+# ---- /answer ----------------------------------------------------------------------------------------------------
+@dataclass
+class AnswerRequest(_retrieve.RetrieveRequest):
+    """The /retrieve request plus echo_evidence."""
+    echo_evidence: bool = False
+
+
+def _evidence_items(pack: Dict[str, Any]) -> List[Dict[str, Any]]:
+    """The pack's items in rank order: artifacts, then quotes (the order _pack fills them in)."""
+    return list(pack.get("artifacts") or []) + list(pack.get("quotes") or [])
+
+
+def _item_line(item: Dict[str, Any]) -> str:
+    who = item.get("speaker") or item.get("kind") or "source"
+    return f"[{item['evidence_id']}] {who}: {item.get('snippet', '')}"
+
+
+def build_messages(query: str, items: Sequence[Dict[str, Any]], turns: Sequence[Dict[str, str]] = ()
+                   ) -> List[Dict[str, str]]:
+    evidence = "\n".join(_item_line(i) for i in items)
+    user = f"Evidence:\n{evidence}\n\nQuestion: {query}\n\nAnswer from the evidence only, citing every sentence."
+    return [{"role": "system", "content": SYSTEM_RULES}, {"role": "user", "content": user}, *turns]
+
+
+def _repair_message(report: Dict[str, Any], ids: Sequence[str]) -> str:
+    parts = ["Your answer failed the citation check."]
+    if report["uncited"]:
+        parts.append("These sentences cite no evidence id: " + " | ".join(report["uncited"]))
+    if report["unknown_ids"]:
+        parts.append("These ids are not in the evidence: " + ", ".join(report["unknown_ids"]))
+    if not report["sentences"]:
+        parts.append("The answer held no sentence.")
+    parts.append("Allowed ids: " + ", ".join(f"[{i}]" for i in ids) + ". Rewrite the whole answer so that every sentence "
+                 "ends with at least one allowed id, or reply with exactly " + INSUFFICIENT + ".")
+    return " ".join(parts)
+
+
+def answer_question(request: AnswerRequest, backend: Optional[_retrieve.RetrieveBackend] = None) -> Dict[str, Any]:
+    if not llm_enabled():
+        raise AnswerClientError("LLM_BASE_URL is not configured")
+    pack_request = _retrieve.RetrieveRequest(query=request.query, intent=request.intent, filters=request.filters,
+                                             budget=request.budget, return_style="evidence_pack_json", debug=request.debug,
+                                             facets=request.facets, facet_top=request.facet_top)
+    pack = _retrieve.retrieve_evidence(pack_request, backend)
+    items = _evidence_items(pack)
+    notes: Dict[str, Any] = {"evidence_items": len(items), "dropped_evidence": 0, "llm_calls": 0, "validator": None}
+    out: Dict[str, Any] = {"query_id": pack["query_id"], "answer": None, "status": STATUS_INSUFFICIENT, "citations": [],
+                           "repairs": 0, "model": None, "notes": notes}
+    if getattr(request, "echo_evidence", False):
+        out["evidence_pack"] = pack
+    if not items:
+        return out
+
+    turns: List[Dict[str, str]] = []
+    query = request.query.strip()
+
+    def call() -> str:
+        while True:
+            try:
+                text, model = chat(build_messages(query, items, turns))
+            except ValueError as exc:   # the prompt does not fit the model's context: the lowest-ranked item goes
+                if len(items) <= 1:
+                    raise AnswerClientError(f"the prompt does not fit with a single evidence item: {exc}") from exc
+                items.pop()
+                notes["dropped_evidence"] += 1
+                continue
+            notes["llm_calls"] += 1
+            out["model"] = model
+            return text
+
+    max_repairs = max(int(settings.answer_max_repairs), 0)
+    for attempt in range(max_repairs + 1):
+        text = call().strip()
+        out["repairs"] = attempt
+        if text.strip(" .\"'`*") == INSUFFICIENT:
+            out["status"] = STATUS_INSUFFICIENT
+            return out
+        ids = [i["evidence_id"] for i in items]
+        report = validate_citations(text, ids)
+        notes["validator"] = report
+        if report["valid"]:
+            by_id = {i["evidence_id"]: i for i in items}
+            out.update(answer=text, status=STATUS_OK,
+                       citations=[{"evidence_id": c, "call_id": by_id[c]["call_id"]} for c in report["cited"]])
+            return out
+        turns += [{"role": "assistant", "content": text}, {"role": "user", "content": _repair_message(report, ids)}]
+    out["status"] = STATUS_FAILED
+    return out

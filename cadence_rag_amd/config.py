@@ -3,7 +3,8 @@
 (case-insensitive, no prefix).  Plain dataclass: the reference's pydantic-settings object is
 mutated by its tests with monkeypatch.setattr(settings, ...), and so is this one.
 
-The RERANK_* knobs are the reference's Phase-4 plan (PHASED_PLAN.md:291-297), same names and spelling.
+The RERANK_* knobs are the reference's Phase-4 plan (PHASED_PLAN.md:291-297), same names and spelling; the LLM_* knobs
+its Phase-5 plan (PHASED_PLAN.md:318-326).
 
 New knob: EMBEDDINGS_BASE_URL keeps its meaning ("" disables the dense lane); the value
 "native" (or "native://...") selects the in-process MI355X encoder instead of an HTTP gateway.
@@ -54,10 +55,22 @@ class Settings:
     # at most this many chunks of one call among the lane's rows, applied over the whole table (the grouped search), so
     # that one long call cannot fill the lane while _pack keeps DEFAULT_MAX_QUOTES_PER_CALL of it.  0 = off
     dense_per_call_cap: int = 0
+    # /answer (PHASED_PLAN.md:318-326): "" = off, "native" = the in-process Qwen3Generator, http(s) = an OpenAI-compatible
+    # chat-completions service
+    llm_base_url: str = ""
+    llm_api_key: str = ""
+    llm_model: str = "Qwen/Qwen3-4B-Instruct-2507"
+    llm_timeout_s: float = 180.0
+    llm_max_new_tokens: int = 512
+    llm_max_context: int = 8192
+    llm_device: int = -1                # -1: embeddings_device
+    answer_max_repairs: int = 2         # reprompts of an answer that fails the citation check
 
     def __post_init__(self) -> None:
         if self.rerank_device < 0:
             self.rerank_device = self.embeddings_device
+        if self.llm_device < 0:
+            self.llm_device = self.embeddings_device
 
     @classmethod
     def from_env(cls) -> "Settings":

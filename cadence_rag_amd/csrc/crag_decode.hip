@@ -1,0 +1,470 @@
+// crag_decode.hip — the operators autoregressive decoding adds to the Qwen3 forward (gfx950).  C ABI: include/crag_encoder.h.
+//
+//   crag_enc_decode_attention   one new token per sequence against a KV cache: q/k-norm + RoPE of the new row, the append
+//                               of its key and value, attention over the len + 1 keys.  Three launches: prepare (norm,
+//                               rope, append), split (one workgroup per (128-key split, kv head, sequence) -> partial
+//                               (m, l, o) in fp32), combine (the splits in ascending order).
+//   crag_enc_lm_head            final RMSNorm (+ delta) of up to 8 rows, fp32 logits against every row of lm_head (the
+//                               weights streamed once through bf16 MFMA), greedy token = lowest id among the maxima,
+//                               banned ids left out.
+//
+// Nothing here depends on the number of sequences, on the slot or on a launch size chosen at run time: a split is
+// always DECODE_SPLIT keys, its keys are always walked by the same lanes in the same order, and the splits are summed
+// in ascending order, so a sequence's output bits are a function of its own data alone.  No atomics.
+
+#include <math.h>
+
+#include "../../include/crag_encoder.h"
+#include "crag_enc_common.h"
+
+namespace {
+
+struct alignas(16) Pack8 {
+    u16 v[8];
+};
+
+constexpr int DECODE_MAX_SEQS = CRAG_DECODE_MAX_SEQS;
+constexpr int DECODE_SPLIT = CRAG_DECODE_SPLIT;  // keys per workgroup of the split kernel
+constexpr int DECODE_THREADS = 256;              // 16 groups of 16 lanes: a group reads one 256-byte key / value row
+constexpr int DECODE_GROUPS = DECODE_THREADS / 16;
+constexpr int DECODE_ITERS = DECODE_SPLIT / DECODE_GROUPS;
+
+// the host-validated per-sequence data travel as kernel arguments
+struct DecodeSeqs {
+    int32_t len[DECODE_MAX_SEQS];
+    int32_t slot[DECODE_MAX_SEQS];
+};
+
+struct DecodeParams {
+    const u16 *qkv_new;   // [n_seqs, (hq + 2 hkv) * 128] raw projections
+    const u16 *qw, *kw;   // [128]
+    const float *cos_sin; // [max_pos, 64, 2]
+    u16 *k_cache;         // [n_slots][hkv][max_len][128]
+    u16 *v_cache;
+    u16 *q_rot;           // workspace: [n_seqs][hq][128] bf16
+    float *part_o;        // workspace: [n_seqs][hq][max_splits][128]
+    float *part_ml;       // workspace: [n_seqs][hq][max_splits][2]
+    u16 *out;             // [n_seqs, hq * 128]
+    int hq, hkv, max_len, max_splits;
+    float eps, scale_log2;
+    DecodeSeqs seqs;
+};
+
+__device__ __forceinline__ int64_t cache_row(const DecodeParams &p, int slot, int kvh, int pos) {
+    return (((int64_t)slot * p.hkv + kvh) * p.max_len + pos) * CRAG_HEAD_DIM;
+}
+
+// ---------------------------------------------------------------------------------------------
+// prepare: one workgroup per sequence.  Per-head RMSNorm + rotate-half RoPE with the arithmetic and the lane layout of
+// qk_norm_rope_body (crag_encoder.hip): 16 lanes per head vector, 8 elements each, lane j pairs with lane j ^ 8.
+// q -> q_rot, k -> the cache row `len`, raw v -> the cache row `len`.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(DECODE_THREADS) void decode_prepare_kernel(const DecodeParams p) {
+    const int b = blockIdx.x;
+    const int pos = p.seqs.len[b], slot = p.seqs.slot[b];
+    const int heads = p.hq + p.hkv;
+    const int64_t row_stride = (int64_t)(p.hq + 2 * p.hkv) * CRAG_HEAD_DIM;
+    const int g = threadIdx.x >> 4;
+    const int sub = threadIdx.x & 15;
+    const bool first_half = sub < 8;
+    const Pack8 wq8 = *reinterpret_cast<const Pack8 *>(p.qw + sub * 8);
+    const Pack8 wk8 = *reinterpret_cast<const Pack8 *>(p.kw + sub * 8);
+    const float *cs = p.cos_sin + ((int64_t)pos * 64 + (sub & 7) * 8) * 2;
+    float c[8], sn[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {  // the model casts cos/sin to bf16
+        c[e] = bf2f(f2bf(cs[2 * e]));
+        sn[e] = bf2f(f2bf(cs[2 * e + 1]));
+    }
+    const u16 *row = p.qkv_new + b * row_stride;
+    for (int hd = g; hd < heads; hd += DECODE_GROUPS) {
+        const Pack8 a = *reinterpret_cast<const Pack8 *>(row + (int64_t)hd * CRAG_HEAD_DIM + sub * 8);
+        const Pack8 &w8 = hd < p.hq ? wq8 : wk8;
+        float v[8];
+        float ss = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            v[e] = bf2f(a.v[e]);
+            ss += v[e] * v[e];
+        }
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o);  // 16-lane group
+        const float rstd = rsqrtf(ss / (float)CRAG_HEAD_DIM + p.eps);
+        float n[8], partner[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) n[e] = bf2f(f2bf(bf2f(w8.v[e]) * bf2f(f2bf(v[e] * rstd))));
+#pragma unroll
+        for (int e = 0; e < 8; ++e) partner[e] = __shfl_xor(n[e], 8);  // rotate_half: element i <-> i + 64
+        Pack8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float rot = first_half ? -partner[e] : partner[e];
+            o.v[e] = f2bf(n[e] * c[e] + rot * sn[e]);
+        }
+        u16 *dst = hd < p.hq ? p.q_rot + ((int64_t)b * p.hq + hd) * CRAG_HEAD_DIM
+                             : p.k_cache + cache_row(p, slot, hd - p.hq, pos);
+        *reinterpret_cast<Pack8 *>(dst + sub * 8) = o;
+    }
+    for (int i = threadIdx.x; i < p.hkv * 16; i += DECODE_THREADS) {
+        const int kvh = i >> 4, ch = i & 15;
+        *reinterpret_cast<Pack8 *>(p.v_cache + cache_row(p, slot, kvh, pos) + ch * 8) =
+            *reinterpret_cast<const Pack8 *>(row + (int64_t)(heads + kvh) * CRAG_HEAD_DIM + ch * 8);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// split: workgroup (split s, kv head, sequence) over the keys [128 s, min(128 s + 128, len + 1)).  A 16-lane group
+// reads one key row (16 bytes per lane) and every load serves the G query heads of the kv head.  Scores and weights
+// pass through LDS in fp32; the 16 groups' partial outputs are summed in group order.
+// ---------------------------------------------------------------------------------------------
+template <int G>
+__global__ __launch_bounds__(DECODE_THREADS) void decode_split_kernel(const DecodeParams p) {
+    __shared__ float sc[G][DECODE_SPLIT];                       // raw dot products, then the weights
+    __shared__ float red[DECODE_GROUPS][G][CRAG_HEAD_DIM];      // 32 KiB at G = 4
+    __shared__ float ml[G][2];
+    const int s = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
+    const int n_keys = p.seqs.len[b] + 1;   // the prepare launch appended the new token's own key
+    const int k0 = s * DECODE_SPLIT;
+    if (k0 >= n_keys) return;               // (uniform)
+    const int slot = p.seqs.slot[b];
+    const int grp = threadIdx.x >> 4, sub = threadIdx.x & 15;
+    const u16 *kc = p.k_cache + cache_row(p, slot, kvh, 0);
+    const u16 *vc = p.v_cache + cache_row(p, slot, kvh, 0);
+
+    float q[G][8];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const Pack8 a = *reinterpret_cast<const Pack8 *>(p.q_rot + ((int64_t)b * p.hq + kvh * G + g) * CRAG_HEAD_DIM + sub * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) q[g][e] = bf2f(a.v[e]);
+    }
+    // scores
+#pragma unroll 4
+    for (int it = 0; it < DECODE_ITERS; ++it) {
+        const int j = it * DECODE_GROUPS + grp;
+        const bool live = k0 + j < n_keys;   // positions at or beyond len + 1 are never read
+        Pack8 a;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a.v[e] = 0;
+        if (live) a = *reinterpret_cast<const Pack8 *>(kc + (int64_t)(k0 + j) * CRAG_HEAD_DIM + sub * 8);
+        float d[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            d[g] = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) d[g] += q[g][e] * bf2f(a.v[e]);
+        }
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1)
+#pragma unroll
+            for (int g = 0; g < G; ++g) d[g] += __shfl_xor(d[g], o);
+        if (sub == 0) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) sc[g][j] = live ? d[g] : -INFINITY;
+        }
+    }
+    __syncthreads();
+    // softmax of the split: wave w = query head w of the group
+    {
+        const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        if (w < G) {
+            float x[DECODE_SPLIT / 64];
+            float m = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < DECODE_SPLIT / 64; ++i) {
+                x[i] = sc[w][lane + 64 * i];
+                m = fmaxf(m, x[i]);
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+            float l = 0.f;
+#pragma unroll
+            for (int i = 0; i < DECODE_SPLIT / 64; ++i) {
+                const float pr = exp2f((x[i] - m) * p.scale_log2);   // the split holds at least one key: m is finite
+                sc[w][lane + 64 * i] = pr;
+                l += pr;
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) l += __shfl_xor(l, o);
+            if (lane == 0) {
+                ml[w][0] = m;
+                ml[w][1] = l;
+            }
+        }
+    }
+    __syncthreads();
+    // weighted values
+    float acc[G][8];
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[g][e] = 0.f;
+#pragma unroll 4
+    for (int it = 0; it < DECODE_ITERS; ++it) {
+        const int j = it * DECODE_GROUPS + grp;
+        if (k0 + j < n_keys) {
+            const Pack8 a = *reinterpret_cast<const Pack8 *>(vc + (int64_t)(k0 + j) * CRAG_HEAD_DIM + sub * 8);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const float pr = sc[g][j];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[g][e] += pr * bf2f(a.v[e]);
+            }
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) red[grp][g][sub * 8 + e] = acc[g][e];
+    __syncthreads();
+    for (int i = threadIdx.x; i < G * CRAG_HEAD_DIM; i += DECODE_THREADS) {
+        const int g = i / CRAG_HEAD_DIM, d = i % CRAG_HEAD_DIM;
+        float o = 0.f;
+#pragma unroll
+        for (int r = 0; r < DECODE_GROUPS; ++r) o += red[r][g][d];
+        const int64_t part = ((int64_t)b * p.hq + kvh * G + g) * p.max_splits + s;
+        p.part_o[part * CRAG_HEAD_DIM + d] = o;
+        if (d < 2) p.part_ml[part * 2 + d] = ml[g][d];
+    }
+}
+
+// combine: workgroup (q head, sequence), 128 threads = the 128 output elements; the splits in ascending order
+__global__ __launch_bounds__(CRAG_HEAD_DIM) void decode_combine_kernel(const DecodeParams p) {
+    const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
+    const int n_splits = p.seqs.len[b] / DECODE_SPLIT + 1;   // ceil((len + 1) / split)
+    const int64_t part0 = ((int64_t)b * p.hq + h) * p.max_splits;
+    float m = -INFINITY;
+    for (int s = 0; s < n_splits; ++s) m = fmaxf(m, p.part_ml[(part0 + s) * 2]);
+    float l = 0.f, o = 0.f;
+    for (int s = 0; s < n_splits; ++s) {
+        const float w = exp2f((p.part_ml[(part0 + s) * 2] - m) * p.scale_log2);
+        l += p.part_ml[(part0 + s) * 2 + 1] * w;
+        o += p.part_o[(part0 + s) * CRAG_HEAD_DIM + d] * w;
+    }
+    p.out[((int64_t)b * p.hq + h) * CRAG_HEAD_DIM + d] = f2bf(o / l);
+}
+
+// ---------------------------------------------------------------------------------------------
+// lm_head: a workgroup norms the n rows into LDS (rerank_head_kernel's roundings: the normed row in the model's bf16),
+// then its four waves stream LM_ROWS_PER_WG rows of lm_head in tiles of 16 rows: D[vocab row][x row] +=
+// W[vocab row][k] X[x row][k] with v_mfma_f32_16x16x32_bf16, the x rows n..15 zero.  A lane reads 32 contiguous bytes
+// of its weight row per 64-element k block (the 4 lanes of a row: one 128-byte line) and the same elements of its x
+// row from LDS; which elements meet in which MFMA does not matter to a dot product as long as both operands agree.
+// The rows live in LDS with a 16-byte pad each: n * (hidden + 8) <= CRAG_LM_HEAD_MAX_ELEMS (64 KiB less the sums).
+// ---------------------------------------------------------------------------------------------
+constexpr int LM_THREADS = 256;
+constexpr int LM_ROWS_PER_WG = 256;
+constexpr int LM_MAX_ROWS = CRAG_DECODE_MAX_SEQS;
+constexpr int LM_PAD = 8;   // elements: consecutive x rows start 4 banks apart
+
+__global__ __launch_bounds__(LM_THREADS) void lm_head_kernel(const u16 *hs, const u16 *delta, const u16 *w, const u16 *lm,
+                                                            float *logits, int n, int hidden, int64_t vocab, float eps) {
+    extern __shared__ __align__(16) unsigned char lm_smem[];
+    const int ld = hidden + LM_PAD;
+    u16 *xn = reinterpret_cast<u16 *>(lm_smem);   // [n][hidden + 8] bf16, then block_sum's four floats
+    float *sh = reinterpret_cast<float *>(lm_smem + (size_t)n * ld * sizeof(u16));
+    for (int r = 0; r < n; ++r) {
+        const u16 *x = hs + (int64_t)r * hidden;
+        const u16 *dl = delta ? delta + (int64_t)r * hidden : nullptr;
+        float ss = 0.f;
+        for (int i = threadIdx.x; i < hidden; i += LM_THREADS) {
+            const u16 s = dl ? f2bf(bf2f(x[i]) + bf2f(dl[i])) : x[i];
+            xn[r * ld + i] = s;   // (this thread's own elements: read back below without a barrier)
+            const float v = bf2f(s);
+            ss += v * v;
+        }
+        ss = block_sum(ss, sh);
+        const float rstd = rsqrtf(ss / (float)hidden + eps);
+        for (int i = threadIdx.x; i < hidden; i += LM_THREADS)
+            xn[r * ld + i] = f2bf(bf2f(w[i]) * bf2f(f2bf(bf2f(xn[r * ld + i]) * rstd)));
+    }
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r16 = lane & 15, kq = lane >> 4;
+    const int64_t v0 = (int64_t)blockIdx.x * LM_ROWS_PER_WG;
+    const int64_t v1 = v0 + LM_ROWS_PER_WG < vocab ? v0 + LM_ROWS_PER_WG : vocab;
+    const bool has_x = r16 < n;
+    const u16 *xp = xn + (has_x ? r16 : 0) * ld + kq * 16;
+    const bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int64_t t0 = v0 + wave * 16; t0 < v1; t0 += 64) {
+        const int64_t vr = t0 + r16 < v1 ? t0 + r16 : v1 - 1;   // a tile's rows past the end re-read the last row; never stored
+        const u16 *wp = lm + vr * hidden + kq * 16;
+        f32x4_t acc = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        int k0 = 0;
+        for (; k0 + 256 <= hidden; k0 += 256) {   // four k blocks: 128 bytes of the weight row per lane in flight
+            bf16x8 a[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) a[u] = ld_frag(wp + k0 + 64 * (u >> 1) + 8 * (u & 1));
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const bf16x8 b = has_x ? ld_frag(xp + k0 + 64 * (u >> 1) + 8 * (u & 1)) : zero;
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u], b, acc, 0, 0, 0);
+            }
+        }
+        for (; k0 < hidden; k0 += 64) {
+            const bf16x8 a0 = ld_frag(wp + k0), a1 = ld_frag(wp + k0 + 8);
+            const bf16x8 b0 = has_x ? ld_frag(xp + k0) : zero, b1 = has_x ? ld_frag(xp + k0 + 8) : zero;
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc, 0, 0, 0);
+        }
+        // D[row = vocab row 4 kq + r of the tile][col = x row r16]
+        if (has_x) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t v = t0 + 4 * kq + r;
+                if (v < v1) logits[(int64_t)r16 * vocab + v] = acc[r];
+            }
+        }
+    }
+}
+
+// greedy token of one row: the lowest id among the maxima of its logits, banned ids and NaNs left out; -1 when nothing
+// is left.  One workgroup per row; a thread walks its ids in ascending order, the threads are merged on (value, id).
+constexpr int ARGMAX_THREADS = 1024;
+
+__device__ __forceinline__ bool better(float v, int id, float bv, int bid) {
+    return bid < 0 || v > bv || (v == bv && id < bid);
+}
+
+__global__ __launch_bounds__(ARGMAX_THREADS) void lm_argmax_kernel(const float *logits, int64_t vocab, const int32_t *banned,
+                                                                   int n_banned, int32_t *token) {
+    __shared__ float sv[ARGMAX_THREADS / 64];
+    __shared__ int si[ARGMAX_THREADS / 64];
+    const float *row = logits + (int64_t)blockIdx.x * vocab;
+    float bv = 0.f;
+    int bid = -1;
+    for (int64_t i = threadIdx.x; i < vocab; i += ARGMAX_THREADS) {
+        const float v = row[i];
+        if (v != v || !(bid < 0 || v > bv)) continue;
+        bool ban = false;
+        for (int k = 0; k < n_banned; ++k) ban |= banned[k] == (int32_t)i;
+        if (!ban) {
+            bv = v;
+            bid = (int)i;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o);
+        const int oi = __shfl_xor(bid, o);
+        if (oi >= 0 && better(ov, oi, bv, bid)) {
+            bv = ov;
+            bid = oi;
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        sv[threadIdx.x >> 6] = bv;
+        si[threadIdx.x >> 6] = bid;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < ARGMAX_THREADS / 64; ++k)
+            if (si[k] >= 0 && better(sv[k], si[k], bv, bid)) {
+                bv = sv[k];
+                bid = si[k];
+            }
+        token[blockIdx.x] = bid;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t crag_enc_decode_workspace_bytes(int n_seqs, int hq, int max_len) {
+    if (n_seqs <= 0 || n_seqs > DECODE_MAX_SEQS || hq <= 0 || max_len <= 0) return 0;
+    const int64_t splits = ((int64_t)max_len + DECODE_SPLIT - 1) / DECODE_SPLIT;
+    const int64_t heads = (int64_t)n_seqs * hq;
+    // q_rot (bf16, rounded up to 16 bytes per head anyway) + partial o + partial (m, l)
+    return heads * CRAG_HEAD_DIM * 2 + heads * splits * CRAG_HEAD_DIM * 4 + heads * splits * 2 * 4;
+}
+
+int crag_enc_decode_attention(const uint16_t *qkv_new, const uint16_t *q_norm_w, const uint16_t *k_norm_w,
+                              const float *cos_sin, int max_pos, uint16_t *k_cache, uint16_t *v_cache, int n_slots,
+                              int max_len, const int32_t *h_slots, const int32_t *h_cache_len, int n_seqs, int hq, int hkv,
+                              float eps, float scale, void *workspace, int64_t workspace_bytes, uint16_t *out,
+                              void *stream) {
+    if (!qkv_new || !q_norm_w || !k_norm_w || !cos_sin || !k_cache || !v_cache || !h_slots || !h_cache_len || !workspace ||
+        !out)
+        return efail("decode_attention: NULL pointer");
+    if (n_seqs < 1 || n_seqs > DECODE_MAX_SEQS)
+        return efail("decode_attention: n_seqs must be in 1..%d (got %d)", DECODE_MAX_SEQS, n_seqs);
+    if (hq <= 0 || hkv <= 0 || hq % hkv || (hq / hkv != 2 && hq / hkv != 4))
+        return efail("decode_attention: hq / hkv must be 2 or 4 (got %d / %d)", hq, hkv);
+    if (n_slots <= 0 || max_len <= 0 || max_pos <= 0) return efail("decode_attention: n_slots, max_len and max_pos must be positive");
+    if (((uintptr_t)qkv_new | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)workspace | (uintptr_t)q_norm_w |
+         (uintptr_t)k_norm_w) & 15)
+        return efail("decode_attention: qkv_new, the norm weights, the cache and the workspace must be 16-byte aligned");
+    DecodeParams p;
+    for (int b = 0; b < n_seqs; ++b) {
+        const int len = h_cache_len[b], slot = h_slots[b];
+        if (len < 0 || len >= max_len)
+            return efail("decode_attention: cache length %d of sequence %d is outside 0..max_len - 1 = %d", len, b, max_len - 1);
+        if (len >= max_pos) return efail("decode_attention: position %d of sequence %d is beyond the RoPE table (%d rows)", len, b, max_pos);
+        if (slot < 0 || slot >= n_slots) return efail("decode_attention: slot %d of sequence %d is outside 0..%d", slot, b, n_slots - 1);
+        for (int a = 0; a < b; ++a)
+            if (h_slots[a] == slot) return efail("decode_attention: slot %d is named twice in one call", slot);
+        p.seqs.len[b] = len;
+        p.seqs.slot[b] = slot;
+    }
+    for (int b = n_seqs; b < DECODE_MAX_SEQS; ++b) p.seqs.len[b] = p.seqs.slot[b] = 0;
+    const int64_t need = crag_enc_decode_workspace_bytes(n_seqs, hq, max_len);
+    if (workspace_bytes < need)
+        return fail(CRAG_E2BIG, "decode_attention: the workspace holds %lld bytes, %lld are needed", (long long)workspace_bytes,
+                    (long long)need);
+    const int max_splits = (max_len + DECODE_SPLIT - 1) / DECODE_SPLIT;
+    const int64_t heads = (int64_t)n_seqs * hq;
+    p.qkv_new = qkv_new;
+    p.qw = q_norm_w;
+    p.kw = k_norm_w;
+    p.cos_sin = cos_sin;
+    p.k_cache = k_cache;
+    p.v_cache = v_cache;
+    p.q_rot = (u16 *)workspace;
+    p.part_o = (float *)((char *)workspace + heads * CRAG_HEAD_DIM * 2);
+    p.part_ml = p.part_o + heads * max_splits * CRAG_HEAD_DIM;
+    p.out = out;
+    p.hq = hq;
+    p.hkv = hkv;
+    p.max_len = max_len;
+    p.max_splits = max_splits;
+    p.eps = eps;
+    p.scale_log2 = scale * 1.4426950408889634f;
+    int longest = 0;
+    for (int b = 0; b < n_seqs; ++b) longest = p.seqs.len[b] > longest ? p.seqs.len[b] : longest;
+    const int splits = longest / DECODE_SPLIT + 1;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(decode_prepare_kernel, dim3((unsigned)n_seqs), dim3(DECODE_THREADS), 0, st, p);
+    const dim3 grid((unsigned)splits, (unsigned)hkv, (unsigned)n_seqs);
+    if (hq / hkv == 2)
+        hipLaunchKernelGGL(decode_split_kernel<2>, grid, dim3(DECODE_THREADS), 0, st, p);
+    else
+        hipLaunchKernelGGL(decode_split_kernel<4>, grid, dim3(DECODE_THREADS), 0, st, p);
+    hipLaunchKernelGGL(decode_combine_kernel, dim3((unsigned)hq, (unsigned)n_seqs), dim3(CRAG_HEAD_DIM), 0, st, p);
+    return hip_ok("decode_attention");
+}
+
+int crag_enc_lm_head(const uint16_t *hidden_states, const uint16_t *delta, const uint16_t *final_norm_w,
+                     const uint16_t *lm_head, float *logits, int32_t *token, const int32_t *banned, int n_banned,
+                     int n_rows, int hidden, int64_t vocab, float eps, void *stream) {
+    if (!hidden_states || !final_norm_w || !lm_head || !logits || !token) return efail("lm_head: NULL pointer");
+    if (n_rows < 1 || n_rows > LM_MAX_ROWS) return efail("lm_head: n_rows must be in 1..%d (got %d)", LM_MAX_ROWS, n_rows);
+    if (hidden <= 0 || (hidden & 63)) return efail("lm_head: hidden must be a positive multiple of 64 (got %d)", hidden);
+    if ((int64_t)n_rows * (hidden + LM_PAD) > CRAG_LM_HEAD_MAX_ELEMS)
+        return efail("lm_head: n_rows * (hidden + 8) must not exceed %d (got %d * %d)", CRAG_LM_HEAD_MAX_ELEMS, n_rows,
+                     hidden + LM_PAD);
+    if (vocab <= 0 || vocab > 0x7fffffff) return efail("lm_head: vocab must be in 1..2^31 - 1");
+    if (n_banned < 0 || n_banned > CRAG_LM_HEAD_MAX_BANNED || (n_banned > 0 && !banned))
+        return efail("lm_head: n_banned must be in 0..%d, with a list when it is positive", CRAG_LM_HEAD_MAX_BANNED);
+    if (((uintptr_t)lm_head | (uintptr_t)hidden_states) & 15) return efail("lm_head: lm_head and hidden_states must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned grid = (unsigned)((vocab + LM_ROWS_PER_WG - 1) / LM_ROWS_PER_WG);
+    const size_t smem = (size_t)n_rows * (hidden + LM_PAD) * sizeof(u16) + (LM_THREADS / 64) * sizeof(float);
+    hipLaunchKernelGGL(lm_head_kernel, dim3(grid), dim3(LM_THREADS), smem, st, hidden_states, delta, final_norm_w, lm_head,
+                       logits, n_rows, hidden, vocab, eps);
+    hipLaunchKernelGGL(lm_argmax_kernel, dim3((unsigned)n_rows), dim3(ARGMAX_THREADS), 0, st, logits, vocab, banned, n_banned,
+                       token);
+    return hip_ok("lm_head");
+}
+
+}  // extern "C"

@@ -1,0 +1,340 @@
+"""Greedy autoregressive decoding with a KV cache on MI355X: the Qwen3 decoder (Qwen3Encoder's weights and layer
+kernels) with a full-vocabulary head -- the in-process LLM behind /answer (cadence_rag_amd.answer).
+
+  prefill(token_lists)  the general packed forward over the prompts (library GEMMs, qk_rope_vt, the causal flash
+                        attention); every layer's normed + rotated keys and raw values are copied into the cache.
+  step(tokens)          one new token per live sequence: per layer qkv, crag_enc_decode_attention (q/k-norm + RoPE of
+                        the new row, append, attention over the cache), o, MLP; then crag_enc_lm_head (final norm, fp32
+                        logits over the whole vocabulary, greedy token).
+  generate(...)         prefill + steps until a stop id or the token budget.  Greedy only.
+
+The cache layout ([layer][slot][kv head][max_len][128] bf16, keys and values apart) sits behind KvCache.keys / .values.
+At most MAX_SEQS = 8 sequences decode at a time.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import ops
+from .qwen3 import QKV_ROW_CHUNK, PackedBatch, Qwen3Config, Qwen3Encoder
+
+MAX_SEQS = 8
+CHAT_SYSTEM = "<|im_start|>system\n{system}<|im_end|>\n"
+CHAT_USER = "<|im_start|>user\n{user}<|im_end|>\n"
+CHAT_ASSISTANT = "<|im_start|>assistant\n{assistant}<|im_end|>\n"
+CHAT_GENERATE = "<|im_start|>assistant\n<think>\n\n</think>\n\n"
+
+
+class PromptTooLong(ValueError):
+    """A prompt does not leave room for the requested new tokens inside the context window."""
+
+
+class KvCache:
+    """Keys (normed, rotated) and raw values of every layer for n_slots sequences of up to max_len tokens.  `lens[slot]`
+    (host) is the number of tokens a slot holds."""
+
+    def __init__(self, n_layers: int, n_slots: int, hkv: int, max_len: int, device) -> None:
+        shape = (n_layers, n_slots, hkv, max_len, 128)
+        self.k = torch.zeros(shape, dtype=torch.bfloat16, device=device)
+        self.v = torch.zeros(shape, dtype=torch.bfloat16, device=device)
+        self.n_slots, self.max_len = int(n_slots), int(max_len)
+        self.lens: List[int] = [0] * n_slots
+
+    def layer(self, i: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The two [n_slots, hkv, max_len, 128] arrays crag_enc_decode_attention takes."""
+        return self.k[i], self.v[i]
+
+    def keys(self, layer: int, slot: int) -> torch.Tensor:
+        """[len, hkv, 128]: the cached keys of a slot, token-major."""
+        return self.k[layer, slot, :, :self.lens[slot]].transpose(0, 1)
+
+    def values(self, layer: int, slot: int) -> torch.Tensor:
+        return self.v[layer, slot, :, :self.lens[slot]].transpose(0, 1)
+
+    def append_prefill(self, layer: int, slot: int, k_rows: torch.Tensor, v_rows: torch.Tensor) -> None:
+        """k_rows / v_rows [n, hkv, 128]: a prompt's keys and values as crag_enc_qk_rope_vt left them in qkv -> rows
+        0..n-1 of the slot (lens is set by the caller once every layer is in)."""
+        n = k_rows.shape[0]
+        self.k[layer, slot, :, :n].copy_(k_rows.transpose(0, 1))
+        self.v[layer, slot, :, :n].copy_(v_rows.transpose(0, 1))
+
+
+class Qwen3Generator:
+    """generate(prompts, max_new_tokens, stop_ids) -> new token ids of every prompt, on one GPU and one stream."""
+
+    def __init__(self, encoder: Qwen3Encoder, lm_head: torch.Tensor, tokenizer=None, *, max_context: Optional[int] = None,
+                 max_seqs: int = MAX_SEQS, model_id: Optional[str] = None) -> None:
+        c = encoder.cfg
+        if c.head_dim != 128 or c.num_heads % c.num_kv_heads or c.num_heads // c.num_kv_heads not in (2, 4):
+            raise ValueError("the decode attention kernel is built for head_dim 128 and 2 or 4 query heads per kv head")
+        if tuple(lm_head.shape) != (c.vocab_size, c.hidden_size):
+            raise ValueError(f"lm_head must be [{c.vocab_size}, {c.hidden_size}]")
+        if not 1 <= int(max_seqs) <= MAX_SEQS:
+            raise ValueError(f"max_seqs must be in 1..{MAX_SEQS}")
+        self.encoder = encoder
+        self.cfg = c
+        self.device = encoder.device
+        self.max_context = int(max_context or c.max_length)
+        if self.max_context > c.max_length:
+            raise ValueError(f"max_context {self.max_context} exceeds the encoder's RoPE table ({c.max_length} positions)")
+        # a tied model passes embed_tokens itself: the same storage, no copy
+        self.lm_head = lm_head if (lm_head.device == self.device and lm_head.dtype == torch.bfloat16
+                                   and lm_head.is_contiguous()) else \
+            lm_head.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        self.tokenizer = tokenizer
+        self.model_id = model_id or c.model_id
+        self.max_seqs = int(max_seqs)
+        self.cache = KvCache(c.num_layers, self.max_seqs, c.num_kv_heads, self.max_context, self.device)
+        self._workspace = ops.decode_workspace(self.max_seqs, c.num_heads, self.max_context, self.device)
+        self.live: List[int] = []          # slots of the sequences the next step() advances
+        self.force_library = False         # tests: keep the 4B widths off the small_gemm path
+        self.last_path = ""
+
+    # -- construction ---------------------------------------------------------------------------------------------
+    @classmethod
+    def from_pretrained(cls, path: str, device: Optional[torch.device] = None, max_context: int = 8192, *,
+                        max_seqs: int = MAX_SEQS, model_id: Optional[str] = None) -> "Qwen3Generator":
+        """A local *ForCausalLM checkpoint directory (config.json, *.safetensors, tokenizer files; nothing is fetched),
+        lm_head tied to embed_tokens or not."""
+        import json
+        from pathlib import Path
+
+        from safetensors.torch import load_file
+        from transformers import AutoTokenizer
+        root = Path(path)
+        hf = json.loads((root / "config.json").read_text())
+        rope = hf.get("rope_theta") or (hf.get("rope_parameters") or {}).get("rope_theta", 1_000_000.0)
+        cfg = Qwen3Config(hidden_size=hf["hidden_size"], num_layers=hf["num_hidden_layers"],
+                          num_heads=hf["num_attention_heads"], num_kv_heads=hf["num_key_value_heads"],
+                          head_dim=hf.get("head_dim", 128), intermediate_size=hf["intermediate_size"],
+                          vocab_size=hf["vocab_size"], rms_norm_eps=hf.get("rms_norm_eps", 1e-6), rope_theta=rope,
+                          max_length=int(max_context), out_dim=min(1024, hf["hidden_size"]), pooling="last",
+                          model_id=model_id or hf.get("_name_or_path") or str(root.name))
+        tokenizer = AutoTokenizer.from_pretrained(str(root), local_files_only=True)
+        files = sorted(root.glob("*.safetensors"))
+        if not files:
+            raise FileNotFoundError(f"no *.safetensors under {root}")
+        sd: Dict[str, torch.Tensor] = {}
+        for f in files:
+            sd.update(load_file(str(f)))
+        prefix = "model." if any(k.startswith("model.") for k in sd) else ""
+        tied = hf.get("tie_word_embeddings", False) or "lm_head.weight" not in sd
+        if tied and not hf.get("tie_word_embeddings", False):
+            raise ValueError(f"{root}: no lm_head.weight and the config does not tie it to embed_tokens")
+        head = None if tied else sd.pop("lm_head.weight")
+        sd.pop("lm_head.weight", None)
+        enc = Qwen3Encoder.from_state_dict(cfg, sd, device, prefix=prefix)
+        enc.tokenizer = tokenizer
+        return cls(enc, enc.embed if tied else head, tokenizer, max_context=max_context, max_seqs=max_seqs,
+                   model_id=cfg.model_id)
+
+    # -- prompts --------------------------------------------------------------------------------------------------
+    def chat_ids(self, messages: Sequence[Dict[str, str]]) -> List[int]:
+        """Token ids of a chat (system / user / assistant turns) ending in the assistant's opening: the tokenizer's own
+        chat template when it has one, otherwise the ChatML text the reranker writes by hand."""
+        tok = self._tokenizer()
+        if getattr(tok, "chat_template", None):
+            text = tok.apply_chat_template(list(messages), tokenize=False, add_generation_prompt=True)
+        else:
+            forms = {"system": CHAT_SYSTEM, "user": CHAT_USER, "assistant": CHAT_ASSISTANT}
+            text = "".join(forms[m["role"]].format(**{m["role"]: m["content"]}) for m in messages) + CHAT_GENERATE
+        return tok.encode(text, add_special_tokens=False)
+
+    def stop_ids(self) -> List[int]:
+        tok = self._tokenizer()
+        ids = []
+        vocab = tok.get_vocab()
+        if "<|im_end|>" in vocab:
+            ids.append(int(vocab["<|im_end|>"]))
+        if getattr(tok, "eos_token_id", None) is not None:
+            ids.append(int(tok.eos_token_id))
+        return sorted(set(ids))
+
+    def _tokenizer(self):
+        if self.tokenizer is None:
+            raise RuntimeError("no tokenizer loaded (Qwen3Generator.from_pretrained, or pass one)")
+        return self.tokenizer
+
+    # -- forward --------------------------------------------------------------------------------------------------
+    def _head(self, hidden: torch.Tensor, delta: Optional[torch.Tensor], banned=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        n = hidden.shape[0]
+        logits = torch.empty(n, self.cfg.vocab_size, dtype=torch.float32, device=self.device)
+        token = torch.empty(n, dtype=torch.int32, device=self.device)
+        ops.lm_head(hidden, self.encoder.final_norm, self.lm_head, logits, token, self.cfg.rms_norm_eps, delta=delta,
+                    banned=banned)
+        return logits, token
+
+    @torch.no_grad()
+    def prefill(self, token_lists: Sequence[Sequence[int]], slots: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """Fills slot slots[b] (default b) with prompt b and makes these the live sequences.  Returns the last-token
+        logits [n, vocab] fp32 on the device; .last_tokens holds their greedy tokens (int32 [n], device)."""
+        c, enc, dev, bf = self.cfg, self.encoder, self.device, torch.bfloat16
+        n = len(token_lists)
+        slots = list(range(n)) if slots is None else [int(s) for s in slots]
+        if not 1 <= n <= self.max_seqs or len(slots) != n or len(set(slots)) != n or \
+                any(not 0 <= s < self.max_seqs for s in slots):
+            raise ValueError(f"prefill takes 1..{self.max_seqs} prompts, each in a slot of its own")
+        lens = [len(tl) for tl in token_lists]
+        if min(lens) <= 0:
+            raise ValueError("every prompt needs at least one token")
+        if max(lens) >= self.max_context:
+            raise PromptTooLong(f"a prompt of {max(lens)} tokens leaves no room in a context of {self.max_context}")
+        batch = PackedBatch.build(lens, dev)
+        ids = torch.from_numpy(np.concatenate([np.asarray(tl, dtype=np.int32) for tl in token_lists])).to(dev)
+        t = batch.n_tokens
+        x = torch.empty(t, c.hidden_size, dtype=bf, device=dev)
+        ops.embed_gather(ids, enc.embed, x)
+        resid = torch.empty_like(x)
+        normed = torch.empty_like(x)
+        width = c.q_size + 2 * c.kv_size
+        qkv_buf = torch.zeros(t + 32, width, dtype=bf, device=dev)  # attention reads up to 31 rows past T
+        qkv = qkv_buf[:t]
+        vt = torch.empty(c.num_kv_heads, c.head_dim, batch.t_pad, dtype=bf, device=dev)
+        attn = torch.empty(t, c.q_size, dtype=bf, device=dev)
+        act = torch.empty(t, c.intermediate_size, dtype=bf, device=dev)
+        scale = 1.0 / math.sqrt(c.head_dim)
+        starts = np.concatenate([[0], np.cumsum(lens)])
+        delta: Optional[torch.Tensor] = None
+        for i, L in enumerate(enc.layers):
+            if i == 0:
+                ops.rmsnorm(x, L["ln1"], normed, c.rms_norm_eps, residual_in=None, residual_out=None)
+                resid.copy_(x)
+            else:
+                ops.rmsnorm(delta, L["ln1"], normed, c.rms_norm_eps, residual_in=resid, residual_out=resid)
+            for lo in range(0, t, QKV_ROW_CHUNK):
+                hi = min(t, lo + QKV_ROW_CHUNK)
+                torch.matmul(normed[lo:hi], L["qkv"].t(), out=qkv[lo:hi])
+            ops.qk_rope_vt(qkv_buf, L["q_norm"], L["k_norm"], enc._cos_sin, batch.positions, c.num_heads, c.num_kv_heads,
+                           c.rms_norm_eps, vt, batch.tok_of_pad)
+            for b, slot in enumerate(slots):   # KV append: the normed + rotated keys and the raw values of the prompt
+                rows = qkv[int(starts[b]):int(starts[b + 1])]
+                self.cache.append_prefill(i, slot, rows[:, c.q_size:c.q_size + c.kv_size].view(-1, c.num_kv_heads, 128),
+                                          rows[:, c.q_size + c.kv_size:].view(-1, c.num_kv_heads, 128))
+            ops.attention(qkv_buf, vt, attn, batch.cu, batch.cu_pad, batch.blk_seq, batch.blk_q0, c.num_heads,
+                          c.num_kv_heads, scale)
+            delta = F.linear(attn, L["o"])
+            ops.rmsnorm(delta, L["ln2"], normed, c.rms_norm_eps, residual_in=resid, residual_out=resid)
+            ops.swiglu(F.linear(normed, L["gate_up"]), act)
+            delta = F.linear(act, L["down"])
+        for slot, m in zip(slots, lens):
+            self.cache.lens[slot] = m
+        self.live = list(slots)
+        logits, self.last_tokens = self._head(resid.index_select(0, batch.last_tok),
+                                              delta.index_select(0, batch.last_tok))
+        return logits
+
+    @torch.no_grad()
+    def step(self, tokens: Sequence[int], slots: Optional[Sequence[int]] = None, banned: Optional[torch.Tensor] = None
+             ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One new token per sequence (slots: default the live ones, in order).  Returns (next tokens int32 [n], logits
+        [n, vocab] fp32), both on the device; the cache of every slot grows by one."""
+        c, enc, dev, bf = self.cfg, self.encoder, self.device, torch.bfloat16
+        slots = list(self.live) if slots is None else [int(s) for s in slots]
+        n = len(slots)
+        if n == 0 or len(tokens) != n:
+            raise ValueError("step needs one token per live sequence")
+        lens = [self.cache.lens[s] for s in slots]
+        if max(lens) >= self.max_context:
+            raise PromptTooLong(f"a sequence of {max(lens)} tokens has filled the context of {self.max_context}")
+        ids = torch.tensor([int(t) for t in tokens], dtype=torch.int32).to(dev)
+        scale = 1.0 / math.sqrt(c.head_dim)
+        width = c.q_size + 2 * c.kv_size
+        skinny = None if self.force_library else enc._skinny_weights()
+        if skinny is not None and not enc._skinny_v1:
+            # the five-launch layer of Qwen3Encoder._forward_small_rows at 16 padded rows, the decode attention in the middle
+            self.last_path = "small_gemm"
+            bufs = self.__dict__.get("_small_bufs")
+            if bufs is None:
+                # allocated once and zeroed once: the kernels store the n live rows only, so the padding rows hold zeros
+                # or the finite rows of an earlier, larger step -- and a row of a GEMM depends on no other row
+                z = lambda cols: torch.zeros(16, cols, dtype=bf, device=dev)   # noqa: E731
+                bufs = self._small_bufs = tuple(z(cols) for cols in (c.hidden_size,) * 5 + (width, c.q_size,
+                                                                                            c.intermediate_size))
+            res_a, res_b, delta_o, delta_d, delta0, qkv, attn, act = bufs
+            ops.embed_gather(ids, enc.embed, res_a[:n])
+            for i, L in enumerate(enc.layers):
+                W = skinny[i]
+                kc, vc = self.cache.layer(i)
+                ops.small_gemm(res_a, W["qkv"], qkv, n, width, 12, delta=delta0 if i == 0 else delta_d, norm_w=L["ln1"],
+                               res_out=res_b, eps=c.rms_norm_eps)
+                ops.decode_attention(qkv, L["q_norm"], L["k_norm"], enc._cos_sin, kc, vc, slots, lens, attn, c.num_heads,
+                                     c.num_kv_heads, c.rms_norm_eps, scale, self._workspace)
+                ops.small_gemm(attn, W["o"], delta_o, n, c.hidden_size, 10)
+                ops.small_gemm(res_b, W["gate_up"], act, n, 2 * c.intermediate_size, 16, swiglu=True, delta=delta_o,
+                               norm_w=L["ln2"], res_out=res_a, eps=c.rms_norm_eps)
+                ops.small_gemm(act, W["down"], delta_d, n, c.hidden_size, 10)
+            hidden, delta = res_a[:n], delta_d[:n]
+        else:
+            self.last_path = "library"
+            x = torch.empty(n, c.hidden_size, dtype=bf, device=dev)
+            ops.embed_gather(ids, enc.embed, x)
+            resid = x.clone()
+            normed = torch.empty_like(x)
+            attn = torch.empty(n, c.q_size, dtype=bf, device=dev)
+            act = torch.empty(n, c.intermediate_size, dtype=bf, device=dev)
+            delta = None
+            for i, L in enumerate(enc.layers):
+                kc, vc = self.cache.layer(i)
+                if i == 0:
+                    ops.rmsnorm(x, L["ln1"], normed, c.rms_norm_eps, residual_in=None, residual_out=None)
+                else:
+                    ops.rmsnorm(delta, L["ln1"], normed, c.rms_norm_eps, residual_in=resid, residual_out=resid)
+                qkv = F.linear(normed, L["qkv"])
+                ops.decode_attention(qkv, L["q_norm"], L["k_norm"], enc._cos_sin, kc, vc, slots, lens, attn, c.num_heads,
+                                     c.num_kv_heads, c.rms_norm_eps, scale, self._workspace)
+                delta = F.linear(attn, L["o"])
+                ops.rmsnorm(delta, L["ln2"], normed, c.rms_norm_eps, residual_in=resid, residual_out=resid)
+                ops.swiglu(F.linear(normed, L["gate_up"]), act)
+                delta = F.linear(act, L["down"])
+            hidden = resid
+        for s in slots:
+            self.cache.lens[s] += 1
+        logits, token = self._head(hidden, delta, banned)
+        return token, logits
+
+    @torch.no_grad()
+    def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_ids: Sequence[int] = ()
+                 ) -> List[List[int]]:
+        """Greedy continuation of every prompt (token ids): at most max_new_tokens ids each, ending before the first
+        stop id.  A prompt longer than max_context - max_new_tokens raises PromptTooLong (a ValueError): the caller
+        shortens its prompt, nothing is truncated here."""
+        max_new_tokens = int(max_new_tokens)
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be positive")
+        room = self.max_context - max_new_tokens
+        longest = max(len(p) for p in prompts)
+        if longest > room:
+            raise PromptTooLong(f"a prompt of {longest} tokens does not fit: max_context {self.max_context} - "
+                                f"max_new_tokens {max_new_tokens} leaves {room}")
+        stop = {int(s) for s in stop_ids}
+        self.prefill(prompts)
+        out: List[List[int]] = [[] for _ in prompts]
+        nxt = self.last_tokens.tolist()
+        live = list(range(len(prompts)))          # slot b holds prompt b
+        while live:
+            feed, keep = [], []
+            for b, tok in zip(live, nxt):
+                if tok in stop or tok < 0:
+                    continue
+                out[b].append(int(tok))
+                if len(out[b]) < max_new_tokens:
+                    keep.append(b)
+                    feed.append(int(tok))
+            live = keep
+            if not live:
+                break
+            self.live = list(live)
+            token, _ = self.step(feed)
+            nxt = token.tolist()
+        self.live = []
+        return out
+
+    def generate_text(self, messages: Sequence[Dict[str, str]], max_new_tokens: int) -> str:
+        """One chat -> the assistant's reply as text."""
+        ids = self.generate([self.chat_ids(messages)], max_new_tokens, self.stop_ids())[0]
+        return self._tokenizer().decode(ids, skip_special_tokens=True)

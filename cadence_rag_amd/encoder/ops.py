@@ -307,3 +307,60 @@ def rerank_head(hidden_states, final_norm_w, rows, lm_rows, out, eps: float, del
                                                       _p(lm_rows), _p(out), rows.numel(), hidden, float(eps), _stream()),
                   "crag_enc_rerank_head")
     return out
+
+
+# -- autoregressive decoding (csrc/crag_decode.hip) ------------------------------------------------------------------
+def decode_workspace(n_seqs: int, hq: int, max_len: int, device) -> torch.Tensor:
+    """Device scratch of decode_attention for up to n_seqs sequences over caches of max_len rows (uint8)."""
+    need = int(_native.load().crag_enc_decode_workspace_bytes(int(n_seqs), int(hq), int(max_len)))
+    if need <= 0:
+        raise ValueError(f"no decode workspace for n_seqs={n_seqs}, hq={hq}, max_len={max_len}")
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def decode_attention(qkv_new, q_w, k_w, cos_sin, k_cache, v_cache, slots, cache_len, out, hq: int, hkv: int, eps: float,
+                     scale: float, workspace):
+    """One new token per sequence against ONE layer's cache (crag_enc_decode_attention).  qkv_new [n, (hq + 2 hkv) * 128]
+    raw projections; k_cache / v_cache [n_slots, hkv, max_len, 128] bf16; slots / cache_len: HOST ints per sequence (the
+    slot, and how many tokens it holds = the new token's position).  The new key and value are appended at position
+    cache_len of the slot; out [n, hq * 128]."""
+    _req(qkv_new, torch.bfloat16, "qkv_new"); _req(cos_sin, torch.float32, "cos_sin"); _req(out, torch.bfloat16, "out")
+    _req(k_cache, torch.bfloat16, "k_cache"); _req(v_cache, torch.bfloat16, "v_cache")
+    _req(q_w, torch.bfloat16, "q_w"); _req(k_w, torch.bfloat16, "k_w"); _req(workspace, torch.uint8, "workspace")
+    n = len(slots)
+    if len(cache_len) != n:
+        raise ValueError("slots and cache_len need one entry per sequence")
+    n_slots, kv_heads, max_len, dim = k_cache.shape
+    if v_cache.shape != k_cache.shape or kv_heads != hkv or dim != 128:
+        raise ValueError("k_cache and v_cache must both be [n_slots, hkv, max_len, 128]")
+    if n <= _native.CRAG_DECODE_MAX_SEQS and (qkv_new.shape[0] < n or out.shape[0] < n
+                                              or qkv_new.shape[1] != (hq + 2 * hkv) * 128 or out.shape[1] != hq * 128):
+        raise ValueError("qkv_new must be [n, (hq + 2 hkv) * 128] and out [n, hq * 128]")
+    h_slots = (ctypes.c_int32 * max(n, 1))(*[int(s) for s in slots])
+    h_lens = (ctypes.c_int32 * max(n, 1))(*[int(x) for x in cache_len])
+    _native.check(_native.load().crag_enc_decode_attention(
+        _p(qkv_new), _p(q_w), _p(k_w), _p(cos_sin), int(cos_sin.shape[0]), _p(k_cache), _p(v_cache), int(n_slots),
+        int(max_len), h_slots, h_lens, n, int(hq), int(hkv), float(eps), float(scale), _p(workspace),
+        int(workspace.numel()), _p(out), _stream()), "crag_enc_decode_attention")
+    return out
+
+
+def lm_head(hidden_states, final_norm_w, lm, logits, token, eps: float, delta=None, banned=None):
+    """Final RMSNorm of hidden_states [n <= 8, hidden] (+ delta), fp32 logits [n, vocab] against lm [vocab, hidden] and the
+    greedy token [n] int32: lowest id among the maxima, `banned` (int32 device list) left out (crag_enc_lm_head)."""
+    _req(hidden_states, torch.bfloat16, "hidden_states"); _req(final_norm_w, torch.bfloat16, "final_norm_w")
+    _req(lm, torch.bfloat16, "lm"); _req(logits, torch.float32, "logits"); _req(token, torch.int32, "token")
+    n, hidden = hidden_states.shape
+    vocab = lm.shape[0]
+    if lm.shape[1] != hidden or logits.shape != (n, vocab) or token.numel() != n:
+        raise ValueError("lm must be [vocab, hidden], logits [n, vocab] and token [n]")
+    if delta is not None:
+        _req(delta, torch.bfloat16, "delta")
+        if delta.shape != hidden_states.shape:
+            raise ValueError("delta must have the shape of hidden_states")
+    if banned is not None:
+        _req(banned, torch.int32, "banned")
+    _native.check(_native.load().crag_enc_lm_head(_p(hidden_states), _p(delta), _p(final_norm_w), _p(lm), _p(logits),
+                                                  _p(token), _p(banned), 0 if banned is None else banned.numel(), n,
+                                                  hidden, vocab, float(eps), _stream()), "crag_enc_lm_head")
+    return logits, token

@@ -4,6 +4,8 @@ EMBEDDINGS_BASE_URL at the MI355X box: `POST /embed {texts, model?} -> {embeddin
 The body is served by the in-process encoder registered with embeddings.set_encoder().
 `POST /rerank {query, documents, model?} -> {scores, order, model}` is the reranker's contract
 (the reference's NVIDIA_IMMERSION_PLAN.md:93-97), served by the reranker registered with reranker.set_reranker().
+`POST /answer` (the /retrieve request plus echo_evidence) is the citation-gated answer of answer.answer_question, served
+by the LLM registered with answer.set_llm() or the service LLM_BASE_URL names.
 `POST /retrieve` is the reference's own route (/root/reference/app/main.py:184-186) over
 retrieve.retrieve_evidence and the backend registered with retrieve.set_backend().
 
@@ -18,6 +20,7 @@ from uuid import UUID
 from fastapi import FastAPI, HTTPException
 from pydantic import BaseModel, Field
 
+from . import answer as _answer
 from . import embeddings
 from . import reranker
 from . import retrieve as _retrieve
@@ -42,7 +45,7 @@ def health() -> dict:
     enc = embeddings.get_encoder()
     return {"status": "ok" if enc is not None else "degraded", "backend": "mi355x-native",
             "encoder_loaded": enc is not None, "embed_output_dim": settings.embeddings_dim,
-            "model": settings.embeddings_model_id}
+            "model": settings.embeddings_model_id, "llm_loaded": _answer.get_llm() is not None}
 
 
 @app.post("/embed", response_model=EmbedResponse)
@@ -126,16 +129,34 @@ class RetrieveRequestModel(BaseModel):
     facet_top: int = Field(default=10, ge=1, le=64)
 
 
-@app.post("/retrieve")
-def retrieve_endpoint(payload: RetrieveRequestModel) -> dict:
+def _request_fields(payload: RetrieveRequestModel) -> dict:
     filters = None
     if payload.filters is not None:
         filters = _retrieve.RetrieveFilters(**payload.filters.model_dump())
-    request = _retrieve.RetrieveRequest(
-        query=payload.query, intent=payload.intent, filters=filters,
-        budget=_retrieve.Budget(**payload.budget.model_dump()), return_style=payload.return_style, debug=payload.debug,
-        facets=payload.facets, facet_top=payload.facet_top)
+    return dict(query=payload.query, intent=payload.intent, filters=filters,
+                budget=_retrieve.Budget(**payload.budget.model_dump()), return_style=payload.return_style,
+                debug=payload.debug, facets=payload.facets, facet_top=payload.facet_top)
+
+
+@app.post("/retrieve")
+def retrieve_endpoint(payload: RetrieveRequestModel) -> dict:
+    request = _retrieve.RetrieveRequest(**_request_fields(payload))
     try:
         return _retrieve.retrieve_evidence(request)
     except RuntimeError as exc:  # no backend registered
+        raise HTTPException(status_code=503, detail=str(exc)) from exc
+
+
+class AnswerRequestModel(RetrieveRequestModel):
+    echo_evidence: bool = False
+
+
+@app.post("/answer")
+def answer_endpoint(payload: AnswerRequestModel) -> dict:
+    request = _answer.AnswerRequest(**_request_fields(payload), echo_evidence=payload.echo_evidence)
+    try:
+        return _answer.answer_question(request)
+    except _answer.AnswerClientError as exc:
+        raise HTTPException(status_code=502, detail=str(exc)) from exc
+    except RuntimeError as exc:  # no retrieve backend registered
         raise HTTPException(status_code=503, detail=str(exc)) from exc

@@ -195,6 +195,43 @@ int crag_enc_rerank_head(const uint16_t *hidden_states, const uint16_t *delta, c
                          const int64_t *rows, const uint16_t *lm_rows, float *out, int n_pairs, int hidden, float eps,
                          void *stream);
 
+/* ---- autoregressive decoding: csrc/crag_decode.hip ----
+ *
+ * The KV cache of ONE layer is two bf16 arrays [n_slots][hkv][max_len][128] (keys: normed and rotated; values: raw).
+ * A slot holds one sequence; how many tokens it holds is the caller's knowledge and comes from the HOST.
+ *
+ * crag_enc_decode_attention: one new token for each of n_seqs (1..CRAG_DECODE_MAX_SEQS) sequences.
+ *   qkv_new [n_seqs, (hq + 2 hkv) * 128]: the raw fused projections of the new tokens (not modified);
+ *   h_slots / h_cache_len [n_seqs]: HOST arrays -- the slot of every sequence and the number of tokens it holds, which
+ *   is also the new token's position.  Per sequence: q/k RMSNorm + RoPE of the new row with the arithmetic and the
+ *   roundings of crag_enc_qk_norm_rope (the cached key of a token is the same bits whichever entry wrote it), the key
+ *   and the raw value stored at position len of the slot, attention of the hq queries over the len + 1 keys (fp32
+ *   softmax and accumulation), out [n_seqs, hq * 128] bf16.  Cache rows at or beyond len + 1 are never read.
+ *   The key range is cut into splits of CRAG_DECODE_SPLIT keys, one workgroup per (split, kv head, sequence), combined
+ *   in ascending split order by a second kernel: no atomics, and a sequence's output bits depend on nothing but its own
+ *   data -- not on n_seqs, the slot or the other sequences.  hq / hkv = 2 or 4.
+ *   workspace: crag_enc_decode_workspace_bytes(n_seqs, hq, max_len) bytes of device scratch, 16-byte aligned.
+ *   CRAG_EINVAL, nothing enqueued: a NULL pointer, n_seqs outside 1..8, a length < 0 or >= max_len (or >= max_pos, the
+ *   rows of cos_sin), a slot outside 0..n_slots - 1 or named twice in the call.  CRAG_E2BIG: the workspace is too small.
+ * crag_enc_lm_head: per row r < n_rows (1..8): x = bf16(hidden_states[r] + delta[r]) (delta nullable), the final RMSNorm
+ *   with crag_enc_rerank_head's roundings, logits[r, v] = fp32 dot with lm_head[v] for EVERY v < vocab (lm_head
+ *   [vocab, hidden] bf16; a tied model passes embed_tokens), token[r] = the lowest id among the maxima of logits[r]
+ *   that is not in banned[n_banned] (device int32, nullable with n_banned 0; at most CRAG_LM_HEAD_MAX_BANNED) -- -1 when
+ *   no id is left.  hidden % 64 == 0, n_rows * (hidden + 8) <= CRAG_LM_HEAD_MAX_ELEMS (the rows live in LDS). */
+#define CRAG_DECODE_MAX_SEQS 8
+#define CRAG_DECODE_SPLIT 128
+#define CRAG_LM_HEAD_MAX_BANNED 64
+#define CRAG_LM_HEAD_MAX_ELEMS 32760
+int64_t crag_enc_decode_workspace_bytes(int n_seqs, int hq, int max_len);
+int crag_enc_decode_attention(const uint16_t *qkv_new, const uint16_t *q_norm_w, const uint16_t *k_norm_w,
+                              const float *cos_sin, int max_pos, uint16_t *k_cache, uint16_t *v_cache, int n_slots,
+                              int max_len, const int32_t *h_slots, const int32_t *h_cache_len, int n_seqs, int hq, int hkv,
+                              float eps, float scale, void *workspace, int64_t workspace_bytes, uint16_t *out,
+                              void *stream);
+int crag_enc_lm_head(const uint16_t *hidden_states, const uint16_t *delta, const uint16_t *final_norm_w,
+                     const uint16_t *lm_head, float *logits, int32_t *token, const int32_t *banned, int n_banned,
+                     int n_rows, int hidden, int64_t vocab, float eps, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
