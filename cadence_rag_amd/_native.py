@@ -31,6 +31,10 @@ CRAG_E2BIG = -5
 CRAG_DECODE_MAX_SEQS = 8
 CRAG_DECODE_SPLIT = 128
 CRAG_LM_HEAD_MAX_BANNED = 64
+CRAG_EXTEND_BLOCK = 32
+CRAG_EXTEND_TILE = 32
+CRAG_EXTEND_SPLIT = 512
+CRAG_EXTEND_SPLIT_ROWS = 512
 
 # every symbol include/crag_dense.h declares: name -> (restype, argtypes)
 _c = ctypes
@@ -126,6 +130,9 @@ SIGNATURES = {
     "crag_enc_decode_attention": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int,
                                              _c.c_int, _c.c_float, _c.c_float, _P, _c.c_int64, _P, _P]),
     "crag_enc_lm_head": (_c.c_int, [_P, _P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_float, _P]),
+    "crag_enc_extend_workspace_bytes": (_c.c_int64, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "crag_enc_extend_attention": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _c.c_int,
+                                             _c.c_int, _c.c_int, _c.c_float, _c.c_float, _P, _c.c_int64, _P, _P]),
 }
 
 

@@ -247,6 +247,10 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
                 continue
             notes["llm_calls"] += 1
             out["model"] = model
+            # a native generator with a prefix cache says how many prompt tokens it took from its KV cache
+            reuse = getattr(_llm, "last_reuse", None) if _is_native(settings.llm_base_url) else None
+            if reuse is not None:
+                notes["prefix_reused_tokens"] = notes.get("prefix_reused_tokens", 0) + int(sum(reuse["reused"]))
             return text
 
     max_repairs = max(int(settings.answer_max_repairs), 0)

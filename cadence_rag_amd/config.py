@@ -64,6 +64,7 @@ class Settings:
     llm_max_new_tokens: int = 512
     llm_max_context: int = 8192
     llm_device: int = -1                # -1: embeddings_device
+    llm_prefix_cache: bool = True       # native LLM: a prompt that continues what its slot holds computes only the rest
     answer_max_repairs: int = 2         # reprompts of an answer that fails the citation check
 
     def __post_init__(self) -> None:

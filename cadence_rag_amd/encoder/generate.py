@@ -6,7 +6,10 @@ kernels) with a full-vocabulary head -- the in-process LLM behind /answer (caden
   step(tokens)          one new token per live sequence: per layer qkv, crag_enc_decode_attention (q/k-norm + RoPE of
                         the new row, append, attention over the cache), o, MLP; then crag_enc_lm_head (final norm, fp32
                         logits over the whole vocabulary, greedy token).
-  generate(...)         prefill + steps until a stop id or the token budget.  Greedy only.
+  extend(token_lists)   m new tokens behind the n a slot already holds: prefill's layer loop over the new rows only, with
+                        crag_enc_extend_attention (norm + RoPE, append, flash attention over the cache rows in place).
+  generate(...)         prefill + steps until a stop id or the token budget.  Greedy only.  With reuse_prefix=True a
+                        prompt that begins with what its slot holds (plan_reuse) keeps those rows and extends.
 
 The cache layout ([layer][slot][kv head][max_len][128] bf16, keys and values apart) sits behind KvCache.keys / .values.
 At most MAX_SEQS = 8 sequences decode at a time.
@@ -24,6 +27,7 @@ from . import ops
 from .qwen3 import QKV_ROW_CHUNK, PackedBatch, Qwen3Config, Qwen3Encoder
 
 MAX_SEQS = 8
+PREFIX_MIN_REUSE = 32    # one query block of the extend kernel: below it a plain prefill is no dearer
 CHAT_SYSTEM = "<|im_start|>system\n{system}<|im_end|>\n"
 CHAT_USER = "<|im_start|>user\n{user}<|im_end|>\n"
 CHAT_ASSISTANT = "<|im_start|>assistant\n{assistant}<|im_end|>\n"
@@ -32,6 +36,16 @@ CHAT_GENERATE = "<|im_start|>assistant\n<think>\n\n</think>\n\n"
 
 class PromptTooLong(ValueError):
     """A prompt does not leave room for the requested new tokens inside the context window."""
+
+
+def plan_reuse(resident_ids: Sequence[int], prompt_ids: Sequence[int], min_reuse: int = PREFIX_MIN_REUSE) -> int:
+    """How many leading cache rows of a slot that holds `resident_ids` serve `prompt_ids`: the length of the common
+    token prefix, at most len(prompt_ids) - 1 (one row must be computed to get logits), and 0 when that is less than
+    min_reuse."""
+    keep, top = 0, min(len(resident_ids), len(prompt_ids) - 1)
+    while keep < top and int(resident_ids[keep]) == int(prompt_ids[keep]):
+        keep += 1
+    return keep if keep >= max(int(min_reuse), 1) else 0
 
 
 class KvCache:
@@ -68,7 +82,7 @@ class Qwen3Generator:
     """generate(prompts, max_new_tokens, stop_ids) -> new token ids of every prompt, on one GPU and one stream."""
 
     def __init__(self, encoder: Qwen3Encoder, lm_head: torch.Tensor, tokenizer=None, *, max_context: Optional[int] = None,
-                 max_seqs: int = MAX_SEQS, model_id: Optional[str] = None) -> None:
+                 max_seqs: int = MAX_SEQS, model_id: Optional[str] = None, prefix_cache: bool = False) -> None:
         c = encoder.cfg
         if c.head_dim != 128 or c.num_heads % c.num_kv_heads or c.num_heads // c.num_kv_heads not in (2, 4):
             raise ValueError("the decode attention kernel is built for head_dim 128 and 2 or 4 query heads per kv head")
@@ -91,14 +105,19 @@ class Qwen3Generator:
         self.max_seqs = int(max_seqs)
         self.cache = KvCache(c.num_layers, self.max_seqs, c.num_kv_heads, self.max_context, self.device)
         self._workspace = ops.decode_workspace(self.max_seqs, c.num_heads, self.max_context, self.device)
+        self._extend_ws: Optional[torch.Tensor] = None   # extend's scratch: grows to the largest call
         self.live: List[int] = []          # slots of the sequences the next step() advances
+        self.tokens: List[List[int]] = [[] for _ in range(self.max_seqs)]   # the token ids every slot holds
+        self.prefix_cache = bool(prefix_cache)   # generate_text reuses a slot's rows (generate(reuse_prefix=True))
+        self.last_reuse: Optional[Dict[str, List[int]]] = None   # per prompt of the last generate(reuse_prefix=True)
         self.force_library = False         # tests: keep the 4B widths off the small_gemm path
         self.last_path = ""
 
     # -- construction ---------------------------------------------------------------------------------------------
     @classmethod
     def from_pretrained(cls, path: str, device: Optional[torch.device] = None, max_context: int = 8192, *,
-                        max_seqs: int = MAX_SEQS, model_id: Optional[str] = None) -> "Qwen3Generator":
+                        max_seqs: int = MAX_SEQS, model_id: Optional[str] = None, prefix_cache: bool = False
+                        ) -> "Qwen3Generator":
         """A local *ForCausalLM checkpoint directory (config.json, *.safetensors, tokenizer files; nothing is fetched),
         lm_head tied to embed_tokens or not."""
         import json
@@ -131,7 +150,7 @@ class Qwen3Generator:
         enc = Qwen3Encoder.from_state_dict(cfg, sd, device, prefix=prefix)
         enc.tokenizer = tokenizer
         return cls(enc, enc.embed if tied else head, tokenizer, max_context=max_context, max_seqs=max_seqs,
-                   model_id=cfg.model_id)
+                   model_id=cfg.model_id, prefix_cache=prefix_cache)
 
     # -- prompts --------------------------------------------------------------------------------------------------
     def chat_ids(self, messages: Sequence[Dict[str, str]]) -> List[int]:
@@ -221,12 +240,93 @@ class Qwen3Generator:
             ops.rmsnorm(delta, L["ln2"], normed, c.rms_norm_eps, residual_in=resid, residual_out=resid)
             ops.swiglu(F.linear(normed, L["gate_up"]), act)
             delta = F.linear(act, L["down"])
-        for slot, m in zip(slots, lens):
+        for slot, m, tl in zip(slots, lens, token_lists):
             self.cache.lens[slot] = m
+            self.tokens[slot] = [int(x) for x in tl]
         self.live = list(slots)
         logits, self.last_tokens = self._head(resid.index_select(0, batch.last_tok),
                                               delta.index_select(0, batch.last_tok))
         return logits
+
+    @torch.no_grad()
+    def extend(self, token_lists: Sequence[Sequence[int]], slots: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """Appends token_lists[b] to slot slots[b] (default b) behind the cache.lens[slot] tokens it holds -- an empty
+        slot is allowed -- and makes these the live sequences.  prefill's layer loop over the new rows only, with
+        crag_enc_extend_attention in the place of qk_rope_vt + the cache copies + the packed attention.  Returns the
+        logits of every sequence's last new row [n, vocab] fp32 on the device; .last_tokens holds their greedy tokens."""
+        c, enc, dev, bf = self.cfg, self.encoder, self.device, torch.bfloat16
+        n = len(token_lists)
+        slots = list(range(n)) if slots is None else [int(s) for s in slots]
+        if not 1 <= n <= self.max_seqs or len(slots) != n or len(set(slots)) != n or \
+                any(not 0 <= s < self.max_seqs for s in slots):
+            raise ValueError(f"extend takes 1..{self.max_seqs} token lists, each for a slot of its own")
+        news = [len(tl) for tl in token_lists]
+        if min(news) <= 0:
+            raise ValueError("every sequence needs at least one new token")
+        held = [self.cache.lens[s] for s in slots]
+        full = max(h + m for h, m in zip(held, news))
+        if full >= self.max_context:
+            raise PromptTooLong(f"a sequence of {full} tokens leaves no room in a context of {self.max_context}")
+        t = sum(news)
+        need = ops.extend_workspace_bytes(n, c.num_heads, t, full)   # the rotated queries, the key splits' partials
+        if self._extend_ws is None or self._extend_ws.numel() < need:
+            self._extend_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ids = torch.from_numpy(np.concatenate([np.asarray(tl, dtype=np.int32) for tl in token_lists])).to(dev)
+        x = torch.empty(t, c.hidden_size, dtype=bf, device=dev)
+        ops.embed_gather(ids, enc.embed, x)
+        resid = torch.empty_like(x)
+        normed = torch.empty_like(x)
+        qkv = torch.empty(t, c.q_size + 2 * c.kv_size, dtype=bf, device=dev)
+        attn = torch.empty(t, c.q_size, dtype=bf, device=dev)
+        act = torch.empty(t, c.intermediate_size, dtype=bf, device=dev)
+        scale = 1.0 / math.sqrt(c.head_dim)
+        delta: Optional[torch.Tensor] = None
+        for i, L in enumerate(enc.layers):
+            if i == 0:
+                ops.rmsnorm(x, L["ln1"], normed, c.rms_norm_eps, residual_in=None, residual_out=None)
+                resid.copy_(x)
+            else:
+                ops.rmsnorm(delta, L["ln1"], normed, c.rms_norm_eps, residual_in=resid, residual_out=resid)
+            for lo in range(0, t, QKV_ROW_CHUNK):
+                hi = min(t, lo + QKV_ROW_CHUNK)
+                torch.matmul(normed[lo:hi], L["qkv"].t(), out=qkv[lo:hi])
+            kc, vc = self.cache.layer(i)
+            ops.extend_attention(qkv, L["q_norm"], L["k_norm"], enc._cos_sin, kc, vc, slots, held, news, attn,
+                                 c.num_heads, c.num_kv_heads, c.rms_norm_eps, scale, self._extend_ws)
+            delta = F.linear(attn, L["o"])
+            ops.rmsnorm(delta, L["ln2"], normed, c.rms_norm_eps, residual_in=resid, residual_out=resid)
+            ops.swiglu(F.linear(normed, L["gate_up"]), act)
+            delta = F.linear(act, L["down"])
+        for slot, m, tl in zip(slots, news, token_lists):
+            self._forget_stale(slot)
+            self.cache.lens[slot] += m
+            self.tokens[slot].extend(int(x) for x in tl)
+        self.live = list(slots)
+        last = torch.from_numpy(np.cumsum(news) - 1).to(dev)
+        logits, self.last_tokens = self._head(resid.index_select(0, last), delta.index_select(0, last))
+        return logits
+
+    # -- what the slots hold ---------------------------------------------------------------------------------------
+    def _forget_stale(self, slot: int) -> None:
+        """A caller that set cache.lens by hand has left the id list behind: such a slot's ids are unknown (-1 matches
+        no token, so nothing of it is ever reused)."""
+        if len(self.tokens[slot]) != self.cache.lens[slot]:
+            self.tokens[slot] = [-1] * self.cache.lens[slot]
+
+    def resident(self, slot: int) -> List[int]:
+        """The token ids slot holds, one per cache row."""
+        self._forget_stale(slot)
+        return self.tokens[slot]
+
+    def truncate(self, slot: int, n: int) -> None:
+        """Shortens a slot to its first n tokens.  Host only: rows behind cache.lens are never read and are overwritten
+        by the next append."""
+        n = int(n)
+        if not 0 <= n <= self.cache.lens[slot]:
+            raise ValueError(f"slot {slot} holds {self.cache.lens[slot]} tokens: cannot truncate to {n}")
+        self._forget_stale(slot)
+        self.cache.lens[slot] = n
+        del self.tokens[slot][n:]
 
     @torch.no_grad()
     def step(self, tokens: Sequence[int], slots: Optional[Sequence[int]] = None, banned: Optional[torch.Tensor] = None
@@ -292,17 +392,22 @@ class Qwen3Generator:
                 ops.swiglu(F.linear(normed, L["gate_up"]), act)
                 delta = F.linear(act, L["down"])
             hidden = resid
-        for s in slots:
+        for s, tok in zip(slots, tokens):
+            self._forget_stale(s)
             self.cache.lens[s] += 1
+            self.tokens[s].append(int(tok))
         logits, token = self._head(hidden, delta, banned)
         return token, logits
 
     @torch.no_grad()
-    def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_ids: Sequence[int] = ()
-                 ) -> List[List[int]]:
+    def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_ids: Sequence[int] = (),
+                 reuse_prefix: bool = False) -> List[List[int]]:
         """Greedy continuation of every prompt (token ids): at most max_new_tokens ids each, ending before the first
         stop id.  A prompt longer than max_context - max_new_tokens raises PromptTooLong (a ValueError): the caller
-        shortens its prompt, nothing is truncated here."""
+        shortens its prompt, nothing is truncated here.
+        reuse_prefix: prompt b is planned against what slot b holds (plan_reuse).  If no slot can keep anything the call
+        is the plain prefill; otherwise every slot is cut to what it keeps and the rests go through one extend().
+        last_reuse = {"reused": [...], "computed": [...]} then holds the tokens per prompt (None without reuse_prefix)."""
         max_new_tokens = int(max_new_tokens)
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be positive")
@@ -312,7 +417,17 @@ class Qwen3Generator:
             raise PromptTooLong(f"a prompt of {longest} tokens does not fit: max_context {self.max_context} - "
                                 f"max_new_tokens {max_new_tokens} leaves {room}")
         stop = {int(s) for s in stop_ids}
-        self.prefill(prompts)
+        keeps = [0] * len(prompts)
+        if reuse_prefix and len(prompts) <= self.max_seqs:
+            keeps = [plan_reuse(self.resident(b), p, PREFIX_MIN_REUSE) for b, p in enumerate(prompts)]
+        if any(keeps):
+            for b, keep in enumerate(keeps):
+                self.truncate(b, keep)
+            self.extend([list(p[keep:]) for p, keep in zip(prompts, keeps)])
+        else:
+            self.prefill(prompts)
+        self.last_reuse = {"reused": list(keeps), "computed": [len(p) - keep for p, keep in zip(prompts, keeps)]} \
+            if reuse_prefix else None
         out: List[List[int]] = [[] for _ in prompts]
         nxt = self.last_tokens.tolist()
         live = list(range(len(prompts)))          # slot b holds prompt b
@@ -336,5 +451,6 @@ class Qwen3Generator:
 
     def generate_text(self, messages: Sequence[Dict[str, str]], max_new_tokens: int) -> str:
         """One chat -> the assistant's reply as text."""
-        ids = self.generate([self.chat_ids(messages)], max_new_tokens, self.stop_ids())[0]
+        ids = self.generate([self.chat_ids(messages)], max_new_tokens, self.stop_ids(),
+                            reuse_prefix=self.prefix_cache)[0]
         return self._tokenizer().decode(ids, skip_special_tokens=True)

@@ -364,3 +364,47 @@ def lm_head(hidden_states, final_norm_w, lm, logits, token, eps: float, delta=No
                                                   _p(token), _p(banned), 0 if banned is None else banned.numel(), n,
                                                   hidden, vocab, float(eps), _stream()), "crag_enc_lm_head")
     return logits, token
+
+
+# -- continuing cached sequences (csrc/crag_extend.hip) ---------------------------------------------------------------
+def extend_workspace_bytes(n_seqs: int, hq: int, max_new_rows: int, max_len: int) -> int:
+    """Bytes of scratch extend_attention needs at most for up to n_seqs sequences with up to max_new_rows new rows in
+    all, none of them longer than max_len rows once extended."""
+    need = int(_native.load().crag_enc_extend_workspace_bytes(int(n_seqs), int(hq), int(max_new_rows), int(max_len)))
+    if need <= 0:
+        raise ValueError(f"no extend workspace for n_seqs={n_seqs}, hq={hq}, max_new_rows={max_new_rows}, max_len={max_len}")
+    return need
+
+
+def extend_workspace(n_seqs: int, hq: int, max_new_rows: int, max_len: int, device) -> torch.Tensor:
+    """Device scratch of extend_attention (extend_workspace_bytes of uint8)."""
+    return torch.empty(extend_workspace_bytes(n_seqs, hq, max_new_rows, max_len), dtype=torch.uint8, device=device)
+
+
+def extend_attention(qkv_new, q_w, k_w, cos_sin, k_cache, v_cache, slots, cache_len, new_len, out, hq: int, hkv: int,
+                     eps: float, scale: float, workspace):
+    """new_len[b] new tokens per sequence against ONE layer's cache (crag_enc_extend_attention).  qkv_new [T_new,
+    (hq + 2 hkv) * 128] raw projections, the sequences' rows back to back; k_cache / v_cache [n_slots, hkv, max_len, 128]
+    bf16; slots / cache_len / new_len: HOST ints per sequence.  The new keys and values are appended at positions
+    cache_len .. cache_len + new_len - 1 of the slot; query row i sees the keys 0 .. cache_len + i; out [T_new, hq * 128]."""
+    _req(qkv_new, torch.bfloat16, "qkv_new"); _req(cos_sin, torch.float32, "cos_sin"); _req(out, torch.bfloat16, "out")
+    _req(k_cache, torch.bfloat16, "k_cache"); _req(v_cache, torch.bfloat16, "v_cache")
+    _req(q_w, torch.bfloat16, "q_w"); _req(k_w, torch.bfloat16, "k_w"); _req(workspace, torch.uint8, "workspace")
+    n = len(slots)
+    if len(cache_len) != n or len(new_len) != n:
+        raise ValueError("slots, cache_len and new_len need one entry per sequence")
+    n_slots, kv_heads, max_len, dim = k_cache.shape
+    if v_cache.shape != k_cache.shape or kv_heads != hkv or dim != 128:
+        raise ValueError("k_cache and v_cache must both be [n_slots, hkv, max_len, 128]")
+    t_new = sum(max(int(x), 0) for x in new_len)
+    if qkv_new.shape[0] < t_new or out.shape[0] < t_new or qkv_new.shape[1] != (hq + 2 * hkv) * 128 \
+            or out.shape[1] != hq * 128:
+        raise ValueError("qkv_new must be [T_new, (hq + 2 hkv) * 128] and out [T_new, hq * 128]")
+    h_slots = (ctypes.c_int32 * max(n, 1))(*[int(s) for s in slots])
+    h_lens = (ctypes.c_int32 * max(n, 1))(*[int(x) for x in cache_len])
+    h_new = (ctypes.c_int32 * max(n, 1))(*[int(x) for x in new_len])
+    _native.check(_native.load().crag_enc_extend_attention(
+        _p(qkv_new), _p(q_w), _p(k_w), _p(cos_sin), int(cos_sin.shape[0]), _p(k_cache), _p(v_cache), int(n_slots),
+        int(max_len), h_slots, h_lens, h_new, n, int(hq), int(hkv), float(eps), float(scale), _p(workspace),
+        int(workspace.numel()), _p(out), _stream()), "crag_enc_extend_attention")
+    return out

@@ -232,6 +232,39 @@ int crag_enc_lm_head(const uint16_t *hidden_states, const uint16_t *delta, const
                      const uint16_t *lm_head, float *logits, int32_t *token, const int32_t *banned, int n_banned,
                      int n_rows, int hidden, int64_t vocab, float eps, void *stream);
 
+/* ---- continuing cached sequences: csrc/crag_extend.hip ----
+ *
+ * crag_enc_extend_attention: h_new_len[b] >= 1 new tokens for each of n_seqs (1..CRAG_DECODE_MAX_SEQS) sequences, over
+ *   the cache of ONE layer (the layout above).  Sequence b sits in slot h_slots[b] and holds h_cache_len[b] >= 0 tokens;
+ *   its new rows lie back to back, in the order of the sequences, in qkv_new [T_new, (hq + 2 hkv) * 128] (raw fused
+ *   projections, not modified; T_new = the sum of h_new_len) and in out [T_new, hq * 128] bf16.  h_slots / h_cache_len /
+ *   h_new_len are HOST arrays.
+ *   New row i of sequence b has position cache_len + i.  q/k RMSNorm + RoPE with the arithmetic and the roundings of
+ *   crag_enc_qk_norm_rope; the key and the raw value are stored at row cache_len + i of the slot -- the bits prefill
+ *   and crag_enc_decode_attention would have appended -- and the rotated query goes to the workspace.  Query row i
+ *   then sees the keys 0 .. cache_len + i of its slot: causal GQA flash attention on bf16 MFMA with fp32 online
+ *   softmax, one workgroup per (kv head, block of CRAG_EXTEND_BLOCK query rows of one sequence), its waves the hq / hkv
+ *   = 2 or 4 query heads, walking tiles of CRAG_EXTEND_TILE keys read in place from the cache.  No cache row at or
+ *   beyond cache_len + new_len is read, nothing beyond max_len.  A sequence with at most CRAG_EXTEND_SPLIT_ROWS new
+ *   rows cuts the keys of a query block into splits of CRAG_EXTEND_SPLIT keys, one workgroup each, combined in
+ *   ascending split order by a third kernel.  No atomics, and a sequence's output bits and appended bits depend on
+ *   its own data alone -- not on n_seqs, the slot or the other sequences.
+ *   workspace: crag_enc_extend_workspace_bytes(n_seqs, hq, max_new_rows, max_len) bytes of device scratch, 16-byte
+ *   aligned, max_new_rows >= T_new.
+ *   CRAG_EINVAL, nothing enqueued: a NULL pointer, n_seqs outside 1..8, hq / hkv not 2 or 4, new_len < 1, cache_len < 0,
+ *   cache_len + new_len > max_len or > max_pos (the rows of cos_sin), a slot outside 0..n_slots - 1 or named twice in
+ *   the call, a misaligned pointer.  CRAG_E2BIG: the workspace is too small. */
+#define CRAG_EXTEND_BLOCK 32
+#define CRAG_EXTEND_TILE 32
+#define CRAG_EXTEND_SPLIT 512
+#define CRAG_EXTEND_SPLIT_ROWS 512
+int64_t crag_enc_extend_workspace_bytes(int n_seqs, int hq, int max_new_rows, int max_len);
+int crag_enc_extend_attention(const uint16_t *qkv_new, const uint16_t *q_norm_w, const uint16_t *k_norm_w,
+                              const float *cos_sin, int max_pos, uint16_t *k_cache, uint16_t *v_cache, int n_slots,
+                              int max_len, const int32_t *h_slots, const int32_t *h_cache_len, const int32_t *h_new_len,
+                              int n_seqs, int hq, int hkv, float eps, float scale, void *workspace,
+                              int64_t workspace_bytes, uint16_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
