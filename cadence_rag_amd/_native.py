@@ -35,6 +35,9 @@ CRAG_EXTEND_BLOCK = 32
 CRAG_EXTEND_TILE = 32
 CRAG_EXTEND_SPLIT = 512
 CRAG_EXTEND_SPLIT_ROWS = 512
+CRAG_GRAMMAR_MAX_STATES = 4096
+CRAG_GRAMMAR_MAX_CLASSES = 64
+CRAG_GRAMMAR_DEAD = 0xFFFF
 
 # every symbol include/crag_dense.h declares: name -> (restype, argtypes)
 _c = ctypes
@@ -133,6 +136,8 @@ SIGNATURES = {
     "crag_enc_extend_workspace_bytes": (_c.c_int64, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "crag_enc_extend_attention": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _c.c_int,
                                              _c.c_int, _c.c_int, _c.c_float, _c.c_float, _P, _c.c_int64, _P, _P]),
+    "crag_enc_grammar_argmax": (_c.c_int, [_P, _c.c_int64, _P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _c.c_int,
+                                           _P]),
 }
 
 

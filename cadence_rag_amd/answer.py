@@ -8,6 +8,10 @@ set_llm() (cadence_rag_amd.encoder.generate.Qwen3Generator); an http(s) URL spea
 The gate: every sentence of an answer must cite at least one evidence id of the pack (`[Q-123]`, `[A-45]`, the
 evidence_id format retrieve._pack emits).  An answer that fails is sent back with the validator's report at most
 ANSWER_MAX_REPAIRS times; if it still fails, the response carries no answer.  No uncited sentence ever leaves.
+
+ANSWER_CONSTRAINED (native backend, a model with supports_grammar): the reply is decoded under the citation grammar of
+the evidence ids in the prompt (cadence_rag_amd.grammar.citation_grammar), which makes a failing answer unrepresentable
+whenever the model stops by itself.  The gate and the repair loop run unchanged on whatever comes back.
 """
 from __future__ import annotations
 
@@ -18,8 +22,10 @@ from typing import Any, Dict, List, Optional, Protocol, Sequence, Tuple
 
 from . import retrieve as _retrieve
 from .config import settings
+from .grammar import INSUFFICIENT as _INSUFFICIENT_BYTES
+from .grammar import TokenGrammar, citation_grammar
 
-INSUFFICIENT = "INSUFFICIENT_EVIDENCE"
+INSUFFICIENT = _INSUFFICIENT_BYTES.decode("ascii")   # "INSUFFICIENT_EVIDENCE": one definition, the grammar's
 STATUS_OK = "ok"
 STATUS_INSUFFICIENT = "insufficient_evidence"
 STATUS_FAILED = "citation_check_failed"
@@ -38,7 +44,10 @@ class AnswerClientError(RuntimeError):
 class ChatModel(Protocol):
     """In-process backend: a chat (list of {"role", "content"}) -> the assistant's reply.  A ValueError means the prompt
     does not fit the context (the caller drops evidence and retries); any other exception is reported as
-    AnswerClientError.  `model_id` names the model."""
+    AnswerClientError.  `model_id` names the model.
+    Optional: a model whose class sets `supports_grammar = True` also takes `generate_text(messages, max_new_tokens,
+    grammar=TokenGrammar)` and decodes only what grammar.dfa accepts; its `token_table()`, if it has one, is the cached
+    byte table of its vocabulary that goes into the TokenGrammar.  The keyword is passed only to such a model."""
 
     model_id: str
 
@@ -152,14 +161,18 @@ def _chat_http(messages: List[Dict[str, str]], max_new_tokens: int) -> Tuple[str
     return content, str(payload.get("model") or settings.llm_model)
 
 
-def _chat_native(messages: List[Dict[str, str]], max_new_tokens: int) -> Tuple[str, str]:
+def _chat_native(messages: List[Dict[str, str]], max_new_tokens: int, grammar: Optional[TokenGrammar] = None
+                 ) -> Tuple[str, str]:
     """ValueError (the prompt does not fit) passes through to the caller, which drops evidence."""
     llm = _llm
     if llm is None:
         raise AnswerClientError("native LLM is not loaded (call set_llm)")
     try:
         with _llm_lock:
-            text = llm.generate_text(messages, max_new_tokens)
+            if grammar is None:
+                text = llm.generate_text(messages, max_new_tokens)
+            else:
+                text = llm.generate_text(messages, max_new_tokens, grammar=grammar)
     except (AnswerClientError, ValueError):
         raise
     except Exception as exc:  # noqa: BLE001 - callers rely on a single error type
@@ -169,14 +182,34 @@ def _chat_native(messages: List[Dict[str, str]], max_new_tokens: int) -> Tuple[s
     return text, str(getattr(llm, "model_id", None) or settings.llm_model)
 
 
-def chat(messages: List[Dict[str, str]], max_new_tokens: Optional[int] = None) -> Tuple[str, str]:
-    """(reply, model id) from the configured LLM."""
+def chat(messages: List[Dict[str, str]], max_new_tokens: Optional[int] = None, grammar: Optional[TokenGrammar] = None
+         ) -> Tuple[str, str]:
+    """(reply, model id) from the configured LLM.  grammar: native backend only (an HTTP service cannot take one)."""
     if not llm_enabled():
         raise AnswerClientError("LLM_BASE_URL is not configured")
     budget = int(max_new_tokens or settings.llm_max_new_tokens)
     if _is_native(settings.llm_base_url):
-        return _chat_native(messages, budget)
+        return _chat_native(messages, budget, grammar)
     return _chat_http(messages, budget)
+
+
+def constrained_decoding() -> bool:
+    """ANSWER_CONSTRAINED applies: it is on, the backend is native and the registered model takes a grammar."""
+    return bool(settings.answer_constrained) and _is_native(settings.llm_base_url) \
+        and bool(getattr(_llm, "supports_grammar", False))
+
+
+def _grammar_for(items: Sequence[Dict[str, Any]], notes: Dict[str, Any]) -> Optional[TokenGrammar]:
+    """The citation grammar of the items in the prompt; None (and the reason in the notes) when it cannot be built."""
+    try:
+        dfa = citation_grammar([i["evidence_id"] for i in items])
+    except ValueError as exc:
+        notes["constrained"] = False
+        notes["constrained_error"] = str(exc)
+        return None
+    table = getattr(_llm, "token_table", None)
+    notes["constrained"] = True
+    return TokenGrammar(dfa, table() if callable(table) else None)
 
 
 # ---- /answer ----------------------------------------------------------------------------------------------------
@@ -225,6 +258,8 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
     pack = _retrieve.retrieve_evidence(pack_request, backend)
     items = _evidence_items(pack)
     notes: Dict[str, Any] = {"evidence_items": len(items), "dropped_evidence": 0, "llm_calls": 0, "validator": None}
+    if settings.answer_constrained:     # with the setting off the response is what it always was: no such note
+        notes["constrained"] = False    # True once a call has decoded under a grammar
     out: Dict[str, Any] = {"query_id": pack["query_id"], "answer": None, "status": STATUS_INSUFFICIENT, "citations": [],
                            "repairs": 0, "model": None, "notes": notes}
     if getattr(request, "echo_evidence", False):
@@ -235,10 +270,14 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
     turns: List[Dict[str, str]] = []
     query = request.query.strip()
 
+    constrained = constrained_decoding()
+
     def call() -> str:
         while True:
             try:
-                text, model = chat(build_messages(query, items, turns))
+                # the grammar of the items in THIS prompt: rebuilt when an item has been dropped for length
+                grammar = _grammar_for(items, notes) if constrained else None
+                text, model = chat(build_messages(query, items, turns), grammar=grammar)
             except ValueError as exc:   # the prompt does not fit the model's context: the lowest-ranked item goes
                 if len(items) <= 1:
                     raise AnswerClientError(f"the prompt does not fit with a single evidence item: {exc}") from exc

@@ -66,6 +66,9 @@ class Settings:
     llm_device: int = -1                # -1: embeddings_device
     llm_prefix_cache: bool = True       # native LLM: a prompt that continues what its slot holds computes only the rest
     answer_max_repairs: int = 2         # reprompts of an answer that fails the citation check
+    # native LLM only: decode under the citation grammar of the evidence in the prompt (cadence_rag_amd.grammar), so that
+    # an uncited sentence or an id outside the pack cannot be generated; the validator still checks what comes back
+    answer_constrained: bool = False
 
     def __post_init__(self) -> None:
         if self.rerank_device < 0:

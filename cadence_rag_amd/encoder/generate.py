@@ -9,7 +9,10 @@ kernels) with a full-vocabulary head -- the in-process LLM behind /answer (caden
   extend(token_lists)   m new tokens behind the n a slot already holds: prefill's layer loop over the new rows only, with
                         crag_enc_extend_attention (norm + RoPE, append, flash attention over the cache rows in place).
   generate(...)         prefill + steps until a stop id or the token budget.  Greedy only.  With reuse_prefix=True a
-                        prompt that begins with what its slot holds (plan_reuse) keeps those rows and extends.
+                        prompt that begins with what its slot holds (plan_reuse) keeps those rows and extends.  With a
+                        grammar (cadence_rag_amd.grammar.TokenGrammar) every token is picked by crag_enc_grammar_argmax
+                        among the tokens the sequence's automaton state allows, on the logits prefill / extend / step
+                        return; the states live on the device.
 
 The cache layout ([layer][slot][kv head][max_len][128] bf16, keys and values apart) sits behind KvCache.keys / .values.
 At most MAX_SEQS = 8 sequences decode at a time.
@@ -23,6 +26,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from ..grammar import KIND_STOP, TokenGrammar, TokenTable
 from . import ops
 from .qwen3 import QKV_ROW_CHUNK, PackedBatch, Qwen3Config, Qwen3Encoder
 
@@ -81,6 +85,8 @@ class KvCache:
 class Qwen3Generator:
     """generate(prompts, max_new_tokens, stop_ids) -> new token ids of every prompt, on one GPU and one stream."""
 
+    supports_grammar = True   # generate / generate_text take grammar=TokenGrammar (answer.py asks before passing one)
+
     def __init__(self, encoder: Qwen3Encoder, lm_head: torch.Tensor, tokenizer=None, *, max_context: Optional[int] = None,
                  max_seqs: int = MAX_SEQS, model_id: Optional[str] = None, prefix_cache: bool = False) -> None:
         c = encoder.cfg
@@ -110,6 +116,8 @@ class Qwen3Generator:
         self.tokens: List[List[int]] = [[] for _ in range(self.max_seqs)]   # the token ids every slot holds
         self.prefix_cache = bool(prefix_cache)   # generate_text reuses a slot's rows (generate(reuse_prefix=True))
         self.last_reuse: Optional[Dict[str, List[int]]] = None   # per prompt of the last generate(reuse_prefix=True)
+        self.last_grammar: Optional[Dict[str, List[bool]]] = None   # per prompt of the last generate(grammar=...)
+        self._token_table: Optional[TokenTable] = None   # the vocabulary's bytes: built once, its tensors stay in HBM
         self.force_library = False         # tests: keep the 4B widths off the small_gemm path
         self.last_path = ""
 
@@ -173,6 +181,13 @@ class Qwen3Generator:
         if getattr(tok, "eos_token_id", None) is not None:
             ids.append(int(tok.eos_token_id))
         return sorted(set(ids))
+
+    def token_table(self) -> TokenTable:
+        """The bytes and kinds of the whole vocabulary (the model's, which may be padded beyond the tokenizer's), the
+        stop ids as stop tokens: what a TokenGrammar without a table of its own decodes with."""
+        if self._token_table is None:
+            self._token_table = TokenTable.from_tokenizer(self._tokenizer(), self.stop_ids(), self.cfg.vocab_size)
+        return self._token_table
 
     def _tokenizer(self):
         if self.tokenizer is None:
@@ -401,13 +416,18 @@ class Qwen3Generator:
 
     @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_ids: Sequence[int] = (),
-                 reuse_prefix: bool = False) -> List[List[int]]:
+                 reuse_prefix: bool = False, grammar: Optional[TokenGrammar] = None) -> List[List[int]]:
         """Greedy continuation of every prompt (token ids): at most max_new_tokens ids each, ending before the first
         stop id.  A prompt longer than max_context - max_new_tokens raises PromptTooLong (a ValueError): the caller
         shortens its prompt, nothing is truncated here.
         reuse_prefix: prompt b is planned against what slot b holds (plan_reuse).  If no slot can keep anything the call
         is the plain prefill; otherwise every slot is cut to what it keeps and the rests go through one extend().
-        last_reuse = {"reused": [...], "computed": [...]} then holds the tokens per prompt (None without reuse_prefix)."""
+        last_reuse = {"reused": [...], "computed": [...]} then holds the tokens per prompt (None without reuse_prefix).
+        grammar: every prompt gets an automaton state on the device, starting at grammar.dfa.start; every token -- the
+        first one too -- is the greedy one among the tokens that state allows (ops.grammar_argmax).  A sequence then also
+        ends at a stop token of the grammar's table, which the automaton allows in accepting states only, and at -1
+        (nothing allowed).  last_grammar = {"accepted": [...]}: whether each sequence ended on such a stop token (None
+        without a grammar)."""
         max_new_tokens = int(max_new_tokens)
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be positive")
@@ -417,23 +437,48 @@ class Qwen3Generator:
             raise PromptTooLong(f"a prompt of {longest} tokens does not fit: max_context {self.max_context} - "
                                 f"max_new_tokens {max_new_tokens} leaves {room}")
         stop = {int(s) for s in stop_ids}
+        if grammar is not None:
+            table = grammar.table if grammar.table is not None else self.token_table()
+            if table.vocab != self.cfg.vocab_size:
+                raise ValueError(f"the grammar's token table holds {table.vocab} ids, the model {self.cfg.vocab_size}")
+            if len(prompts) > self.max_seqs:
+                raise ValueError(f"generate takes 1..{self.max_seqs} prompts")
         keeps = [0] * len(prompts)
         if reuse_prefix and len(prompts) <= self.max_seqs:
             keeps = [plan_reuse(self.resident(b), p, PREFIX_MIN_REUSE) for b, p in enumerate(prompts)]
         if any(keeps):
             for b, keep in enumerate(keeps):
                 self.truncate(b, keep)
-            self.extend([list(p[keep:]) for p, keep in zip(prompts, keeps)])
+            logits = self.extend([list(p[keep:]) for p, keep in zip(prompts, keeps)])
         else:
-            self.prefill(prompts)
+            logits = self.prefill(prompts)
         self.last_reuse = {"reused": list(keeps), "computed": [len(p) - keep for p, keep in zip(prompts, keeps)]} \
             if reuse_prefix else None
         out: List[List[int]] = [[] for _ in prompts]
-        nxt = self.last_tokens.tolist()
         live = list(range(len(prompts)))          # slot b holds prompt b
+        accepted = [False] * len(prompts)
+        if grammar is None:
+            nxt = self.last_tokens.tolist()
+        else:
+            tables = table.to(self.device) + grammar.dfa.to(self.device)
+            state = torch.full((len(prompts),), int(grammar.dfa.start), dtype=torch.int32, device=self.device)
+
+            def select(rows: List[int], logits: torch.Tensor) -> List[int]:
+                """The allowed greedy token of the sequences `rows` (logits [len(rows), vocab]); their states move on."""
+                idx = torch.tensor(rows, dtype=torch.int64).to(self.device)
+                cur = state.index_select(0, idx)
+                token = torch.empty(len(rows), dtype=torch.int32, device=self.device)
+                ops.grammar_argmax(logits, *tables, cur, token)
+                state.index_copy_(0, idx, cur)
+                return token.tolist()
+
+            nxt = select(live, logits)
         while live:
             feed, keep = [], []
             for b, tok in zip(live, nxt):
+                if grammar is not None and tok >= 0 and table.kind[tok] == KIND_STOP:
+                    accepted[b] = True
+                    continue
                 if tok in stop or tok < 0:
                     continue
                 out[b].append(int(tok))
@@ -444,13 +489,15 @@ class Qwen3Generator:
             if not live:
                 break
             self.live = list(live)
-            token, _ = self.step(feed)
-            nxt = token.tolist()
+            token, logits = self.step(feed)
+            nxt = token.tolist() if grammar is None else select(live, logits)
         self.live = []
+        self.last_grammar = {"accepted": accepted} if grammar is not None else None
         return out
 
-    def generate_text(self, messages: Sequence[Dict[str, str]], max_new_tokens: int) -> str:
-        """One chat -> the assistant's reply as text."""
+    def generate_text(self, messages: Sequence[Dict[str, str]], max_new_tokens: int,
+                      grammar: Optional[TokenGrammar] = None) -> str:
+        """One chat -> the assistant's reply as text; under `grammar` when one is given (generate)."""
         ids = self.generate([self.chat_ids(messages)], max_new_tokens, self.stop_ids(),
-                            reuse_prefix=self.prefix_cache)[0]
+                            reuse_prefix=self.prefix_cache, grammar=grammar)[0]
         return self._tokenizer().decode(ids, skip_special_tokens=True)

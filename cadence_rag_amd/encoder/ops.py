@@ -366,6 +366,36 @@ def lm_head(hidden_states, final_norm_w, lm, logits, token, eps: float, delta=No
     return logits, token
 
 
+# -- greedy selection under a byte automaton (csrc/crag_grammar.hip) ---------------------------------------------------
+def grammar_argmax(logits, tok_offsets, tok_bytes, tok_kind, class_of, trans, accept, state, token, allowed_bits=None):
+    """Per row of logits [n <= 8, vocab] fp32: token[r] (int32) = the lowest id among the maxima over the tokens the
+    automaton allows in state[r] (int32, device, updated in place to the chosen token's end state), -1 when nothing is
+    allowed (crag_enc_grammar_argmax).  tok_offsets [vocab + 1] int32 / tok_bytes uint8 / tok_kind [vocab] uint8: the
+    token table; class_of [256] uint8, trans [n_states, n_classes] uint16 (stored as int16), accept [n_states] uint8:
+    the automaton.  allowed_bits (optional) [n, ceil(vocab / 32)] int32 receives the allowed flags."""
+    _req(logits, torch.float32, "logits"); _req(tok_offsets, torch.int32, "tok_offsets")
+    _req(tok_bytes, torch.uint8, "tok_bytes"); _req(tok_kind, torch.uint8, "tok_kind")
+    _req(class_of, torch.uint8, "class_of"); _req(trans, torch.int16, "trans"); _req(accept, torch.uint8, "accept")
+    _req(state, torch.int32, "state"); _req(token, torch.int32, "token")
+    if logits.dim() != 2 or trans.dim() != 2:
+        raise ValueError("logits must be [n, vocab] and trans [n_states, n_classes]")
+    n, vocab = logits.shape
+    n_states, n_classes = trans.shape
+    if tok_offsets.numel() != vocab + 1 or tok_kind.numel() != vocab or class_of.numel() != 256 \
+            or accept.numel() != n_states or state.numel() != n or token.numel() != n:
+        raise ValueError("tok_offsets must be [vocab + 1], tok_kind [vocab], class_of [256], accept [n_states], "
+                         "state and token [n]")
+    if allowed_bits is not None:
+        _req(allowed_bits, torch.int32, "allowed_bits")
+        if allowed_bits.shape != (n, (vocab + 31) // 32):
+            raise ValueError("allowed_bits must be [n, ceil(vocab / 32)]")
+    _native.check(_native.load().crag_enc_grammar_argmax(
+        _p(logits), int(vocab), _p(tok_offsets), _p(tok_bytes), _p(tok_kind), _p(class_of), _p(trans), _p(accept),
+        int(n_states), int(n_classes), _p(state), _p(token), _p(allowed_bits), int(n), _stream()),
+        "crag_enc_grammar_argmax")
+    return token, state
+
+
 # -- continuing cached sequences (csrc/crag_extend.hip) ---------------------------------------------------------------
 def extend_workspace_bytes(n_seqs: int, hq: int, max_new_rows: int, max_len: int) -> int:
     """Bytes of scratch extend_attention needs at most for up to n_seqs sequences with up to max_new_rows new rows in

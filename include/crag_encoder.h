@@ -265,6 +265,34 @@ int crag_enc_extend_attention(const uint16_t *qkv_new, const uint16_t *q_norm_w,
                               int n_seqs, int hq, int hkv, float eps, float scale, void *workspace,
                               int64_t workspace_bytes, uint16_t *out, void *stream);
 
+/* ---- greedy selection under a byte automaton: csrc/crag_grammar.hip ----
+ *
+ * Serves the reference's Phase 5, item 2 (PHASED_PLAN.md: every sentence of an answer cites evidence ids of the pack):
+ * the decoder can only produce token sequences whose bytes a deterministic byte automaton accepts.
+ *
+ * The automaton: class_of [256] (byte -> class < n_classes), trans [n_states, n_classes] uint16 (the next state;
+ *   CRAG_GRAMMAR_DEAD = no way on), accept [n_states] (non-zero: a stop token is allowed here).
+ * The tokens: tok_offsets [vocab + 1] into tok_bytes (the raw bytes of every id, back to back), tok_kind [vocab]:
+ *   0 an ordinary token, walked byte by byte; 1 a stop token; 2 never allowed.
+ * crag_enc_grammar_argmax: per row r < n_rows (1..CRAG_DECODE_MAX_SEQS), with s = state[r] (device, in/out): token t
+ *   is allowed when kind[t] == 1 and accept[s], or kind[t] == 0, t has at least one byte and the walk of its bytes
+ *   from s never meets CRAG_GRAMMAR_DEAD (nor an index outside the tables).  token[r] = the lowest id among the maxima
+ *   of logits[r] ([n_rows, vocab] fp32) over the allowed tokens, NaNs left out -- crag_enc_lm_head's tie rule -- and
+ *   state[r] becomes the end state of its walk (unchanged for a stop token).  Nothing allowed, or s outside
+ *   0..n_states - 1: token[r] = -1, state[r] unchanged.  allowed_bits (nullable) [n_rows, ceil(vocab / 32)]: bit
+ *   t % 32 of word t / 32 is the allowed flag of token t, the bits at and beyond vocab zero.
+ *   One workgroup per row; no atomics; a row's results depend on its own logits and state alone.
+ *   CRAG_EINVAL, nothing enqueued: a NULL pointer (allowed_bits excepted), n_rows outside 1..8, n_states outside
+ *   1..CRAG_GRAMMAR_MAX_STATES, n_classes outside 1..CRAG_GRAMMAR_MAX_CLASSES, vocab outside 1..2^31 - 1, a pointer
+ *   that is not aligned to its element. */
+#define CRAG_GRAMMAR_MAX_STATES 4096
+#define CRAG_GRAMMAR_MAX_CLASSES 64
+#define CRAG_GRAMMAR_DEAD 0xFFFF
+int crag_enc_grammar_argmax(const float *logits, int64_t vocab, const int32_t *tok_offsets, const uint8_t *tok_bytes,
+                            const uint8_t *tok_kind, const uint8_t *class_of, const uint16_t *trans, const uint8_t *accept,
+                            int n_states, int n_classes, int32_t *state, int32_t *token, uint32_t *allowed_bits, int n_rows,
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif
