@@ -38,6 +38,8 @@ CRAG_EXTEND_SPLIT_ROWS = 512
 CRAG_GRAMMAR_MAX_STATES = 4096
 CRAG_GRAMMAR_MAX_CLASSES = 64
 CRAG_GRAMMAR_DEAD = 0xFFFF
+CRAG_SAMPLE_MIN_TEMPERATURE = 0.01
+CRAG_SAMPLE_MAX_TEMPERATURE = 100.0
 
 # every symbol include/crag_dense.h declares: name -> (restype, argtypes)
 _c = ctypes
@@ -138,6 +140,8 @@ SIGNATURES = {
                                              _c.c_int, _c.c_int, _c.c_float, _c.c_float, _P, _c.c_int64, _P, _P]),
     "crag_enc_grammar_argmax": (_c.c_int, [_P, _c.c_int64, _P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _c.c_int,
                                            _P]),
+    "crag_enc_sample": (_c.c_int, [_P, _c.c_int64, _P, _P, _P, _P, _P, _P, _c.c_uint64, _c.c_uint32, _P, _P, _P, _c.c_int, _P]),
+    "crag_enc_grammar_advance": (_c.c_int, [_P, _P, _P, _c.c_int64, _P, _P, _c.c_int, _c.c_int, _P, _P, _c.c_int, _P]),
 }
 
 

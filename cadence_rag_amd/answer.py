@@ -9,6 +9,11 @@ The gate: every sentence of an answer must cite at least one evidence id of the 
 evidence_id format retrieve._pack emits).  An answer that fails is sent back with the validator's report at most
 ANSWER_MAX_REPAIRS times; if it still fails, the response carries no answer.  No uncited sentence ever leaves.
 
+Sampling (cadence_rag_amd.sampling): a request's temperature / top_p / top_k / min_p / seed, over the ANSWER_* defaults.
+With a temperature of 0 and no such field in the request nothing changes: greedy decoding, the same HTTP body, the same
+notes.  Otherwise a native model with supports_sampling draws every token on the GPU (crag_enc_sample), an HTTP service
+gets temperature, top_p and seed, notes.sampling echoes the parameters, and repair round i draws on noise stream i.
+
 ANSWER_CONSTRAINED (native backend, a model with supports_grammar): the reply is decoded under the citation grammar of
 the evidence ids in the prompt (cadence_rag_amd.grammar.citation_grammar), which makes a failing answer unrepresentable
 whenever the model stops by itself.  The gate and the repair loop run unchanged on whatever comes back.
@@ -24,6 +29,7 @@ from . import retrieve as _retrieve
 from .config import settings
 from .grammar import INSUFFICIENT as _INSUFFICIENT_BYTES
 from .grammar import TokenGrammar, citation_grammar
+from .sampling import SamplingParams
 
 INSUFFICIENT = _INSUFFICIENT_BYTES.decode("ascii")   # "INSUFFICIENT_EVIDENCE": one definition, the grammar's
 STATUS_OK = "ok"
@@ -41,13 +47,18 @@ class AnswerClientError(RuntimeError):
     pass
 
 
+class AnswerRequestError(ValueError):
+    """The request itself is wrong (a sampling parameter out of range): nothing was retrieved or generated."""
+
+
 class ChatModel(Protocol):
     """In-process backend: a chat (list of {"role", "content"}) -> the assistant's reply.  A ValueError means the prompt
     does not fit the context (the caller drops evidence and retries); any other exception is reported as
     AnswerClientError.  `model_id` names the model.
     Optional: a model whose class sets `supports_grammar = True` also takes `generate_text(messages, max_new_tokens,
     grammar=TokenGrammar)` and decodes only what grammar.dfa accepts; its `token_table()`, if it has one, is the cached
-    byte table of its vocabulary that goes into the TokenGrammar.  The keyword is passed only to such a model."""
+    byte table of its vocabulary that goes into the TokenGrammar.  The keyword is passed only to such a model.
+    Optional: a model whose class sets `supports_sampling = True` also takes `sampling=SamplingParams, stream=int`."""
 
     model_id: str
 
@@ -142,12 +153,15 @@ def _post_json(url: str, headers: Dict[str, str], body: Dict[str, Any], timeout_
     return resp.status_code, resp.text
 
 
-def _chat_http(messages: List[Dict[str, str]], max_new_tokens: int) -> Tuple[str, str]:
+def _chat_http(messages: List[Dict[str, str]], max_new_tokens: int, sampling: Optional[SamplingParams] = None
+               ) -> Tuple[str, str]:
     import json
 
     url = settings.llm_base_url.rstrip("/") + "/chat/completions"
     headers = {"Authorization": f"Bearer {settings.llm_api_key}"} if settings.llm_api_key else {}
     body = {"model": settings.llm_model, "messages": messages, "temperature": 0, "max_tokens": int(max_new_tokens)}
+    if sampling is not None:   # the three knobs every OpenAI-compatible service knows
+        body.update(temperature=float(sampling.temperature), top_p=float(sampling.top_p), seed=int(sampling.seed))
     status, text = _post_json(url, headers, body, settings.llm_timeout_s)
     if status != 200:
         raise AnswerClientError(f"LLM service returned {status}: {text.strip()[:400]}")
@@ -161,18 +175,18 @@ def _chat_http(messages: List[Dict[str, str]], max_new_tokens: int) -> Tuple[str
     return content, str(payload.get("model") or settings.llm_model)
 
 
-def _chat_native(messages: List[Dict[str, str]], max_new_tokens: int, grammar: Optional[TokenGrammar] = None
-                 ) -> Tuple[str, str]:
+def _chat_native(messages: List[Dict[str, str]], max_new_tokens: int, grammar: Optional[TokenGrammar] = None,
+                 sampling: Optional[SamplingParams] = None, stream: int = 0) -> Tuple[str, str]:
     """ValueError (the prompt does not fit) passes through to the caller, which drops evidence."""
     llm = _llm
     if llm is None:
         raise AnswerClientError("native LLM is not loaded (call set_llm)")
     try:
         with _llm_lock:
-            if grammar is None:
-                text = llm.generate_text(messages, max_new_tokens)
-            else:
-                text = llm.generate_text(messages, max_new_tokens, grammar=grammar)
+            extra: Dict[str, Any] = {} if grammar is None else {"grammar": grammar}
+            if sampling is not None:
+                extra.update(sampling=sampling, stream=int(stream))
+            text = llm.generate_text(messages, max_new_tokens, **extra)
     except (AnswerClientError, ValueError):
         raise
     except Exception as exc:  # noqa: BLE001 - callers rely on a single error type
@@ -182,21 +196,43 @@ def _chat_native(messages: List[Dict[str, str]], max_new_tokens: int, grammar: O
     return text, str(getattr(llm, "model_id", None) or settings.llm_model)
 
 
-def chat(messages: List[Dict[str, str]], max_new_tokens: Optional[int] = None, grammar: Optional[TokenGrammar] = None
-         ) -> Tuple[str, str]:
-    """(reply, model id) from the configured LLM.  grammar: native backend only (an HTTP service cannot take one)."""
+def chat(messages: List[Dict[str, str]], max_new_tokens: Optional[int] = None, grammar: Optional[TokenGrammar] = None,
+         sampling: Optional[SamplingParams] = None, stream: int = 0) -> Tuple[str, str]:
+    """(reply, model id) from the configured LLM.  grammar: native backend only (an HTTP service cannot take one).
+    sampling: None is greedy; a native model must have supports_sampling (native_sampling()), and draws on noise stream
+    `stream`; an HTTP service gets temperature, top_p and seed."""
     if not llm_enabled():
         raise AnswerClientError("LLM_BASE_URL is not configured")
     budget = int(max_new_tokens or settings.llm_max_new_tokens)
     if _is_native(settings.llm_base_url):
-        return _chat_native(messages, budget, grammar)
-    return _chat_http(messages, budget)
+        return _chat_native(messages, budget, grammar, sampling, stream)
+    return _chat_http(messages, budget, sampling)
 
 
 def constrained_decoding() -> bool:
     """ANSWER_CONSTRAINED applies: it is on, the backend is native and the registered model takes a grammar."""
     return bool(settings.answer_constrained) and _is_native(settings.llm_base_url) \
         and bool(getattr(_llm, "supports_grammar", False))
+
+
+def native_sampling() -> bool:
+    """The registered native model takes sampling=SamplingParams."""
+    return bool(getattr(_llm, "supports_sampling", False))
+
+
+def sampling_for(request: Any) -> Optional[SamplingParams]:
+    """The request's sampling fields over the ANSWER_* defaults.  None -- greedy decoding, exactly as without sampling --
+    when the temperature comes out 0 and the request names no sampling field.  AnswerRequestError: a value out of range."""
+    given = {name: getattr(request, name, None) for name in ("temperature", "top_p", "top_k", "min_p", "seed")}
+    base = {"temperature": settings.answer_temperature, "top_p": settings.answer_top_p, "top_k": settings.answer_top_k,
+            "min_p": settings.answer_min_p, "seed": settings.answer_seed}
+    merged = {name: base[name] if value is None else value for name, value in given.items()}
+    if float(merged["temperature"]) == 0.0 and all(value is None for value in given.values()):
+        return None
+    try:
+        return SamplingParams(**merged)
+    except (TypeError, ValueError) as exc:
+        raise AnswerRequestError(str(exc)) from exc
 
 
 def _grammar_for(items: Sequence[Dict[str, Any]], notes: Dict[str, Any]) -> Optional[TokenGrammar]:
@@ -215,8 +251,13 @@ def _grammar_for(items: Sequence[Dict[str, Any]], notes: Dict[str, Any]) -> Opti
 # ---- /answer ----------------------------------------------------------------------------------------------------
 @dataclass
 class AnswerRequest(_retrieve.RetrieveRequest):
-    """The /retrieve request plus echo_evidence."""
+    """The /retrieve request plus echo_evidence and the optional sampling fields (None: the ANSWER_* default)."""
     echo_evidence: bool = False
+    temperature: Optional[float] = None
+    top_p: Optional[float] = None
+    top_k: Optional[int] = None
+    min_p: Optional[float] = None
+    seed: Optional[int] = None
 
 
 def _evidence_items(pack: Dict[str, Any]) -> List[Dict[str, Any]]:
@@ -252,6 +293,7 @@ def _repair_message(report: Dict[str, Any], ids: Sequence[str]) -> str:
 def answer_question(request: AnswerRequest, backend: Optional[_retrieve.RetrieveBackend] = None) -> Dict[str, Any]:
     if not llm_enabled():
         raise AnswerClientError("LLM_BASE_URL is not configured")
+    sampling = sampling_for(request)
     pack_request = _retrieve.RetrieveRequest(query=request.query, intent=request.intent, filters=request.filters,
                                              budget=request.budget, return_style="evidence_pack_json", debug=request.debug,
                                              facets=request.facets, facet_top=request.facet_top)
@@ -260,6 +302,11 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
     notes: Dict[str, Any] = {"evidence_items": len(items), "dropped_evidence": 0, "llm_calls": 0, "validator": None}
     if settings.answer_constrained:     # with the setting off the response is what it always was: no such note
         notes["constrained"] = False    # True once a call has decoded under a grammar
+    if sampling is not None:            # greedy by default: no such note
+        notes["sampling"] = sampling.echo()
+        if _is_native(settings.llm_base_url) and not native_sampling():
+            notes["sampling"]["applied"] = False   # the registered model cannot sample: it decodes greedily
+            sampling = None
     out: Dict[str, Any] = {"query_id": pack["query_id"], "answer": None, "status": STATUS_INSUFFICIENT, "citations": [],
                            "repairs": 0, "model": None, "notes": notes}
     if getattr(request, "echo_evidence", False):
@@ -272,12 +319,13 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
 
     constrained = constrained_decoding()
 
-    def call() -> str:
+    def call(attempt: int) -> str:
         while True:
             try:
                 # the grammar of the items in THIS prompt: rebuilt when an item has been dropped for length
                 grammar = _grammar_for(items, notes) if constrained else None
-                text, model = chat(build_messages(query, items, turns), grammar=grammar)
+                extra = {} if sampling is None else {"sampling": sampling, "stream": attempt}
+                text, model = chat(build_messages(query, items, turns), grammar=grammar, **extra)
             except ValueError as exc:   # the prompt does not fit the model's context: the lowest-ranked item goes
                 if len(items) <= 1:
                     raise AnswerClientError(f"the prompt does not fit with a single evidence item: {exc}") from exc
@@ -294,7 +342,7 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
 
     max_repairs = max(int(settings.answer_max_repairs), 0)
     for attempt in range(max_repairs + 1):
-        text = call().strip()
+        text = call(attempt).strip()
         out["repairs"] = attempt
         if text.strip(" .\"'`*") == INSUFFICIENT:
             out["status"] = STATUS_INSUFFICIENT

@@ -69,6 +69,13 @@ class Settings:
     # native LLM only: decode under the citation grammar of the evidence in the prompt (cadence_rag_amd.grammar), so that
     # an uncited sentence or an id outside the pack cannot be generated; the validator still checks what comes back
     answer_constrained: bool = False
+    # sampling defaults of /answer (cadence_rag_amd.sampling); a request's own temperature / top_p / top_k / min_p / seed
+    # override them.  Temperature 0 is greedy decoding: with these defaults /answer is what it was without sampling
+    answer_temperature: float = 0.0
+    answer_top_p: float = 1.0
+    answer_top_k: int = 0
+    answer_min_p: float = 0.0
+    answer_seed: int = 0
 
     def __post_init__(self) -> None:
         if self.rerank_device < 0:

@@ -8,11 +8,13 @@ kernels) with a full-vocabulary head -- the in-process LLM behind /answer (caden
                         logits over the whole vocabulary, greedy token).
   extend(token_lists)   m new tokens behind the n a slot already holds: prefill's layer loop over the new rows only, with
                         crag_enc_extend_attention (norm + RoPE, append, flash attention over the cache rows in place).
-  generate(...)         prefill + steps until a stop id or the token budget.  Greedy only.  With reuse_prefix=True a
-                        prompt that begins with what its slot holds (plan_reuse) keeps those rows and extends.  With a
+  generate(...)         prefill + steps until a stop id or the token budget.  Greedy, or with sampling=SamplingParams
+                        drawn on the device by crag_enc_sample (temperature, top-k, top-p, min-p; seeded).  With
+                        reuse_prefix=True a prompt that begins with what its slot holds (plan_reuse) keeps those rows and extends.  With a
                         grammar (cadence_rag_amd.grammar.TokenGrammar) every token is picked by crag_enc_grammar_argmax
                         among the tokens the sequence's automaton state allows, on the logits prefill / extend / step
-                        return; the states live on the device.
+                        return; the states live on the device.  Under a grammar a sampled token is drawn among the
+                        tokens the state allows, and crag_enc_grammar_advance moves the state behind it.
 
 The cache layout ([layer][slot][kv head][max_len][128] bf16, keys and values apart) sits behind KvCache.keys / .values.
 At most MAX_SEQS = 8 sequences decode at a time.
@@ -27,6 +29,7 @@ import torch
 import torch.nn.functional as F
 
 from ..grammar import KIND_STOP, TokenGrammar, TokenTable
+from ..sampling import SamplingParams
 from . import ops
 from .qwen3 import QKV_ROW_CHUNK, PackedBatch, Qwen3Config, Qwen3Encoder
 
@@ -86,6 +89,7 @@ class Qwen3Generator:
     """generate(prompts, max_new_tokens, stop_ids) -> new token ids of every prompt, on one GPU and one stream."""
 
     supports_grammar = True   # generate / generate_text take grammar=TokenGrammar (answer.py asks before passing one)
+    supports_sampling = True  # ... and sampling=SamplingParams
 
     def __init__(self, encoder: Qwen3Encoder, lm_head: torch.Tensor, tokenizer=None, *, max_context: Optional[int] = None,
                  max_seqs: int = MAX_SEQS, model_id: Optional[str] = None, prefix_cache: bool = False) -> None:
@@ -416,7 +420,8 @@ class Qwen3Generator:
 
     @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_ids: Sequence[int] = (),
-                 reuse_prefix: bool = False, grammar: Optional[TokenGrammar] = None) -> List[List[int]]:
+                 reuse_prefix: bool = False, grammar: Optional[TokenGrammar] = None,
+                 sampling=None, streams: Optional[Sequence[int]] = None) -> List[List[int]]:
         """Greedy continuation of every prompt (token ids): at most max_new_tokens ids each, ending before the first
         stop id.  A prompt longer than max_context - max_new_tokens raises PromptTooLong (a ValueError): the caller
         shortens its prompt, nothing is truncated here.
@@ -427,7 +432,13 @@ class Qwen3Generator:
         first one too -- is the greedy one among the tokens that state allows (ops.grammar_argmax).  A sequence then also
         ends at a stop token of the grammar's table, which the automaton allows in accepting states only, and at -1
         (nothing allowed).  last_grammar = {"accepted": [...]}: whether each sequence ended on such a stop token (None
-        without a grammar)."""
+        without a grammar).
+        sampling: a SamplingParams for every prompt, or one per prompt (all with one seed).  Token j of prompt b is then
+        drawn by ops.sample with step = j and stream = streams[b] (default b), the first on the logits prefill / extend
+        return and the later ones on step's; a temperature of 0 gives the greedy token.  Under a grammar the draw is
+        among the tokens the state allows: grammar_argmax hands out their bits (its own token is dropped and the state
+        it moved is discarded), sample draws under the bits, grammar_advance moves the state behind the drawn token.
+        None: greedy, the code path without sampling."""
         max_new_tokens = int(max_new_tokens)
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be positive")
@@ -443,6 +454,13 @@ class Qwen3Generator:
                 raise ValueError(f"the grammar's token table holds {table.vocab} ids, the model {self.cfg.vocab_size}")
             if len(prompts) > self.max_seqs:
                 raise ValueError(f"generate takes 1..{self.max_seqs} prompts")
+        if sampling is not None:
+            draws = [sampling] * len(prompts) if isinstance(sampling, SamplingParams) else list(sampling)
+            lanes = list(range(len(prompts))) if streams is None else [int(s) for s in streams]
+            if len(prompts) > self.max_seqs or len(draws) != len(prompts) or len(lanes) != len(prompts):
+                raise ValueError(f"sampling takes 1..{self.max_seqs} prompts, and one SamplingParams and one stream for each")
+            if len({int(d.seed) for d in draws}) > 1:
+                raise ValueError("the prompts of one call are drawn with one seed")
         keeps = [0] * len(prompts)
         if reuse_prefix and len(prompts) <= self.max_seqs:
             keeps = [plan_reuse(self.resident(b), p, PREFIX_MIN_REUSE) for b, p in enumerate(prompts)]
@@ -457,8 +475,15 @@ class Qwen3Generator:
         out: List[List[int]] = [[] for _ in prompts]
         live = list(range(len(prompts)))          # slot b holds prompt b
         accepted = [False] * len(prompts)
+        produced = 0     # tokens every live sequence has so far: the step of the next draw
+
+        def draw(rows: List[int], logits: torch.Tensor, bits: Optional[torch.Tensor] = None) -> torch.Tensor:
+            token = torch.empty(len(rows), dtype=torch.int32, device=self.device)
+            return ops.sample(logits, [draws[b] for b in rows], produced, [lanes[b] for b in rows], token,
+                              allowed_bits=bits)
+
         if grammar is None:
-            nxt = self.last_tokens.tolist()
+            nxt = self.last_tokens.tolist() if sampling is None else draw(live, logits).tolist()
         else:
             tables = table.to(self.device) + grammar.dfa.to(self.device)
             state = torch.full((len(prompts),), int(grammar.dfa.start), dtype=torch.int32, device=self.device)
@@ -468,7 +493,13 @@ class Qwen3Generator:
                 idx = torch.tensor(rows, dtype=torch.int64).to(self.device)
                 cur = state.index_select(0, idx)
                 token = torch.empty(len(rows), dtype=torch.int32, device=self.device)
-                ops.grammar_argmax(logits, *tables, cur, token)
+                if sampling is None:
+                    ops.grammar_argmax(logits, *tables, cur, token)
+                else:
+                    bits = torch.empty(len(rows), (table.vocab + 31) // 32, dtype=torch.int32, device=self.device)
+                    ops.grammar_argmax(logits, *tables, cur.clone(), token, allowed_bits=bits)
+                    token = draw(rows, logits, bits)
+                    ops.grammar_advance(*tables[:5], cur, token)
                 state.index_copy_(0, idx, cur)
                 return token.tolist()
 
@@ -490,14 +521,21 @@ class Qwen3Generator:
                 break
             self.live = list(live)
             token, logits = self.step(feed)
-            nxt = token.tolist() if grammar is None else select(live, logits)
+            produced += 1
+            if grammar is not None:
+                nxt = select(live, logits)
+            else:
+                nxt = token.tolist() if sampling is None else draw(live, logits).tolist()
         self.live = []
         self.last_grammar = {"accepted": accepted} if grammar is not None else None
         return out
 
     def generate_text(self, messages: Sequence[Dict[str, str]], max_new_tokens: int,
-                      grammar: Optional[TokenGrammar] = None) -> str:
-        """One chat -> the assistant's reply as text; under `grammar` when one is given (generate)."""
+                      grammar: Optional[TokenGrammar] = None, sampling: Optional[SamplingParams] = None,
+                      stream: int = 0) -> str:
+        """One chat -> the assistant's reply as text; under `grammar` when one is given, drawn with `sampling` on noise
+        stream `stream` when that is given (generate)."""
         ids = self.generate([self.chat_ids(messages)], max_new_tokens, self.stop_ids(),
-                            reuse_prefix=self.prefix_cache, grammar=grammar)[0]
+                            reuse_prefix=self.prefix_cache, grammar=grammar, sampling=sampling,
+                            streams=None if sampling is None else [int(stream)])[0]
         return self._tokenizer().decode(ids, skip_special_tokens=True)

@@ -396,6 +396,66 @@ def grammar_argmax(logits, tok_offsets, tok_bytes, tok_kind, class_of, trans, ac
     return token, state
 
 
+# -- seeded sampling (csrc/crag_sample.hip) -----------------------------------------------------------------------------
+def sample(logits, params, step: int, streams, token, allowed_bits=None, kept=None, cut=None):
+    """Per row of logits [n <= 8, vocab] fp32: token[r] (int32) drawn under params[r] (cadence_rag_amd.sampling
+    SamplingParams; one for all rows, or one per row -- every row then carries the same seed) with the noise of
+    (seed; token id, step, streams[r]) (crag_enc_sample; the rule: sampling.sample_host).  allowed_bits (optional)
+    [n, ceil(vocab / 32)] int32: grammar_argmax's flags, only set ids are candidates.  kept (optional) int32 [n] /
+    cut (optional) float32 [n] receive the number of ids the cuts keep and the lowest kept logit."""
+    from ..sampling import SamplingParams, min_p_cut
+    _req(logits, torch.float32, "logits"); _req(token, torch.int32, "token")
+    if logits.dim() != 2:
+        raise ValueError("logits must be [n, vocab]")
+    n, vocab = logits.shape
+    rows = [params] * n if isinstance(params, SamplingParams) else list(params)
+    streams = [int(s) for s in streams]
+    if len(rows) != n or len(streams) != n or token.numel() != n:
+        raise ValueError("params, streams and token need one entry per row")
+    if len({int(p.seed) for p in rows}) > 1:
+        raise ValueError("one call draws with one seed: every row's params must carry the same")
+    if allowed_bits is not None:
+        _req(allowed_bits, torch.int32, "allowed_bits")
+        if allowed_bits.shape != (n, (vocab + 31) // 32):
+            raise ValueError("allowed_bits must be [n, ceil(vocab / 32)]")
+    if kept is not None:
+        _req(kept, torch.int32, "kept")
+    if cut is not None:
+        _req(cut, torch.float32, "cut")
+    if (kept is not None and kept.numel() != n) or (cut is not None and cut.numel() != n):
+        raise ValueError("kept and cut must be [n]")
+    m = max(n, 1)
+    h_t = (ctypes.c_float * m)(*[float(p.temperature) for p in rows])
+    h_k = (ctypes.c_int32 * m)(*[int(p.top_k) for p in rows])
+    h_p = (ctypes.c_float * m)(*[float(p.top_p) for p in rows])
+    h_m = (ctypes.c_float * m)(*[float(min_p_cut(p.temperature, p.min_p)) for p in rows])
+    h_s = (ctypes.c_uint32 * m)(*[s & 0xFFFFFFFF for s in streams])
+    _native.check(_native.load().crag_enc_sample(
+        _p(logits), int(vocab), _p(allowed_bits), h_t, h_k, h_p, h_m, h_s, int(rows[0].seed) if rows else 0,
+        int(step) & 0xFFFFFFFF, _p(token), _p(kept), _p(cut), int(n), _stream()), "crag_enc_sample")
+    return token
+
+
+def grammar_advance(tok_offsets, tok_bytes, tok_kind, class_of, trans, state, token):
+    """state[r] (int32, device, in place) becomes the state behind token[r] (int32, device) walked from it; it stays for a
+    stop token, for -1 and for a token the state does not allow (crag_enc_grammar_advance).  The tables are
+    grammar_argmax's."""
+    _req(tok_offsets, torch.int32, "tok_offsets"); _req(tok_bytes, torch.uint8, "tok_bytes")
+    _req(tok_kind, torch.uint8, "tok_kind"); _req(class_of, torch.uint8, "class_of"); _req(trans, torch.int16, "trans")
+    _req(state, torch.int32, "state"); _req(token, torch.int32, "token")
+    if trans.dim() != 2:
+        raise ValueError("trans must be [n_states, n_classes]")
+    vocab = tok_kind.numel()
+    n_states, n_classes = trans.shape
+    n = state.numel()
+    if tok_offsets.numel() != vocab + 1 or class_of.numel() != 256 or token.numel() != n:
+        raise ValueError("tok_offsets must be [vocab + 1], class_of [256], state and token [n]")
+    _native.check(_native.load().crag_enc_grammar_advance(
+        _p(tok_offsets), _p(tok_bytes), _p(tok_kind), int(vocab), _p(class_of), _p(trans), int(n_states), int(n_classes),
+        _p(state), _p(token), int(n), _stream()), "crag_enc_grammar_advance")
+    return state
+
+
 # -- continuing cached sequences (csrc/crag_extend.hip) ---------------------------------------------------------------
 def extend_workspace_bytes(n_seqs: int, hq: int, max_new_rows: int, max_len: int) -> int:
     """Bytes of scratch extend_attention needs at most for up to n_seqs sequences with up to max_new_rows new rows in

@@ -149,13 +149,23 @@ def retrieve_endpoint(payload: RetrieveRequestModel) -> dict:
 
 class AnswerRequestModel(RetrieveRequestModel):
     echo_evidence: bool = False
+    # sampling (cadence_rag_amd.sampling): absent fields take the ANSWER_* defaults; a value out of range is a 422
+    temperature: Optional[float] = Field(default=None, ge=0.0, le=100.0)
+    top_p: Optional[float] = Field(default=None, gt=0.0, le=1.0)
+    top_k: Optional[int] = Field(default=None, ge=0)
+    min_p: Optional[float] = Field(default=None, ge=0.0, le=1.0)
+    seed: Optional[int] = Field(default=None, ge=0, lt=2 ** 64)
 
 
 @app.post("/answer")
 def answer_endpoint(payload: AnswerRequestModel) -> dict:
-    request = _answer.AnswerRequest(**_request_fields(payload), echo_evidence=payload.echo_evidence)
+    request = _answer.AnswerRequest(**_request_fields(payload), echo_evidence=payload.echo_evidence,
+                                    temperature=payload.temperature, top_p=payload.top_p, top_k=payload.top_k,
+                                    min_p=payload.min_p, seed=payload.seed)
     try:
         return _answer.answer_question(request)
+    except _answer.AnswerRequestError as exc:
+        raise HTTPException(status_code=422, detail=str(exc)) from exc
     except _answer.AnswerClientError as exc:
         raise HTTPException(status_code=502, detail=str(exc)) from exc
     except RuntimeError as exc:  # no retrieve backend registered

@@ -293,6 +293,46 @@ int crag_enc_grammar_argmax(const float *logits, int64_t vocab, const int32_t *t
                             int n_states, int n_classes, int32_t *state, int32_t *token, uint32_t *allowed_bits, int n_rows,
                             void *stream);
 
+/* ---- seeded sampling: csrc/crag_sample.hip ----
+ *
+ * crag_enc_sample: per row r < n_rows (1..CRAG_DECODE_MAX_SEQS) of logits [n_rows, vocab] fp32, one token drawn from the
+ *   row's softmax at temperature T = h_temperature[r] under the cuts h_top_k[r], h_top_p[r] and h_min_p_cut[r].  The h_*
+ *   arrays are HOST arrays of n_rows entries; seed and step hold for the whole call.
+ *   Candidates: the ids whose bit is set in allowed_bits[r] ([n_rows, ceil(vocab / 32)], crag_enc_grammar_argmax's layout;
+ *   NULL: every id) and whose logit is neither NaN nor -inf.  m = their maximum.
+ *     no candidate          token -1, kept 0, cut NaN
+ *     m == +inf, or T == 0  token = the lowest id holding m (crag_enc_lm_head's rule), kept = the ids holding m, cut = m
+ *   Otherwise every cut is a threshold on the logit, so equal logits stay together (-0 == +0):
+ *     t_k   the top_k-th largest candidate logit (top_k == 0, or no more candidates than top_k: none)
+ *     t_m   (l - m) >= min_p_cut in fp32; the host passes fp32(T * ln min_p), -inf for min_p == 0
+ *     t_p   inside S = {l >= t_k, t_m holds}, with w = exp((l - m) / T): the largest logit value such that the weights of
+ *           the logits >= t_p reach top_p of the weights of S (top_p == 1: none).  The weights are summed as 64-bit
+ *           fixed-point integers (unit 2^-40), so the sums do not depend on any order.
+ *   The kept ids are those of S at or above t_p; kept[r] (nullable) is their number and cut[r] (nullable) the lowest
+ *   kept logit.  The draw is the Gumbel maximum: u_i = ((x0 >> 8) + 0.5) * 2^-24 with x0 = word 0 of Philox4x32-10,
+ *   key (seed lo, seed hi), counter (i, step, h_stream[r], 0); key_i = (l_i - m) / T - ln(-ln u_i); token[r] = the kept
+ *   id with the largest key, the lowest id among equals.
+ *   One workgroup per row; integer atomics on LDS only; the same inputs give the same token, kept and cut bits on every
+ *   run, and a row's outputs depend on its own logits, bits and parameters alone -- not on n_rows or its position.
+ *   CRAG_EINVAL, nothing enqueued: a NULL pointer (allowed_bits, kept and cut excepted), n_rows outside 1..8, vocab
+ *   outside 1..2^31 - 1, a temperature that is neither 0 nor in CRAG_SAMPLE_MIN_TEMPERATURE..CRAG_SAMPLE_MAX_TEMPERATURE,
+ *   top_k outside 0..vocab, top_p outside (0, 1], min_p_cut > 0 or NaN, a device pointer not aligned to 4 bytes.
+ * crag_enc_grammar_advance: per row r < n_rows, one lane each: state[r] (device, in/out) becomes the state behind the
+ *   bytes of token[r] walked from it, with crag_enc_grammar_argmax's tables and its checks before every table read.
+ *   The state stays for a stop token, for -1, for an id outside 0..vocab - 1, for a state outside the table and for a
+ *   token the state does not allow (kind 2, no bytes, a walk that dies).  Under a grammar the decoder samples among
+ *   allowed_bits and then calls this: the state crag_enc_grammar_argmax leaves is the one behind ITS token.
+ *   CRAG_EINVAL, nothing enqueued: a NULL pointer, n_rows / n_states / n_classes / vocab outside their ranges (as
+ *   above), a pointer that is not aligned to its element. */
+#define CRAG_SAMPLE_MIN_TEMPERATURE 0.01f
+#define CRAG_SAMPLE_MAX_TEMPERATURE 100.0f
+int crag_enc_sample(const float *logits, int64_t vocab, const uint32_t *allowed_bits, const float *h_temperature,
+                    const int32_t *h_top_k, const float *h_top_p, const float *h_min_p_cut, const uint32_t *h_stream,
+                    uint64_t seed, uint32_t step, int32_t *token, int32_t *kept, float *cut, int n_rows, void *stream);
+int crag_enc_grammar_advance(const int32_t *tok_offsets, const uint8_t *tok_bytes, const uint8_t *tok_kind, int64_t vocab,
+                             const uint8_t *class_of, const uint16_t *trans, int n_states, int n_classes, int32_t *state,
+                             const int32_t *token, int n_rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
