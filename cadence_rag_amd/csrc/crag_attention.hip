@@ -51,15 +51,7 @@ constexpr int ATT_VROW = 40;    // u16 per staged V^T row (32 + 8 pad)
 constexpr int ATT_VROW2 = 72;   // u16 per staged V^T row of a 64-key pair (64 + 8 pad)
 
 // A lane holds keys 4h.. of ITS query row (c = lane & 31, h = lane >> 5): a row's 32 keys of a tile sit in lanes c and
-// c + 32.  The two half-waves are combined with v_permlane32_swap instead of an LDS-crossbar shuffle.
-__device__ __forceinline__ float halfwave_max(float v) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float halfwave_sum(float v) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
+// c + 32, combined by halfwave_max / halfwave_sum (crag_enc_common.h).
 
 // ---- 32 keys per iteration.  PREFIXED selects where a key tile is fetched from (the parent's tiles first, then the
 // sequence's own), how many tiles are walked and the mask; everything else is one text. ----

@@ -19,10 +19,6 @@
 
 namespace {
 
-struct alignas(16) Pack8 {
-    u16 v[8];
-};
-
 constexpr int DECODE_MAX_SEQS = CRAG_DECODE_MAX_SEQS;
 constexpr int DECODE_SPLIT = CRAG_DECODE_SPLIT;  // keys per workgroup of the split kernel
 constexpr int DECODE_THREADS = 256;              // 16 groups of 16 lanes: a group reads one 256-byte key / value row
@@ -50,66 +46,14 @@ struct DecodeParams {
     DecodeSeqs seqs;
 };
 
-__device__ __forceinline__ int64_t cache_row(const DecodeParams &p, int slot, int kvh, int pos) {
-    return (((int64_t)slot * p.hkv + kvh) * p.max_len + pos) * CRAG_HEAD_DIM;
-}
+static_assert(DECODE_THREADS == KV_APPEND_THREADS, "the prepare kernel is kv_append_row's workgroup");
 
-// ---------------------------------------------------------------------------------------------
-// prepare: one workgroup per sequence.  Per-head RMSNorm + rotate-half RoPE with the arithmetic and the lane layout of
-// qk_norm_rope_body (crag_encoder.hip): 16 lanes per head vector, 8 elements each, lane j pairs with lane j ^ 8.
-// q -> q_rot, k -> the cache row `len`, raw v -> the cache row `len`.
-// ---------------------------------------------------------------------------------------------
+// prepare: one workgroup per sequence appends the new token at position len (kv_append_row, crag_enc_common.h)
 __global__ __launch_bounds__(DECODE_THREADS) void decode_prepare_kernel(const DecodeParams p) {
     const int b = blockIdx.x;
     const int pos = p.seqs.len[b], slot = p.seqs.slot[b];
-    const int heads = p.hq + p.hkv;
-    const int64_t row_stride = (int64_t)(p.hq + 2 * p.hkv) * CRAG_HEAD_DIM;
-    const int g = threadIdx.x >> 4;
-    const int sub = threadIdx.x & 15;
-    const bool first_half = sub < 8;
-    const Pack8 wq8 = *reinterpret_cast<const Pack8 *>(p.qw + sub * 8);
-    const Pack8 wk8 = *reinterpret_cast<const Pack8 *>(p.kw + sub * 8);
-    const float *cs = p.cos_sin + ((int64_t)pos * 64 + (sub & 7) * 8) * 2;
-    float c[8], sn[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {  // the model casts cos/sin to bf16
-        c[e] = bf2f(f2bf(cs[2 * e]));
-        sn[e] = bf2f(f2bf(cs[2 * e + 1]));
-    }
-    const u16 *row = p.qkv_new + b * row_stride;
-    for (int hd = g; hd < heads; hd += DECODE_GROUPS) {
-        const Pack8 a = *reinterpret_cast<const Pack8 *>(row + (int64_t)hd * CRAG_HEAD_DIM + sub * 8);
-        const Pack8 &w8 = hd < p.hq ? wq8 : wk8;
-        float v[8];
-        float ss = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            v[e] = bf2f(a.v[e]);
-            ss += v[e] * v[e];
-        }
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o);  // 16-lane group
-        const float rstd = rsqrtf(ss / (float)CRAG_HEAD_DIM + p.eps);
-        float n[8], partner[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) n[e] = bf2f(f2bf(bf2f(w8.v[e]) * bf2f(f2bf(v[e] * rstd))));
-#pragma unroll
-        for (int e = 0; e < 8; ++e) partner[e] = __shfl_xor(n[e], 8);  // rotate_half: element i <-> i + 64
-        Pack8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float rot = first_half ? -partner[e] : partner[e];
-            o.v[e] = f2bf(n[e] * c[e] + rot * sn[e]);
-        }
-        u16 *dst = hd < p.hq ? p.q_rot + ((int64_t)b * p.hq + hd) * CRAG_HEAD_DIM
-                             : p.k_cache + cache_row(p, slot, hd - p.hq, pos);
-        *reinterpret_cast<Pack8 *>(dst + sub * 8) = o;
-    }
-    for (int i = threadIdx.x; i < p.hkv * 16; i += DECODE_THREADS) {
-        const int kvh = i >> 4, ch = i & 15;
-        *reinterpret_cast<Pack8 *>(p.v_cache + cache_row(p, slot, kvh, pos) + ch * 8) =
-            *reinterpret_cast<const Pack8 *>(row + (int64_t)(heads + kvh) * CRAG_HEAD_DIM + ch * 8);
-    }
+    kv_append_row(p.qkv_new + b * (int64_t)(p.hq + 2 * p.hkv) * CRAG_HEAD_DIM, p.qw, p.kw, p.cos_sin, p.k_cache, p.v_cache,
+                  p.q_rot + (int64_t)b * p.hq * CRAG_HEAD_DIM, p.hq, p.hkv, p.max_len, slot, pos, p.eps);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -128,8 +72,8 @@ __global__ __launch_bounds__(DECODE_THREADS) void decode_split_kernel(const Deco
     if (k0 >= n_keys) return;               // (uniform)
     const int slot = p.seqs.slot[b];
     const int grp = threadIdx.x >> 4, sub = threadIdx.x & 15;
-    const u16 *kc = p.k_cache + cache_row(p, slot, kvh, 0);
-    const u16 *vc = p.v_cache + cache_row(p, slot, kvh, 0);
+    const u16 *kc = p.k_cache + kv_row(p.hkv, p.max_len, slot, kvh, 0);
+    const u16 *vc = p.v_cache + kv_row(p.hkv, p.max_len, slot, kvh, 0);
 
     float q[G][8];
 #pragma unroll
@@ -322,10 +266,6 @@ __global__ __launch_bounds__(LM_THREADS) void lm_head_kernel(const u16 *hs, cons
 // is left.  One workgroup per row; a thread walks its ids in ascending order, the threads are merged on (value, id).
 constexpr int ARGMAX_THREADS = 1024;
 
-__device__ __forceinline__ bool better(float v, int id, float bv, int bid) {
-    return bid < 0 || v > bv || (v == bv && id < bid);
-}
-
 __global__ __launch_bounds__(ARGMAX_THREADS) void lm_argmax_kernel(const float *logits, int64_t vocab, const int32_t *banned,
                                                                    int n_banned, int32_t *token) {
     __shared__ float sv[ARGMAX_THREADS / 64];
@@ -343,28 +283,8 @@ __global__ __launch_bounds__(ARGMAX_THREADS) void lm_argmax_kernel(const float *
             bid = (int)i;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o);
-        const int oi = __shfl_xor(bid, o);
-        if (oi >= 0 && better(ov, oi, bv, bid)) {
-            bv = ov;
-            bid = oi;
-        }
-    }
-    if ((threadIdx.x & 63) == 0) {
-        sv[threadIdx.x >> 6] = bv;
-        si[threadIdx.x >> 6] = bid;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < ARGMAX_THREADS / 64; ++k)
-            if (si[k] >= 0 && better(sv[k], si[k], bv, bid)) {
-                bv = sv[k];
-                bid = si[k];
-            }
-        token[blockIdx.x] = bid;
-    }
+    const Best best = block_best<ARGMAX_THREADS / 64, false>(bv, bid, 0, sv, si, nullptr);
+    if (threadIdx.x == 0) token[blockIdx.x] = best.id;
 }
 
 }  // namespace

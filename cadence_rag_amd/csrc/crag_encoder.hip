@@ -13,10 +13,6 @@
 
 namespace {
 
-struct alignas(16) Pack8 {
-    u16 v[8];
-};
-
 // ---------------------------------------------------------------------------------------------
 // embedding gather
 // ---------------------------------------------------------------------------------------------
@@ -87,9 +83,8 @@ __global__ __launch_bounds__(NORM_THREADS) void rmsnorm_kernel(const u16 *x, con
 }
 
 // ---------------------------------------------------------------------------------------------
-// per-head q/k RMSNorm + RoPE, in place on the fused qkv rows
-// 16 lanes per head vector (8 elements each); lane j of the group pairs with lane j^8 for
-// rotate_half (element i <-> i + 64)
+// per-head q/k RMSNorm + RoPE, in place on the fused qkv rows (norm_rope_chunk, crag_enc_common.h: 16 lanes per head
+// vector, 8 elements each)
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ void qk_norm_rope_body(u16 *qkv, const u16 *qw, const u16 *kw, const float *cos_sin,
                                                   const int32_t *positions, int64_t n_tokens, int hq, int hkv,
@@ -105,40 +100,12 @@ __device__ __forceinline__ void qk_norm_rope_body(u16 *qkv, const u16 *qw, const
     const Pack8 wq8 = *reinterpret_cast<const Pack8 *>(qw + sub * 8);
     const Pack8 wk8 = *reinterpret_cast<const Pack8 *>(kw + sub * 8);
     for (int64_t t = first_token; t < n_tokens; t += token_stride) {
-        const int pos = positions[t];
-        const float *cs = cos_sin + ((int64_t)pos * 64 + (sub & 7) * 8) * 2;
         float c[8], sn[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {  // the model casts cos/sin to bf16
-            c[e] = bf2f(f2bf(cs[2 * e]));
-            sn[e] = bf2f(f2bf(cs[2 * e + 1]));
-        }
+        rope_chunk(cos_sin, positions[t], sub, c, sn);
         for (int hd = g; hd < heads; hd += 16) {
             u16 *p = qkv + t * row_stride + (int64_t)hd * CRAG_HEAD_DIM + sub * 8;
             const Pack8 a = *reinterpret_cast<Pack8 *>(p);
-            const Pack8 &w8 = hd < hq ? wq8 : wk8;
-            float v[8];
-            float ss = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                v[e] = bf2f(a.v[e]);
-                ss += v[e] * v[e];
-            }
-#pragma unroll
-            for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o);  // 16-lane group
-            const float rstd = rsqrtf(ss / (float)CRAG_HEAD_DIM + eps);
-            float n[8], partner[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) n[e] = bf2f(f2bf(bf2f(w8.v[e]) * bf2f(f2bf(v[e] * rstd))));
-#pragma unroll
-            for (int e = 0; e < 8; ++e) partner[e] = __shfl_xor(n[e], 8);  // rotate_half: element i <-> i + 64
-            Pack8 o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float rot = first_half ? -partner[e] : partner[e];
-                o.v[e] = f2bf(n[e] * c[e] + rot * sn[e]);
-            }
-            *reinterpret_cast<Pack8 *>(p) = o;
+            *reinterpret_cast<Pack8 *>(p) = norm_rope_chunk(a, hd < hq ? wq8 : wk8, c, sn, first_half, eps);
         }
     }
 }

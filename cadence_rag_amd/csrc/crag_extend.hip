@@ -34,10 +34,6 @@
 
 namespace {
 
-struct alignas(16) Pack8 {
-    u16 v[8];
-};
-
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int EXTEND_MAX_SEQS = CRAG_DECODE_MAX_SEQS;
@@ -49,8 +45,8 @@ constexpr int SPLIT_TILES = EXTEND_SPLIT / EXTEND_TILE;
 constexpr int PART_O = EXTEND_BLOCK * CRAG_HEAD_DIM;   // floats of one partial o: (query block, head, split)
 constexpr int PART_ML = EXTEND_BLOCK * 2;              // floats of its (m, l) pairs
 static_assert(EXTEND_SPLIT % EXTEND_TILE == 0, "a split is whole tiles");
-constexpr int PREP_THREADS = 256;                 // 16 groups of 16 lanes: a group norms and rotates one head vector
-constexpr int PREP_GROUPS = PREP_THREADS / 16;
+constexpr int PREP_THREADS = 256;
+static_assert(PREP_THREADS == KV_APPEND_THREADS, "the prepare kernel is kv_append_row's workgroup");
 constexpr int EXT_KROW = 136;                     // u16 per staged K row (128 + 8 pad: conflict-free ds_read_b128)
 constexpr int EXT_VROW = 160;                     // u16 per staged V row (128 + 32 pad: conflict-free transposed reads)
 static_assert(EXTEND_BLOCK == 32 && EXTEND_TILE == 32, "the MFMA maps below are those of 32 x 32 tiles");
@@ -80,78 +76,14 @@ struct ExtendParams {
     ExtendSeqs seqs;
 };
 
-__device__ __forceinline__ int64_t cache_row(const ExtendParams &p, int slot, int kvh, int pos) {
-    return (((int64_t)slot * p.hkv + kvh) * p.max_len + pos) * CRAG_HEAD_DIM;
-}
-
-// ---------------------------------------------------------------------------------------------
-// prepare: one workgroup per (new row, sequence).  decode_prepare_kernel's body (crag_decode.hip), itself
-// qk_norm_rope_body's arithmetic and lane layout: 16 lanes per head vector, 8 elements each, lane j pairs with lane
-// j ^ 8.  q -> q_rot, k -> cache row len + i, raw v -> cache row len + i.
-// ---------------------------------------------------------------------------------------------
+// prepare: one workgroup per (new row, sequence) appends row i at position len + i (kv_append_row, crag_enc_common.h)
 __global__ __launch_bounds__(PREP_THREADS) void extend_prepare_kernel(const ExtendParams p) {
     const int i = blockIdx.x, b = blockIdx.y;
     if (i >= p.seqs.n_new[b]) return;   // (uniform)
     const int pos = p.seqs.len[b] + i, slot = p.seqs.slot[b];
     const int64_t t = (int64_t)p.seqs.row0[b] + i;
-    const int heads = p.hq + p.hkv;
-    const int64_t row_stride = (int64_t)(p.hq + 2 * p.hkv) * CRAG_HEAD_DIM;
-    const int g = threadIdx.x >> 4;
-    const int sub = threadIdx.x & 15;
-    const bool first_half = sub < 8;
-    const Pack8 wq8 = *reinterpret_cast<const Pack8 *>(p.qw + sub * 8);
-    const Pack8 wk8 = *reinterpret_cast<const Pack8 *>(p.kw + sub * 8);
-    const float *cs = p.cos_sin + ((int64_t)pos * 64 + (sub & 7) * 8) * 2;
-    float c[8], sn[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {  // the model casts cos/sin to bf16
-        c[e] = bf2f(f2bf(cs[2 * e]));
-        sn[e] = bf2f(f2bf(cs[2 * e + 1]));
-    }
-    const u16 *row = p.qkv_new + t * row_stride;
-    for (int hd = g; hd < heads; hd += PREP_GROUPS) {
-        const Pack8 a = *reinterpret_cast<const Pack8 *>(row + (int64_t)hd * CRAG_HEAD_DIM + sub * 8);
-        const Pack8 &w8 = hd < p.hq ? wq8 : wk8;
-        float v[8];
-        float ss = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            v[e] = bf2f(a.v[e]);
-            ss += v[e] * v[e];
-        }
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o);  // 16-lane group
-        const float rstd = rsqrtf(ss / (float)CRAG_HEAD_DIM + p.eps);
-        float n[8], partner[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) n[e] = bf2f(f2bf(bf2f(w8.v[e]) * bf2f(f2bf(v[e] * rstd))));
-#pragma unroll
-        for (int e = 0; e < 8; ++e) partner[e] = __shfl_xor(n[e], 8);  // rotate_half: element i <-> i + 64
-        Pack8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float rot = first_half ? -partner[e] : partner[e];
-            o.v[e] = f2bf(n[e] * c[e] + rot * sn[e]);
-        }
-        u16 *dst = hd < p.hq ? p.q_rot + (t * p.hq + hd) * CRAG_HEAD_DIM : p.k_cache + cache_row(p, slot, hd - p.hq, pos);
-        *reinterpret_cast<Pack8 *>(dst + sub * 8) = o;
-    }
-    for (int j = threadIdx.x; j < p.hkv * 16; j += PREP_THREADS) {
-        const int kvh = j >> 4, ch = j & 15;
-        *reinterpret_cast<Pack8 *>(p.v_cache + cache_row(p, slot, kvh, pos) + ch * 8) =
-            *reinterpret_cast<const Pack8 *>(row + (int64_t)(heads + kvh) * CRAG_HEAD_DIM + ch * 8);
-    }
-}
-
-// A lane holds keys 4h.. of ITS query row (c = lane & 31, h = lane >> 5): a row's 32 keys of a tile sit in lanes c and
-// c + 32 (crag_attention.hip).
-__device__ __forceinline__ float halfwave_max(float v) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float halfwave_sum(float v) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    kv_append_row(p.qkv_new + t * (p.hq + 2 * p.hkv) * CRAG_HEAD_DIM, p.qw, p.kw, p.cos_sin, p.k_cache, p.v_cache,
+                  p.q_rot + t * p.hq * CRAG_HEAD_DIM, p.hq, p.hkv, p.max_len, slot, pos, p.eps);
 }
 
 // ds_read_b64_tr_b16: the 16 lanes of a group name a block of 4 rows x 16 columns (lane 4q + p: row q, columns 4p..) and
@@ -209,8 +141,8 @@ __global__ __launch_bounds__(64 * GROUP) void extend_attention_kernel(const Exte
     const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     f32x16 oacc[4] = {zero, zero, zero, zero};
     float m = -INFINITY, l = 0.f;
-    const u16 *kglob = p.k_cache + cache_row(p, p.seqs.slot[b], kvh, 0);
-    const u16 *vglob = p.v_cache + cache_row(p, p.seqs.slot[b], kvh, 0);
+    const u16 *kglob = p.k_cache + kv_row(p.hkv, p.max_len, p.seqs.slot[b], kvh, 0);
+    const u16 *vglob = p.v_cache + kv_row(p.hkv, p.max_len, p.seqs.slot[b], kvh, 0);
 
     // cooperative staging: a K tile and a V tile are 32 rows x 16 chunks of 16 B each; with `nthr` threads every
     // thread moves 512 / nthr chunks of each.  Rows at or beyond n_keys are not read: zeros take their place.

@@ -6,7 +6,7 @@
 //                             row's state, never reach the dead state.
 //
 // One workgroup per row, as lm_argmax_kernel (crag_decode.hip): a thread walks its ids in ascending order, so the
-// (value, id) merge of the threads gives the lowest id among equal maxima.  class_of sits in LDS; the transition table
+// (value, id) merge of the threads (block_best, crag_enc_common.h) gives the lowest id among equal maxima.  class_of sits in LDS; the transition table
 // too when it fits GRAMMAR_LDS_TRANS entries, otherwise it is read through the cache (two instantiations).  Without
 // allowed_bits a thread walks only a token whose logit beats its own best so far; with allowed_bits every token is
 // walked and a wave stores its 64 flags as two words (ballot; lanes 0 and 32 store).  Every store is a plain vector
@@ -38,11 +38,6 @@ struct GrammarParams {
     uint32_t *allowed_bits;
     int64_t n_words;
 };
-
-// lm_argmax_kernel's order: a higher value wins, equal values go to the lower id
-__device__ __forceinline__ bool better(float v, int id, float bv, int bid) {
-    return bid < 0 || v > bv || (v == bv && id < bid);
-}
 
 template <bool BITS, bool TRANS_LDS>
 __global__ __launch_bounds__(GRAMMAR_THREADS) void grammar_argmax_kernel(const GrammarParams p) {
@@ -103,32 +98,10 @@ __global__ __launch_bounds__(GRAMMAR_THREADS) void grammar_argmax_kernel(const G
                 p.allowed_bits[(int64_t)r * p.n_words + word + 1] = (uint32_t)(flags >> 32);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o);
-        const int oi = __shfl_xor(bid, o);
-        const int os = __shfl_xor(bstate, o);
-        if (oi >= 0 && better(ov, oi, bv, bid)) {
-            bv = ov;
-            bid = oi;
-            bstate = os;
-        }
-    }
-    if ((tid & 63) == 0) {
-        sv[tid >> 6] = bv;
-        si[tid >> 6] = bid;
-        ss[tid >> 6] = bstate;
-    }
-    __syncthreads();
+    const Best best = block_best<GRAMMAR_WAVES, true>(bv, bid, bstate, sv, si, ss);   // the end state travels with the winner
     if (tid == 0) {
-        for (int k = 1; k < GRAMMAR_WAVES; ++k)
-            if (si[k] >= 0 && better(sv[k], si[k], bv, bid)) {
-                bv = sv[k];
-                bid = si[k];
-                bstate = ss[k];
-            }
-        p.token[r] = bid;
-        if (bid >= 0) p.state[r] = bstate;   // nothing allowed: the state stays
+        p.token[r] = best.id;
+        if (best.id >= 0) p.state[r] = best.payload;   // nothing allowed: the state stays
     }
 }
 

@@ -114,10 +114,6 @@ __device__ __forceinline__ float gumbel(uint32_t x0) {
     return -logf(t);
 }
 
-__device__ __forceinline__ bool better(float v, int id, float bv, int bid) {
-    return bid < 0 || v > bv || (v == bv && id < bid);
-}
-
 __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(const SampleParams p) {
     __shared__ uint32_t s_cnt[SAMPLE_BINS];
     __shared__ u64 s_wq[SAMPLE_BINS];

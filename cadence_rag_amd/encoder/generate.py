@@ -6,9 +6,12 @@ kernels) with a full-vocabulary head -- the in-process LLM behind /answer (caden
   step(tokens)          one new token per live sequence: per layer qkv, crag_enc_decode_attention (q/k-norm + RoPE of
                         the new row, append, attention over the cache), o, MLP; then crag_enc_lm_head (final norm, fp32
                         logits over the whole vocabulary, greedy token).
-  extend(token_lists)   m new tokens behind the n a slot already holds: prefill's layer loop over the new rows only, with
+  extend(token_lists)   m new tokens behind the n a slot already holds: the new rows only, with
                         crag_enc_extend_attention (norm + RoPE, append, flash attention over the cache rows in place).
-  generate(...)         prefill + steps until a stop id or the token budget.  Greedy, or with sampling=SamplingParams
+                        prefill, extend and step's library branch share one layer loop (_layers) and hand it their own
+                        qkv projection + attention; step's small_gemm branch (the 4B widths) is a layer of its own.
+  generate(...)         prefill + steps until a stop id or the token budget; every token comes from one _Picker, built
+                        per call, which hides the four selection modes.  Greedy, or with sampling=SamplingParams
                         drawn on the device by crag_enc_sample (temperature, top-k, top-p, min-p; seeded).  With
                         reuse_prefix=True a prompt that begins with what its slot holds (plan_reuse) keeps those rows and extends.  With a
                         grammar (cadence_rag_amd.grammar.TokenGrammar) every token is picked by crag_enc_grammar_argmax
@@ -83,6 +86,54 @@ class KvCache:
         n = k_rows.shape[0]
         self.k[layer, slot, :, :n].copy_(k_rows.transpose(0, 1))
         self.v[layer, slot, :, :n].copy_(v_rows.transpose(0, 1))
+
+
+class _Picker:
+    """The token selection of one generate() call over n prompts.  pick(rows, logits, greedy_tokens, step) -> the next
+    token of the sequences `rows` (logits [len(rows), vocab]): greedy_tokens as they are (nothing is launched), drawn
+    by ops.sample, the allowed greedy one by ops.grammar_argmax, or drawn among the allowed ones.  It holds the draws and
+    streams per prompt, and under a grammar the tables and every prompt's automaton state on the device."""
+
+    def __init__(self, gen: "Qwen3Generator", n: int, grammar: Optional[TokenGrammar], sampling, streams) -> None:
+        self.device = gen.device
+        self.table = self.draws = None
+        if grammar is not None:
+            self.table = grammar.table if grammar.table is not None else gen.token_table()
+            if self.table.vocab != gen.cfg.vocab_size:
+                raise ValueError(f"the grammar's token table holds {self.table.vocab} ids, the model {gen.cfg.vocab_size}")
+            if n > gen.max_seqs:
+                raise ValueError(f"generate takes 1..{gen.max_seqs} prompts")
+        if sampling is not None:
+            self.draws = [sampling] * n if isinstance(sampling, SamplingParams) else list(sampling)
+            self.lanes = list(range(n)) if streams is None else [int(s) for s in streams]
+            if n > gen.max_seqs or len(self.draws) != n or len(self.lanes) != n:
+                raise ValueError(f"sampling takes 1..{gen.max_seqs} prompts, and one SamplingParams and one stream for each")
+            if len({int(d.seed) for d in self.draws}) > 1:
+                raise ValueError("the prompts of one call are drawn with one seed")
+        if grammar is not None:
+            self.tables = self.table.to(self.device) + grammar.dfa.to(self.device)
+            self.state = torch.full((n,), int(grammar.dfa.start), dtype=torch.int32, device=self.device)
+
+    def _draw(self, rows: List[int], logits: torch.Tensor, step: int, bits: Optional[torch.Tensor] = None) -> torch.Tensor:
+        token = torch.empty(len(rows), dtype=torch.int32, device=self.device)
+        return ops.sample(logits, [self.draws[b] for b in rows], step, [self.lanes[b] for b in rows], token,
+                          allowed_bits=bits)
+
+    def __call__(self, rows: List[int], logits: torch.Tensor, greedy_tokens: torch.Tensor, step: int) -> List[int]:
+        if self.table is None:
+            return (greedy_tokens if self.draws is None else self._draw(rows, logits, step)).tolist()
+        idx = torch.tensor(rows, dtype=torch.int64).to(self.device)
+        cur = self.state.index_select(0, idx)      # the states of `rows`: they move on behind the chosen tokens
+        token = torch.empty(len(rows), dtype=torch.int32, device=self.device)
+        if self.draws is None:
+            ops.grammar_argmax(logits, *self.tables, cur, token)
+        else:   # grammar_argmax hands out the bits on a copy of the states; its own token is dropped
+            bits = torch.empty(len(rows), (self.table.vocab + 31) // 32, dtype=torch.int32, device=self.device)
+            ops.grammar_argmax(logits, *self.tables, cur.clone(), token, allowed_bits=bits)
+            token = self._draw(rows, logits, step, bits)
+            ops.grammar_advance(*self.tables[:5], cur, token)
+        self.state.index_copy_(0, idx, cur)
+        return token.tolist()
 
 
 class Qwen3Generator:
@@ -207,43 +258,61 @@ class Qwen3Generator:
                     banned=banned)
         return logits, token
 
+    def _check_slots(self, what: str, n: int, slots: Optional[Sequence[int]]) -> List[int]:
+        slots = list(range(n)) if slots is None else [int(s) for s in slots]
+        if not 1 <= n <= self.max_seqs or len(slots) != n or len(set(slots)) != n or \
+                any(not 0 <= s < self.max_seqs for s in slots):
+            raise ValueError(what % self.max_seqs)
+        return slots
+
+    def _embed(self, token_lists: Sequence[Sequence[int]]) -> torch.Tensor:
+        ids = torch.from_numpy(np.concatenate([np.asarray(tl, dtype=np.int32) for tl in token_lists])).to(self.device)
+        x = torch.empty(ids.numel(), self.cfg.hidden_size, dtype=torch.bfloat16, device=self.device)
+        ops.embed_gather(ids, self.encoder.embed, x)
+        return x
+
+    def _layers(self, x: torch.Tensor, project_and_attend) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The decoder layers over the embedded rows x with library GEMMs: rmsnorm, project_and_attend(i, L, normed) ->
+        the attention output [rows, q_size] (the caller's qkv projection and attention against layer i), o, rmsnorm,
+        gate_up, swiglu, down.  Returns (resid, delta): the hidden state is their sum."""
+        c = self.cfg
+        resid, normed = torch.empty_like(x), torch.empty_like(x)
+        act = torch.empty(x.shape[0], c.intermediate_size, dtype=x.dtype, device=x.device)
+        delta: Optional[torch.Tensor] = None
+        for i, L in enumerate(self.encoder.layers):
+            if i == 0:
+                ops.rmsnorm(x, L["ln1"], normed, c.rms_norm_eps, residual_in=None, residual_out=None)
+                resid.copy_(x)
+            else:
+                ops.rmsnorm(delta, L["ln1"], normed, c.rms_norm_eps, residual_in=resid, residual_out=resid)
+            delta = F.linear(project_and_attend(i, L, normed), L["o"])
+            ops.rmsnorm(delta, L["ln2"], normed, c.rms_norm_eps, residual_in=resid, residual_out=resid)
+            ops.swiglu(F.linear(normed, L["gate_up"]), act)
+            delta = F.linear(act, L["down"])
+        return resid, delta
+
     @torch.no_grad()
     def prefill(self, token_lists: Sequence[Sequence[int]], slots: Optional[Sequence[int]] = None) -> torch.Tensor:
         """Fills slot slots[b] (default b) with prompt b and makes these the live sequences.  Returns the last-token
         logits [n, vocab] fp32 on the device; .last_tokens holds their greedy tokens (int32 [n], device)."""
         c, enc, dev, bf = self.cfg, self.encoder, self.device, torch.bfloat16
-        n = len(token_lists)
-        slots = list(range(n)) if slots is None else [int(s) for s in slots]
-        if not 1 <= n <= self.max_seqs or len(slots) != n or len(set(slots)) != n or \
-                any(not 0 <= s < self.max_seqs for s in slots):
-            raise ValueError(f"prefill takes 1..{self.max_seqs} prompts, each in a slot of its own")
+        slots = self._check_slots("prefill takes 1..%d prompts, each in a slot of its own", len(token_lists), slots)
         lens = [len(tl) for tl in token_lists]
         if min(lens) <= 0:
             raise ValueError("every prompt needs at least one token")
         if max(lens) >= self.max_context:
             raise PromptTooLong(f"a prompt of {max(lens)} tokens leaves no room in a context of {self.max_context}")
         batch = PackedBatch.build(lens, dev)
-        ids = torch.from_numpy(np.concatenate([np.asarray(tl, dtype=np.int32) for tl in token_lists])).to(dev)
         t = batch.n_tokens
-        x = torch.empty(t, c.hidden_size, dtype=bf, device=dev)
-        ops.embed_gather(ids, enc.embed, x)
-        resid = torch.empty_like(x)
-        normed = torch.empty_like(x)
-        width = c.q_size + 2 * c.kv_size
-        qkv_buf = torch.zeros(t + 32, width, dtype=bf, device=dev)  # attention reads up to 31 rows past T
+        x = self._embed(token_lists)
+        qkv_buf = torch.zeros(t + 32, c.q_size + 2 * c.kv_size, dtype=bf, device=dev)  # attention reads up to 31 rows past T
         qkv = qkv_buf[:t]
         vt = torch.empty(c.num_kv_heads, c.head_dim, batch.t_pad, dtype=bf, device=dev)
         attn = torch.empty(t, c.q_size, dtype=bf, device=dev)
-        act = torch.empty(t, c.intermediate_size, dtype=bf, device=dev)
         scale = 1.0 / math.sqrt(c.head_dim)
         starts = np.concatenate([[0], np.cumsum(lens)])
-        delta: Optional[torch.Tensor] = None
-        for i, L in enumerate(enc.layers):
-            if i == 0:
-                ops.rmsnorm(x, L["ln1"], normed, c.rms_norm_eps, residual_in=None, residual_out=None)
-                resid.copy_(x)
-            else:
-                ops.rmsnorm(delta, L["ln1"], normed, c.rms_norm_eps, residual_in=resid, residual_out=resid)
+
+        def attend(i, L, normed):
             for lo in range(0, t, QKV_ROW_CHUNK):
                 hi = min(t, lo + QKV_ROW_CHUNK)
                 torch.matmul(normed[lo:hi], L["qkv"].t(), out=qkv[lo:hi])
@@ -255,10 +324,9 @@ class Qwen3Generator:
                                           rows[:, c.q_size + c.kv_size:].view(-1, c.num_kv_heads, 128))
             ops.attention(qkv_buf, vt, attn, batch.cu, batch.cu_pad, batch.blk_seq, batch.blk_q0, c.num_heads,
                           c.num_kv_heads, scale)
-            delta = F.linear(attn, L["o"])
-            ops.rmsnorm(delta, L["ln2"], normed, c.rms_norm_eps, residual_in=resid, residual_out=resid)
-            ops.swiglu(F.linear(normed, L["gate_up"]), act)
-            delta = F.linear(act, L["down"])
+            return attn
+
+        resid, delta = self._layers(x, attend)
         for slot, m, tl in zip(slots, lens, token_lists):
             self.cache.lens[slot] = m
             self.tokens[slot] = [int(x) for x in tl]
@@ -270,15 +338,12 @@ class Qwen3Generator:
     @torch.no_grad()
     def extend(self, token_lists: Sequence[Sequence[int]], slots: Optional[Sequence[int]] = None) -> torch.Tensor:
         """Appends token_lists[b] to slot slots[b] (default b) behind the cache.lens[slot] tokens it holds -- an empty
-        slot is allowed -- and makes these the live sequences.  prefill's layer loop over the new rows only, with
+        slot is allowed -- and makes these the live sequences.  prefill's layers over the new rows only, with
         crag_enc_extend_attention in the place of qk_rope_vt + the cache copies + the packed attention.  Returns the
         logits of every sequence's last new row [n, vocab] fp32 on the device; .last_tokens holds their greedy tokens."""
         c, enc, dev, bf = self.cfg, self.encoder, self.device, torch.bfloat16
         n = len(token_lists)
-        slots = list(range(n)) if slots is None else [int(s) for s in slots]
-        if not 1 <= n <= self.max_seqs or len(slots) != n or len(set(slots)) != n or \
-                any(not 0 <= s < self.max_seqs for s in slots):
-            raise ValueError(f"extend takes 1..{self.max_seqs} token lists, each for a slot of its own")
+        slots = self._check_slots("extend takes 1..%d token lists, each for a slot of its own", n, slots)
         news = [len(tl) for tl in token_lists]
         if min(news) <= 0:
             raise ValueError("every sequence needs at least one new token")
@@ -290,32 +355,20 @@ class Qwen3Generator:
         need = ops.extend_workspace_bytes(n, c.num_heads, t, full)   # the rotated queries, the key splits' partials
         if self._extend_ws is None or self._extend_ws.numel() < need:
             self._extend_ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        ids = torch.from_numpy(np.concatenate([np.asarray(tl, dtype=np.int32) for tl in token_lists])).to(dev)
-        x = torch.empty(t, c.hidden_size, dtype=bf, device=dev)
-        ops.embed_gather(ids, enc.embed, x)
-        resid = torch.empty_like(x)
-        normed = torch.empty_like(x)
+        x = self._embed(token_lists)
         qkv = torch.empty(t, c.q_size + 2 * c.kv_size, dtype=bf, device=dev)
         attn = torch.empty(t, c.q_size, dtype=bf, device=dev)
-        act = torch.empty(t, c.intermediate_size, dtype=bf, device=dev)
         scale = 1.0 / math.sqrt(c.head_dim)
-        delta: Optional[torch.Tensor] = None
-        for i, L in enumerate(enc.layers):
-            if i == 0:
-                ops.rmsnorm(x, L["ln1"], normed, c.rms_norm_eps, residual_in=None, residual_out=None)
-                resid.copy_(x)
-            else:
-                ops.rmsnorm(delta, L["ln1"], normed, c.rms_norm_eps, residual_in=resid, residual_out=resid)
+
+        def attend(i, L, normed):
             for lo in range(0, t, QKV_ROW_CHUNK):
                 hi = min(t, lo + QKV_ROW_CHUNK)
                 torch.matmul(normed[lo:hi], L["qkv"].t(), out=qkv[lo:hi])
-            kc, vc = self.cache.layer(i)
-            ops.extend_attention(qkv, L["q_norm"], L["k_norm"], enc._cos_sin, kc, vc, slots, held, news, attn,
+            ops.extend_attention(qkv, L["q_norm"], L["k_norm"], enc._cos_sin, *self.cache.layer(i), slots, held, news, attn,
                                  c.num_heads, c.num_kv_heads, c.rms_norm_eps, scale, self._extend_ws)
-            delta = F.linear(attn, L["o"])
-            ops.rmsnorm(delta, L["ln2"], normed, c.rms_norm_eps, residual_in=resid, residual_out=resid)
-            ops.swiglu(F.linear(normed, L["gate_up"]), act)
-            delta = F.linear(act, L["down"])
+            return attn
+
+        resid, delta = self._layers(x, attend)
         for slot, m, tl in zip(slots, news, token_lists):
             self._forget_stale(slot)
             self.cache.lens[slot] += m
@@ -392,25 +445,14 @@ class Qwen3Generator:
             self.last_path = "library"
             x = torch.empty(n, c.hidden_size, dtype=bf, device=dev)
             ops.embed_gather(ids, enc.embed, x)
-            resid = x.clone()
-            normed = torch.empty_like(x)
             attn = torch.empty(n, c.q_size, dtype=bf, device=dev)
-            act = torch.empty(n, c.intermediate_size, dtype=bf, device=dev)
-            delta = None
-            for i, L in enumerate(enc.layers):
-                kc, vc = self.cache.layer(i)
-                if i == 0:
-                    ops.rmsnorm(x, L["ln1"], normed, c.rms_norm_eps, residual_in=None, residual_out=None)
-                else:
-                    ops.rmsnorm(delta, L["ln1"], normed, c.rms_norm_eps, residual_in=resid, residual_out=resid)
-                qkv = F.linear(normed, L["qkv"])
-                ops.decode_attention(qkv, L["q_norm"], L["k_norm"], enc._cos_sin, kc, vc, slots, lens, attn, c.num_heads,
-                                     c.num_kv_heads, c.rms_norm_eps, scale, self._workspace)
-                delta = F.linear(attn, L["o"])
-                ops.rmsnorm(delta, L["ln2"], normed, c.rms_norm_eps, residual_in=resid, residual_out=resid)
-                ops.swiglu(F.linear(normed, L["gate_up"]), act)
-                delta = F.linear(act, L["down"])
-            hidden = resid
+
+            def attend(i, L, normed):
+                ops.decode_attention(F.linear(normed, L["qkv"]), L["q_norm"], L["k_norm"], enc._cos_sin, *self.cache.layer(i),
+                                     slots, lens, attn, c.num_heads, c.num_kv_heads, c.rms_norm_eps, scale, self._workspace)
+                return attn
+
+            hidden, delta = self._layers(x, attend)
         for s, tok in zip(slots, tokens):
             self._forget_stale(s)
             self.cache.lens[s] += 1
@@ -448,19 +490,7 @@ class Qwen3Generator:
             raise PromptTooLong(f"a prompt of {longest} tokens does not fit: max_context {self.max_context} - "
                                 f"max_new_tokens {max_new_tokens} leaves {room}")
         stop = {int(s) for s in stop_ids}
-        if grammar is not None:
-            table = grammar.table if grammar.table is not None else self.token_table()
-            if table.vocab != self.cfg.vocab_size:
-                raise ValueError(f"the grammar's token table holds {table.vocab} ids, the model {self.cfg.vocab_size}")
-            if len(prompts) > self.max_seqs:
-                raise ValueError(f"generate takes 1..{self.max_seqs} prompts")
-        if sampling is not None:
-            draws = [sampling] * len(prompts) if isinstance(sampling, SamplingParams) else list(sampling)
-            lanes = list(range(len(prompts))) if streams is None else [int(s) for s in streams]
-            if len(prompts) > self.max_seqs or len(draws) != len(prompts) or len(lanes) != len(prompts):
-                raise ValueError(f"sampling takes 1..{self.max_seqs} prompts, and one SamplingParams and one stream for each")
-            if len({int(d.seed) for d in draws}) > 1:
-                raise ValueError("the prompts of one call are drawn with one seed")
+        pick = _Picker(self, len(prompts), grammar, sampling, streams)
         keeps = [0] * len(prompts)
         if reuse_prefix and len(prompts) <= self.max_seqs:
             keeps = [plan_reuse(self.resident(b), p, PREFIX_MIN_REUSE) for b, p in enumerate(prompts)]
@@ -475,39 +505,11 @@ class Qwen3Generator:
         out: List[List[int]] = [[] for _ in prompts]
         live = list(range(len(prompts)))          # slot b holds prompt b
         accepted = [False] * len(prompts)
-        produced = 0     # tokens every live sequence has so far: the step of the next draw
-
-        def draw(rows: List[int], logits: torch.Tensor, bits: Optional[torch.Tensor] = None) -> torch.Tensor:
-            token = torch.empty(len(rows), dtype=torch.int32, device=self.device)
-            return ops.sample(logits, [draws[b] for b in rows], produced, [lanes[b] for b in rows], token,
-                              allowed_bits=bits)
-
-        if grammar is None:
-            nxt = self.last_tokens.tolist() if sampling is None else draw(live, logits).tolist()
-        else:
-            tables = table.to(self.device) + grammar.dfa.to(self.device)
-            state = torch.full((len(prompts),), int(grammar.dfa.start), dtype=torch.int32, device=self.device)
-
-            def select(rows: List[int], logits: torch.Tensor) -> List[int]:
-                """The allowed greedy token of the sequences `rows` (logits [len(rows), vocab]); their states move on."""
-                idx = torch.tensor(rows, dtype=torch.int64).to(self.device)
-                cur = state.index_select(0, idx)
-                token = torch.empty(len(rows), dtype=torch.int32, device=self.device)
-                if sampling is None:
-                    ops.grammar_argmax(logits, *tables, cur, token)
-                else:
-                    bits = torch.empty(len(rows), (table.vocab + 31) // 32, dtype=torch.int32, device=self.device)
-                    ops.grammar_argmax(logits, *tables, cur.clone(), token, allowed_bits=bits)
-                    token = draw(rows, logits, bits)
-                    ops.grammar_advance(*tables[:5], cur, token)
-                state.index_copy_(0, idx, cur)
-                return token.tolist()
-
-            nxt = select(live, logits)
+        greedy, produced = self.last_tokens, 0    # produced: tokens every live sequence has so far, the step of the next draw
         while live:
             feed, keep = [], []
-            for b, tok in zip(live, nxt):
-                if grammar is not None and tok >= 0 and table.kind[tok] == KIND_STOP:
+            for b, tok in zip(live, pick(live, logits, greedy, produced)):
+                if pick.table is not None and tok >= 0 and pick.table.kind[tok] == KIND_STOP:
                     accepted[b] = True
                     continue
                 if tok in stop or tok < 0:
@@ -517,15 +519,10 @@ class Qwen3Generator:
                     keep.append(b)
                     feed.append(int(tok))
             live = keep
-            if not live:
-                break
-            self.live = list(live)
-            token, logits = self.step(feed)
-            produced += 1
-            if grammar is not None:
-                nxt = select(live, logits)
-            else:
-                nxt = token.tolist() if sampling is None else draw(live, logits).tolist()
+            if live:
+                self.live = list(live)
+                greedy, logits = self.step(feed)
+                produced += 1
         self.live = []
         self.last_grammar = {"accepted": accepted} if grammar is not None else None
         return out

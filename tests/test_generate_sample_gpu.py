@@ -1,6 +1,7 @@
 """Qwen3Generator.generate(sampling=...) on the tiny checkpoint: temperature 0 is the greedy path (with and without a
 grammar, with reuse_prefix); a sampled run equals a hand loop of prefill / step / ops.sample; seeds repeat and differ;
-under the citation grammar every drawn token is one the tracked state allows and accepted outputs pass the validator;
+under the citation grammar every drawn token is one the tracked state allows and accepted outputs pass the validator,
+and a sampled run equals a hand loop of prefill / step / ops.grammar_argmax / ops.sample / ops.grammar_advance;
 /answer reports the parameters."""
 from __future__ import annotations
 
@@ -119,6 +120,49 @@ def test_under_the_grammar_every_drawn_token_is_allowed(gpu, generator, prompts)
             else:
                 assert len(out) == 48
     print(f"accepted any: {accepted_any}")
+
+
+def test_a_sampled_run_under_the_grammar_equals_the_hand_loop(gpu, generator, prompts):
+    """The fourth selection mode, token for token: grammar_argmax hands out the bits on a copy of the states, sample draws
+    under them with step = the token's index and the prompt's stream, grammar_advance moves the states."""
+    from cadence_rag_amd.encoder import ops
+    gen, two, new, streams = generator, prompts[:2], 12, [3, 5]
+    g = TokenGrammar(citation_grammar(["Q-12", "A-45"]), gen.token_table())
+    params = SamplingParams(temperature=1.0, top_k=20, seed=11)
+    stop = set(gen.stop_ids())
+    got = gen.generate(two, new, gen.stop_ids(), grammar=g, sampling=params, streams=streams)
+    got_accepted = gen.last_grammar["accepted"]
+
+    tables = g.table.to(DEV) + g.dfa.to(DEV)
+    state = torch.full((2,), int(g.dfa.start), dtype=torch.int32, device=DEV)
+    by_hand, accepted, live = [[], []], [False, False], [0, 1]
+    logits = gen.prefill(two)
+    for j in range(new):
+        idx = torch.tensor(live, dtype=torch.int64).to(DEV)
+        cur = state.index_select(0, idx)
+        token = torch.empty(len(live), dtype=torch.int32, device=DEV)
+        bits = torch.empty(len(live), (g.table.vocab + 31) // 32, dtype=torch.int32, device=DEV)
+        ops.grammar_argmax(logits, *tables, cur.clone(), token, allowed_bits=bits)
+        ops.sample(logits, params, j, [streams[b] for b in live], token, allowed_bits=bits)
+        ops.grammar_advance(*tables[:5], cur, token)
+        state.index_copy_(0, idx, cur)
+        feed, keep = [], []
+        for b, t in zip(live, token.tolist()):
+            if t >= 0 and g.table.kind[t] == grammar.KIND_STOP:
+                accepted[b] = True
+            elif t >= 0 and t not in stop:
+                by_hand[b].append(t)
+                if len(by_hand[b]) < new:
+                    keep.append(b)
+                    feed.append(t)
+        live = keep
+        if not live:
+            break
+        _, logits = gen.step(feed, slots=live)
+    gen.live = []
+    print(f"by hand: {by_hand}, accepted {accepted}")
+    assert got == by_hand and got_accepted == accepted
+    assert any(by_hand) and by_hand != gen.generate(two, new, gen.stop_ids(), grammar=g)   # drawn, not the greedy run
 
 
 def test_answer_reports_the_sampling_parameters(gpu, generator, monkeypatch):

@@ -1,7 +1,8 @@
 """crag_enc_sample and crag_enc_grammar_advance on the GPU against the host rule (cadence_rag_amd.sampling.sample_host,
 grammar.next_state_host).
 
-Exact, no tolerance: greedy rows against crag_enc_lm_head's and crag_enc_grammar_argmax's own tokens; with top_p == 1 the
+Exact, no tolerance: greedy rows against crag_enc_lm_head's and crag_enc_grammar_argmax's own tokens, and the three at
+the edges of their shared (value, id) merge (the maximum at ids 0 and vocab - 1); with top_p == 1 the
 kept count and the lowest kept logit; the same bits when a call is repeated, its rows permuted and padded by others;
 every (state, token) step of a citation grammar.
 The draw: a case is compared when the fp64 winner is the same under top_p (1 - d) and top_p (1 + d), d = 1e-4 (the fp32
@@ -112,6 +113,67 @@ def test_greedy_rows_equal_lm_head_and_grammar_argmax(gpu, v, rows):
     assert token == [-1] * rows and kept == [0] * rows
     token, kept, _ = _sample(x, SamplingParams(1.0), 0, [0] * rows, allowed=np.zeros((rows, v), bool))
     assert token == [-1] * rows and kept == [0] * rows
+
+
+@pytest.mark.parametrize("v", [63, 64, 65, 1024, 1025])
+def test_the_maximum_at_the_first_and_the_last_id_goes_to_the_lower_one(gpu, v):
+    """The (value, id) merge at its edges: below and above one wave, below and above one pass of the 1024 threads.  The
+    maximum sits at ids 0 and v - 1 alone -- thread 0 and the last thread that holds an id -- and lm_head's token,
+    grammar_argmax in a state that allows everything and sample at T = 0 all name id 0; with id 0 banned, or its logit
+    NaN, they all name v - 1."""
+    from cadence_rag_amd.encoder import ops
+    rng = np.random.default_rng(v)
+    rows, hidden = 2, 64
+    x = rng.standard_normal((rows, hidden)).astype(np.float32)
+    x[:, :2] = 1.0
+    lm = (rng.standard_normal((v, hidden)) * 0.1).astype(np.float32)
+    lm[0] = lm[v - 1] = np.sign(x[0]) * (np.sign(x[0]) == np.sign(x[1])) * 4.0    # a large dot product with both rows
+    hs = torch.from_numpy(x).to(DEV).to(torch.bfloat16)
+    w = torch.ones(hidden, dtype=torch.bfloat16, device=DEV)
+    lmw = torch.from_numpy(lm).to(DEV).to(torch.bfloat16).contiguous()
+    logits = torch.empty(rows, v, dtype=torch.float32, device=DEV)
+    token = torch.full((rows,), -7, dtype=torch.int32, device=DEV)
+    ops.lm_head(hs, w, lmw, logits, token, 1e-6)
+    host = logits.cpu().numpy()
+    top = host.max(1)
+    assert [np.flatnonzero(host[r] == top[r]).tolist() for r in range(rows)] == [[0, v - 1]] * rows
+    assert token.tolist() == [0] * rows
+    greedy = SamplingParams(0.0)
+    kind = np.zeros(v, np.uint8)
+    dfa = ByteDfa(np.zeros(256, np.uint8), np.zeros((1, 1), np.uint16), np.ones(1, np.uint8)).to(DEV)
+
+    def grammar_token(lg, kind, with_bits):
+        table = TokenTable(np.arange(v + 1, dtype=np.int32), np.full(v, 65, np.uint8), kind).to(DEV)
+        state = torch.zeros(rows, dtype=torch.int32, device=DEV)
+        out = torch.full((rows,), -7, dtype=torch.int32, device=DEV)
+        bits = torch.empty(rows, (v + 31) // 32, dtype=torch.int32, device=DEV) if with_bits else None
+        ops.grammar_argmax(lg, *table, *dfa, state, out, allowed_bits=bits)
+        return out.tolist(), bits
+
+    def sample_token(lg, bits):
+        out = torch.full((rows,), -7, dtype=torch.int32, device=DEV)
+        ops.sample(lg, greedy, 0, [0] * rows, out, allowed_bits=bits)
+        return out.tolist()
+
+    for with_bits in (False, True):
+        got, bits = grammar_token(logits, kind, with_bits)
+        assert got == [0] * rows and sample_token(logits, bits) == [0] * rows
+    # id 0 banned
+    ops.lm_head(hs, w, lmw, logits, token, 1e-6, banned=torch.zeros(1, dtype=torch.int32, device=DEV))
+    assert token.tolist() == [v - 1] * rows
+    banned_kind = kind.copy()
+    banned_kind[0] = KIND_NEVER
+    for with_bits in (False, True):
+        got, bits = grammar_token(logits, banned_kind, with_bits)
+        assert got == [v - 1] * rows
+    assert sample_token(logits, bits) == [v - 1] * rows
+    # id 0 NaN: an inf and a -inf weight meet in its dot product
+    lm[0, :2] = [np.inf, -np.inf]
+    ops.lm_head(hs, w, torch.from_numpy(lm).to(DEV).to(torch.bfloat16).contiguous(), logits, token, 1e-6)
+    assert torch.isnan(logits[:, 0]).all() and token.tolist() == [v - 1] * rows
+    for with_bits in (False, True):
+        got, bits = grammar_token(logits, kind, with_bits)
+        assert got == [v - 1] * rows and sample_token(logits, bits) == [v - 1] * rows
 
 
 # ---- the cuts, exactly ----------------------------------------------------------------------------------------------------
