@@ -134,6 +134,9 @@ SIGNATURES = {
     "crag_enc_decode_workspace_bytes": (_c.c_int64, [_c.c_int, _c.c_int, _c.c_int]),
     "crag_enc_decode_attention": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int,
                                              _c.c_int, _c.c_float, _c.c_float, _P, _c.c_int64, _P, _P]),
+    "crag_enc_decode_attention_shared": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _P,
+                                                    _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _P, _c.c_int64,
+                                                    _P, _P]),
     "crag_enc_lm_head": (_c.c_int, [_P, _P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_float, _P]),
     "crag_enc_extend_workspace_bytes": (_c.c_int64, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "crag_enc_extend_attention": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _c.c_int,

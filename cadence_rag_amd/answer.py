@@ -14,6 +14,14 @@ With a temperature of 0 and no such field in the request nothing changes: greedy
 notes.  Otherwise a native model with supports_sampling draws every token on the GPU (crag_enc_sample), an HTTP service
 gets temperature, top_p and seed, notes.sampling echoes the parameters, and repair round i draws on noise stream i.
 
+Several candidates per attempt (`samples` of the request, ANSWER_SAMPLES; 1..8, sampling on): a native model with
+supports_samples draws them from ONE prefill (Qwen3Generator.generate_text_samples: the candidates are forks of the
+prompt's KV rows), attempt a on the noise streams a * n + i.  They are judged in index order: the first that passes the
+gate is the answer; if every one is INSUFFICIENT_EVIDENCE so is the response; otherwise the first failing candidate that
+is not INSUFFICIENT_EVIDENCE goes into the repair turn.  notes.samples = {"drawn", "valid", "chosen"} describes the last
+attempt; llm_calls counts calls, not candidates.  An HTTP service, or a native model without supports_samples, gives one
+candidate as ever and notes.samples = {"applied": False}.  With one sample nothing changes.
+
 ANSWER_CONSTRAINED (native backend, a model with supports_grammar): the reply is decoded under the citation grammar of
 the evidence ids in the prompt (cadence_rag_amd.grammar.citation_grammar), which makes a failing answer unrepresentable
 whenever the model stops by itself.  The gate and the repair loop run unchanged on whatever comes back.
@@ -58,7 +66,10 @@ class ChatModel(Protocol):
     Optional: a model whose class sets `supports_grammar = True` also takes `generate_text(messages, max_new_tokens,
     grammar=TokenGrammar)` and decodes only what grammar.dfa accepts; its `token_table()`, if it has one, is the cached
     byte table of its vocabulary that goes into the TokenGrammar.  The keyword is passed only to such a model.
-    Optional: a model whose class sets `supports_sampling = True` also takes `sampling=SamplingParams, stream=int`."""
+    Optional: a model whose class sets `supports_sampling = True` also takes `sampling=SamplingParams, stream=int`.
+    Optional: a model whose class sets `supports_samples = True` also has `generate_text_samples(messages, n,
+    max_new_tokens, grammar=None, sampling=None, streams=None) -> List[str]`: n replies to one chat, reply i drawn on
+    noise stream streams[i]; the same exceptions as generate_text."""
 
     model_id: str
 
@@ -196,6 +207,28 @@ def _chat_native(messages: List[Dict[str, str]], max_new_tokens: int, grammar: O
     return text, str(getattr(llm, "model_id", None) or settings.llm_model)
 
 
+def chat_samples(messages: List[Dict[str, str]], n: int, max_new_tokens: Optional[int] = None,
+                 grammar: Optional[TokenGrammar] = None, sampling: Optional[SamplingParams] = None,
+                 streams: Optional[Sequence[int]] = None) -> Tuple[List[str], str]:
+    """(n replies, model id) from the registered native model's generate_text_samples (native_samples()).  ValueError
+    (the prompt does not fit) passes through, as from chat()."""
+    llm = _llm
+    if not llm_enabled() or not _is_native(settings.llm_base_url) or llm is None:
+        raise AnswerClientError("native LLM is not loaded (call set_llm)")
+    try:
+        with _llm_lock:
+            texts = llm.generate_text_samples(messages, int(n), int(max_new_tokens or settings.llm_max_new_tokens),
+                                              grammar=grammar, sampling=sampling,
+                                              streams=None if streams is None else [int(x) for x in streams])
+    except (AnswerClientError, ValueError):
+        raise
+    except Exception as exc:  # noqa: BLE001 - callers rely on a single error type
+        raise AnswerClientError(f"native LLM failed: {exc}") from exc
+    if not isinstance(texts, list) or len(texts) != int(n) or not all(isinstance(t, str) for t in texts):
+        raise AnswerClientError(f"native LLM did not return {int(n)} texts")
+    return texts, str(getattr(llm, "model_id", None) or settings.llm_model)
+
+
 def chat(messages: List[Dict[str, str]], max_new_tokens: Optional[int] = None, grammar: Optional[TokenGrammar] = None,
          sampling: Optional[SamplingParams] = None, stream: int = 0) -> Tuple[str, str]:
     """(reply, model id) from the configured LLM.  grammar: native backend only (an HTTP service cannot take one).
@@ -218,6 +251,24 @@ def constrained_decoding() -> bool:
 def native_sampling() -> bool:
     """The registered native model takes sampling=SamplingParams."""
     return bool(getattr(_llm, "supports_sampling", False))
+
+
+def native_samples() -> bool:
+    """The backend is native and the registered model has generate_text_samples."""
+    return _is_native(settings.llm_base_url) and bool(getattr(_llm, "supports_samples", False))
+
+
+def samples_for(request: Any) -> int:
+    """The request's `samples` over ANSWER_SAMPLES: how many candidates an attempt draws.  AnswerRequestError: outside
+    1..8, or more than one while decoding is greedy (sampling_for gives None) -- n greedy copies are one answer."""
+    given = getattr(request, "samples", None)
+    n = settings.answer_samples if given is None else given
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 8:
+        raise AnswerRequestError(f"samples must be an integer in 1..8 (got {n!r})")
+    sampling = sampling_for(request) if n > 1 else None
+    if n > 1 and (sampling is None or float(sampling.temperature) == 0.0):   # (a named temperature of 0 is greedy too)
+        raise AnswerRequestError(f"samples = {n} needs sampling: with a temperature of 0 every candidate is the same answer")
+    return n
 
 
 def sampling_for(request: Any) -> Optional[SamplingParams]:
@@ -251,13 +302,15 @@ def _grammar_for(items: Sequence[Dict[str, Any]], notes: Dict[str, Any]) -> Opti
 # ---- /answer ----------------------------------------------------------------------------------------------------
 @dataclass
 class AnswerRequest(_retrieve.RetrieveRequest):
-    """The /retrieve request plus echo_evidence and the optional sampling fields (None: the ANSWER_* default)."""
+    """The /retrieve request plus echo_evidence, the optional sampling fields and `samples`, the candidates per attempt
+    (None: the ANSWER_* default)."""
     echo_evidence: bool = False
     temperature: Optional[float] = None
     top_p: Optional[float] = None
     top_k: Optional[int] = None
     min_p: Optional[float] = None
     seed: Optional[int] = None
+    samples: Optional[int] = None
 
 
 def _evidence_items(pack: Dict[str, Any]) -> List[Dict[str, Any]]:
@@ -294,6 +347,7 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
     if not llm_enabled():
         raise AnswerClientError("LLM_BASE_URL is not configured")
     sampling = sampling_for(request)
+    n_samples = samples_for(request)
     pack_request = _retrieve.RetrieveRequest(query=request.query, intent=request.intent, filters=request.filters,
                                              budget=request.budget, return_style="evidence_pack_json", debug=request.debug,
                                              facets=request.facets, facet_top=request.facet_top)
@@ -307,6 +361,10 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
         if _is_native(settings.llm_base_url) and not native_sampling():
             notes["sampling"]["applied"] = False   # the registered model cannot sample: it decodes greedily
             sampling = None
+    # several candidates come from one call of a native model that can fork a prefill; anything else draws one as ever
+    multi = n_samples > 1 and sampling is not None and native_samples()
+    if n_samples > 1 and not multi:
+        notes["samples"] = {"applied": False}
     out: Dict[str, Any] = {"query_id": pack["query_id"], "answer": None, "status": STATUS_INSUFFICIENT, "citations": [],
                            "repairs": 0, "model": None, "notes": notes}
     if getattr(request, "echo_evidence", False):
@@ -319,13 +377,20 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
 
     constrained = constrained_decoding()
 
-    def call(attempt: int) -> str:
+    def call(attempt: int) -> List[str]:
+        """The candidates of one attempt: one reply, or under `multi` n_samples from one call."""
         while True:
             try:
                 # the grammar of the items in THIS prompt: rebuilt when an item has been dropped for length
                 grammar = _grammar_for(items, notes) if constrained else None
-                extra = {} if sampling is None else {"sampling": sampling, "stream": attempt}
-                text, model = chat(build_messages(query, items, turns), grammar=grammar, **extra)
+                if multi:
+                    texts, model = chat_samples(build_messages(query, items, turns), n_samples, grammar=grammar,
+                                                sampling=sampling,
+                                                streams=[attempt * n_samples + i for i in range(n_samples)])
+                else:
+                    extra = {} if sampling is None else {"sampling": sampling, "stream": attempt}
+                    text, model = chat(build_messages(query, items, turns), grammar=grammar, **extra)
+                    texts = [text]
             except ValueError as exc:   # the prompt does not fit the model's context: the lowest-ranked item goes
                 if len(items) <= 1:
                     raise AnswerClientError(f"the prompt does not fit with a single evidence item: {exc}") from exc
@@ -337,18 +402,28 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
             # a native generator with a prefix cache says how many prompt tokens it took from its KV cache
             reuse = getattr(_llm, "last_reuse", None) if _is_native(settings.llm_base_url) else None
             if reuse is not None:
-                notes["prefix_reused_tokens"] = notes.get("prefix_reused_tokens", 0) + int(sum(reuse["reused"]))
-            return text
+                # (under `multi` every candidate reports the one prompt's rows: they were reused once)
+                notes["prefix_reused_tokens"] = notes.get("prefix_reused_tokens", 0) + \
+                    int(reuse["reused"][0] if multi else sum(reuse["reused"]))
+            return texts
 
     max_repairs = max(int(settings.answer_max_repairs), 0)
     for attempt in range(max_repairs + 1):
-        text = call(attempt).strip()
+        texts = [t.strip() for t in call(attempt)]
         out["repairs"] = attempt
-        if text.strip(" .\"'`*") == INSUFFICIENT:
+        ids = [i["evidence_id"] for i in items]
+        # judged in index order; None: the candidate says INSUFFICIENT_EVIDENCE
+        reports = [None if t.strip(" .\"'`*") == INSUFFICIENT else validate_citations(t, ids) for t in texts]
+        chosen = next((i for i, r in enumerate(reports) if r is not None and r["valid"]), None)
+        if multi:
+            notes["samples"] = {"drawn": len(texts), "valid": sum(1 for r in reports if r is not None and r["valid"]),
+                                "chosen": chosen}
+        if all(r is None for r in reports):
             out["status"] = STATUS_INSUFFICIENT
             return out
-        ids = [i["evidence_id"] for i in items]
-        report = validate_citations(text, ids)
+        if chosen is None:   # the repair turn quotes the first candidate that tried to answer
+            chosen = next(i for i, r in enumerate(reports) if r is not None)
+        text, report = texts[chosen], reports[chosen]
         notes["validator"] = report
         if report["valid"]:
             by_id = {i["evidence_id"]: i for i in items}

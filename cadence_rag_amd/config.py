@@ -76,6 +76,9 @@ class Settings:
     answer_top_k: int = 0
     answer_min_p: float = 0.0
     answer_seed: int = 0
+    # candidates drawn per attempt (1..8; a request's `samples` overrides it).  Above 1 -- sampling on, a native model with
+    # generate_text_samples -- one prefill serves all of them and the first that passes the citation check is the answer
+    answer_samples: int = 1
 
     def __post_init__(self) -> None:
         if self.rerank_device < 0:

@@ -8,11 +8,18 @@
 //                               weights streamed once through bf16 MFMA), greedy token = lowest id among the maxima,
 //                               banned ids left out.
 //
+//   crag_enc_decode_attention_shared   the same over FORKED sequences: a sequence reads its first shared_len rows from
+//                               a parent slot and the rest from its own.  The split launch runs units: the sequences of
+//                               one parent form group units, each of which loads every row of a wholly shared split
+//                               once for its members' query heads; every sequence is a unit of its own for its other
+//                               splits.
+//
 // Nothing here depends on the number of sequences, on the slot or on a launch size chosen at run time: a split is
 // always DECODE_SPLIT keys, its keys are always walked by the same lanes in the same order, and the splits are summed
 // in ascending order, so a sequence's output bits are a function of its own data alone.  No atomics.
 
 #include <math.h>
+#include <string.h>
 
 #include "../../include/crag_encoder.h"
 #include "crag_enc_common.h"
@@ -172,6 +179,213 @@ __global__ __launch_bounds__(DECODE_THREADS) void decode_split_kernel(const Deco
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// split over forked sequences.  A unit (blockIdx.z) is a list of member sequences that read the SAME rows in the splits
+// [s_begin, s_end): logical row j comes from slot `parent` when j < shared and from slot `own` otherwise.  A group unit
+// holds 2..FORK_UNIT_MEMBERS sequences of one parent over the splits wholly below the shared_len of every sequence of
+// that parent; a sequence's other splits are a unit of one member.  decode_split_kernel's arithmetic per (sequence, head, split): a row is read by
+// the same 16-lane group and dotted in the same element and shuffle order, the 16 groups are summed in group order.
+// A lane keeps its 8 key rows, then its 8 value rows, in registers (one Pack8 each) while the members pass by: their
+// rotated queries wait in LDS, their scores in sc[member]; red is reused member after member.
+// ---------------------------------------------------------------------------------------------
+constexpr int FORK_MAX_UNITS = DECODE_MAX_SEQS + DECODE_MAX_SEQS / 2;   // every sequence alone + the units of >= 2
+// Sequences one group unit serves.  Measured at 32 / 8 heads with 8 children of one parent (profiles/fork_bench.jsonl,
+// the lines with "unit_members"): units of 8 take 36 / 51 us at 1024 / 4096 shared keys, units of 4 28 / 41 us, units
+// of 2 22 / 43 us, private copies 23 / 50 us -- a unit works its members off one after the other, and with 8 or 32
+// splits per kv head the launch has too few workgroups to hide that.  Two is the size that loses nowhere; the kernel
+// itself takes any size up to 8.
+constexpr int FORK_UNIT_MEMBERS = 2;
+static_assert(FORK_UNIT_MEMBERS >= 2 && FORK_UNIT_MEMBERS <= DECODE_MAX_SEQS, "a group unit holds 2..8 sequences");
+
+struct ForkUnits {
+    int32_t n_members[FORK_MAX_UNITS];
+    int32_t s_begin[FORK_MAX_UNITS], s_end[FORK_MAX_UNITS];
+    int32_t parent[FORK_MAX_UNITS], own[FORK_MAX_UNITS];   // slots
+    int32_t shared[FORK_MAX_UNITS], n_keys[FORK_MAX_UNITS];
+    int8_t member[FORK_MAX_UNITS][DECODE_MAX_SEQS];         // sequence indices
+};
+
+// Lane i of every 16-lane row <- lane (i + N) % 16 of the row, on the VALU (DPP row_ror).  In a butterfly over the
+// strides 8, 4, 2, 1 it stands for __shfl_xor(v, N) bit for bit: behind the stages of the larger strides every lane
+// holds what its partners across those strides hold (a + b == b + a), and (i + N) % 16 differs from i ^ N in the bits
+// of those strides only.
+template <int N>
+__device__ __forceinline__ float row_ror(float v) {
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x120 + N, 0xF, 0xF, true));
+}
+
+template <int G>
+__global__ __launch_bounds__(DECODE_THREADS) void decode_split_shared_kernel(const DecodeParams p, const ForkUnits u) {
+    __shared__ float sc[FORK_UNIT_MEMBERS][G][DECODE_SPLIT];    // raw dot products, then the weights
+    __shared__ float red[DECODE_GROUPS][G][CRAG_HEAD_DIM];      // 32 KiB at G = 4
+    __shared__ float ml[FORK_UNIT_MEMBERS][G][2];
+    __shared__ __align__(16) u16 qs[FORK_UNIT_MEMBERS][G][CRAG_HEAD_DIM];   // the members' rotated queries
+    const int s = blockIdx.x, kvh = blockIdx.y, unit = blockIdx.z;
+    if (s < u.s_begin[unit] || s >= u.s_end[unit]) return;   // (uniform)
+    const int n_mem = u.n_members[unit], n_keys = u.n_keys[unit], shared = u.shared[unit];
+    const int k0 = s * DECODE_SPLIT;
+    const int grp = threadIdx.x >> 4, sub = threadIdx.x & 15;
+    const u16 *kp = p.k_cache + kv_row(p.hkv, p.max_len, u.parent[unit], kvh, 0);
+    const u16 *vp = p.v_cache + kv_row(p.hkv, p.max_len, u.parent[unit], kvh, 0);
+    const u16 *ko = p.k_cache + kv_row(p.hkv, p.max_len, u.own[unit], kvh, 0);
+    const u16 *vo = p.v_cache + kv_row(p.hkv, p.max_len, u.own[unit], kvh, 0);
+
+    for (int i = threadIdx.x; i < n_mem * G * 16; i += DECODE_THREADS) {
+        const int m = i / (G * 16), g = i / 16 % G, ch = i % 16;
+        *reinterpret_cast<Pack8 *>(&qs[m][g][ch * 8]) = *reinterpret_cast<const Pack8 *>(
+            p.q_rot + ((int64_t)u.member[unit][m] * p.hq + kvh * G + g) * CRAG_HEAD_DIM + ch * 8);
+    }
+    Pack8 rows[DECODE_ITERS];
+#pragma unroll
+    for (int it = 0; it < DECODE_ITERS; ++it) {
+        const int j = k0 + it * DECODE_GROUPS + grp;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) rows[it].v[e] = 0;
+        if (j < n_keys)   // positions at or beyond len + 1 are never read, nor a child's own rows below shared_len
+            rows[it] = *reinterpret_cast<const Pack8 *>((j < shared ? kp : ko) + (int64_t)j * CRAG_HEAD_DIM + sub * 8);
+    }
+    __syncthreads();
+    // scores
+    for (int m = 0; m < n_mem; ++m) {
+        float q[G][8];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const Pack8 a = *reinterpret_cast<const Pack8 *>(&qs[m][g][sub * 8]);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) q[g][e] = bf2f(a.v[e]);
+        }
+        float d[DECODE_ITERS][G];
+#pragma unroll
+        for (int it = 0; it < DECODE_ITERS; ++it)
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                d[it][g] = 0.f;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) d[it][g] += q[g][e] * bf2f(rows[it].v[e]);
+            }
+#pragma unroll
+        for (int it = 0; it < DECODE_ITERS; ++it)
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                d[it][g] += row_ror<8>(d[it][g]);
+                d[it][g] += row_ror<4>(d[it][g]);
+                d[it][g] += row_ror<2>(d[it][g]);
+                d[it][g] += row_ror<1>(d[it][g]);
+            }
+        if (sub == 0) {
+#pragma unroll
+            for (int it = 0; it < DECODE_ITERS; ++it) {
+                const int j = it * DECODE_GROUPS + grp;
+#pragma unroll
+                for (int g = 0; g < G; ++g) sc[m][g][j] = k0 + j < n_keys ? d[it][g] : -INFINITY;
+            }
+        }
+    }
+    // the value rows travel while the softmax runs
+#pragma unroll
+    for (int it = 0; it < DECODE_ITERS; ++it) {
+        const int j = k0 + it * DECODE_GROUPS + grp;
+        if (j < n_keys)
+            rows[it] = *reinterpret_cast<const Pack8 *>((j < shared ? vp : vo) + (int64_t)j * CRAG_HEAD_DIM + sub * 8);
+    }
+    __syncthreads();
+    // softmax of the split: a wave takes every fourth (member, query head), SM_HEADS of them side by side so that
+    // their reductions overlap (the strides 32 and 16 cross the 16-lane rows: shuffles; below them row_ror)
+    {
+        constexpr int WAVES = DECODE_THREADS / 64;
+        constexpr int SM_HEADS = FORK_UNIT_MEMBERS * G >= 4 * WAVES ? 4 : FORK_UNIT_MEMBERS * G > WAVES ? 2 : 1;
+        const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        const int n_heads = n_mem * G;
+        for (int h0 = w; h0 < n_heads; h0 += SM_HEADS * WAVES) {   // (uniform in the wave)
+            float x[SM_HEADS][DECODE_SPLIT / 64], mx[SM_HEADS], l[SM_HEADS];
+#pragma unroll
+            for (int t = 0; t < SM_HEADS; ++t) {
+                const int hd = h0 + t * WAVES < n_heads ? h0 + t * WAVES : h0;   // past the last head: h0 again, not stored
+                mx[t] = -INFINITY;
+#pragma unroll
+                for (int i = 0; i < DECODE_SPLIT / 64; ++i) {
+                    x[t][i] = sc[hd / G][hd % G][lane + 64 * i];
+                    mx[t] = fmaxf(mx[t], x[t][i]);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < SM_HEADS; ++t) mx[t] = fmaxf(mx[t], __shfl_xor(mx[t], 32));
+#pragma unroll
+            for (int t = 0; t < SM_HEADS; ++t) mx[t] = fmaxf(mx[t], __shfl_xor(mx[t], 16));
+#pragma unroll
+            for (int t = 0; t < SM_HEADS; ++t) {
+                mx[t] = fmaxf(mx[t], row_ror<8>(mx[t]));
+                mx[t] = fmaxf(mx[t], row_ror<4>(mx[t]));
+                mx[t] = fmaxf(mx[t], row_ror<2>(mx[t]));
+                mx[t] = fmaxf(mx[t], row_ror<1>(mx[t]));
+                l[t] = 0.f;
+#pragma unroll
+                for (int i = 0; i < DECODE_SPLIT / 64; ++i) {
+                    x[t][i] = exp2f((x[t][i] - mx[t]) * p.scale_log2);   // the split holds at least one key: mx is finite
+                    l[t] += x[t][i];
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < SM_HEADS; ++t) l[t] += __shfl_xor(l[t], 32);
+#pragma unroll
+            for (int t = 0; t < SM_HEADS; ++t) l[t] += __shfl_xor(l[t], 16);
+#pragma unroll
+            for (int t = 0; t < SM_HEADS; ++t) {
+                l[t] += row_ror<8>(l[t]);
+                l[t] += row_ror<4>(l[t]);
+                l[t] += row_ror<2>(l[t]);
+                l[t] += row_ror<1>(l[t]);
+                const int hd = h0 + t * WAVES;
+                if (hd < n_heads) {
+#pragma unroll
+                    for (int i = 0; i < DECODE_SPLIT / 64; ++i) sc[hd / G][hd % G][lane + 64 * i] = x[t][i];
+                    if (lane == 0) {
+                        ml[hd / G][hd % G][0] = mx[t];
+                        ml[hd / G][hd % G][1] = l[t];
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // weighted values, member after member
+    for (int m = 0; m < n_mem; ++m) {
+        float acc[G][8];
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[g][e] = 0.f;
+#pragma unroll
+        for (int it = 0; it < DECODE_ITERS; ++it) {
+            const int j = it * DECODE_GROUPS + grp;
+            if (k0 + j < n_keys) {
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    const float pr = sc[m][g][j];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) acc[g][e] += pr * bf2f(rows[it].v[e]);
+                }
+            }
+        }
+        if (m) __syncthreads();   // the sums of the member before have been read
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) red[grp][g][sub * 8 + e] = acc[g][e];
+        __syncthreads();
+        const int b = u.member[unit][m];
+        for (int i = threadIdx.x; i < G * CRAG_HEAD_DIM; i += DECODE_THREADS) {
+            const int g = i / CRAG_HEAD_DIM, d = i % CRAG_HEAD_DIM;
+            float o = 0.f;
+#pragma unroll
+            for (int r = 0; r < DECODE_GROUPS; ++r) o += red[r][g][d];
+            const int64_t part = ((int64_t)b * p.hq + kvh * G + g) * p.max_splits + s;
+            p.part_o[part * CRAG_HEAD_DIM + d] = o;
+            if (d < 2) p.part_ml[part * 2 + d] = ml[m][g][d];
+        }
+    }
+}
+
 // combine: workgroup (q head, sequence), 128 threads = the 128 output elements; the splits in ascending order
 __global__ __launch_bounds__(CRAG_HEAD_DIM) void decode_combine_kernel(const DecodeParams p) {
     const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
@@ -287,50 +501,37 @@ __global__ __launch_bounds__(ARGMAX_THREADS) void lm_argmax_kernel(const float *
     if (threadIdx.x == 0) token[blockIdx.x] = best.id;
 }
 
-}  // namespace
-
-extern "C" {
-
-int64_t crag_enc_decode_workspace_bytes(int n_seqs, int hq, int max_len) {
-    if (n_seqs <= 0 || n_seqs > DECODE_MAX_SEQS || hq <= 0 || max_len <= 0) return 0;
-    const int64_t splits = ((int64_t)max_len + DECODE_SPLIT - 1) / DECODE_SPLIT;
-    const int64_t heads = (int64_t)n_seqs * hq;
-    // q_rot (bf16, rounded up to 16 bytes per head anyway) + partial o + partial (m, l)
-    return heads * CRAG_HEAD_DIM * 2 + heads * splits * CRAG_HEAD_DIM * 4 + heads * splits * 2 * 4;
-}
-
-int crag_enc_decode_attention(const uint16_t *qkv_new, const uint16_t *q_norm_w, const uint16_t *k_norm_w,
-                              const float *cos_sin, int max_pos, uint16_t *k_cache, uint16_t *v_cache, int n_slots,
-                              int max_len, const int32_t *h_slots, const int32_t *h_cache_len, int n_seqs, int hq, int hkv,
-                              float eps, float scale, void *workspace, int64_t workspace_bytes, uint16_t *out,
-                              void *stream) {
+// the checks the two attention entries share, and the parameter block they launch with; `what` names the entry
+int decode_setup(const char *what, const uint16_t *qkv_new, const uint16_t *q_norm_w, const uint16_t *k_norm_w,
+                 const float *cos_sin, int max_pos, uint16_t *k_cache, uint16_t *v_cache, int n_slots, int max_len,
+                 const int32_t *h_slots, const int32_t *h_cache_len, int n_seqs, int hq, int hkv, float eps, float scale,
+                 void *workspace, int64_t workspace_bytes, uint16_t *out, DecodeParams &p) {
     if (!qkv_new || !q_norm_w || !k_norm_w || !cos_sin || !k_cache || !v_cache || !h_slots || !h_cache_len || !workspace ||
         !out)
-        return efail("decode_attention: NULL pointer");
+        return efail("%s: NULL pointer", what);
     if (n_seqs < 1 || n_seqs > DECODE_MAX_SEQS)
-        return efail("decode_attention: n_seqs must be in 1..%d (got %d)", DECODE_MAX_SEQS, n_seqs);
+        return efail("%s: n_seqs must be in 1..%d (got %d)", what, DECODE_MAX_SEQS, n_seqs);
     if (hq <= 0 || hkv <= 0 || hq % hkv || (hq / hkv != 2 && hq / hkv != 4))
-        return efail("decode_attention: hq / hkv must be 2 or 4 (got %d / %d)", hq, hkv);
-    if (n_slots <= 0 || max_len <= 0 || max_pos <= 0) return efail("decode_attention: n_slots, max_len and max_pos must be positive");
+        return efail("%s: hq / hkv must be 2 or 4 (got %d / %d)", what, hq, hkv);
+    if (n_slots <= 0 || max_len <= 0 || max_pos <= 0) return efail("%s: n_slots, max_len and max_pos must be positive", what);
     if (((uintptr_t)qkv_new | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)workspace | (uintptr_t)q_norm_w |
          (uintptr_t)k_norm_w) & 15)
-        return efail("decode_attention: qkv_new, the norm weights, the cache and the workspace must be 16-byte aligned");
-    DecodeParams p;
+        return efail("%s: qkv_new, the norm weights, the cache and the workspace must be 16-byte aligned", what);
     for (int b = 0; b < n_seqs; ++b) {
         const int len = h_cache_len[b], slot = h_slots[b];
         if (len < 0 || len >= max_len)
-            return efail("decode_attention: cache length %d of sequence %d is outside 0..max_len - 1 = %d", len, b, max_len - 1);
-        if (len >= max_pos) return efail("decode_attention: position %d of sequence %d is beyond the RoPE table (%d rows)", len, b, max_pos);
-        if (slot < 0 || slot >= n_slots) return efail("decode_attention: slot %d of sequence %d is outside 0..%d", slot, b, n_slots - 1);
+            return efail("%s: cache length %d of sequence %d is outside 0..max_len - 1 = %d", what, len, b, max_len - 1);
+        if (len >= max_pos) return efail("%s: position %d of sequence %d is beyond the RoPE table (%d rows)", what, len, b, max_pos);
+        if (slot < 0 || slot >= n_slots) return efail("%s: slot %d of sequence %d is outside 0..%d", what, slot, b, n_slots - 1);
         for (int a = 0; a < b; ++a)
-            if (h_slots[a] == slot) return efail("decode_attention: slot %d is named twice in one call", slot);
+            if (h_slots[a] == slot) return efail("%s: slot %d is named twice in one call", what, slot);
         p.seqs.len[b] = len;
         p.seqs.slot[b] = slot;
     }
     for (int b = n_seqs; b < DECODE_MAX_SEQS; ++b) p.seqs.len[b] = p.seqs.slot[b] = 0;
     const int64_t need = crag_enc_decode_workspace_bytes(n_seqs, hq, max_len);
     if (workspace_bytes < need)
-        return fail(CRAG_E2BIG, "decode_attention: the workspace holds %lld bytes, %lld are needed", (long long)workspace_bytes,
+        return fail(CRAG_E2BIG, "%s: the workspace holds %lld bytes, %lld are needed", what, (long long)workspace_bytes,
                     (long long)need);
     const int max_splits = (max_len + DECODE_SPLIT - 1) / DECODE_SPLIT;
     const int64_t heads = (int64_t)n_seqs * hq;
@@ -350,6 +551,92 @@ int crag_enc_decode_attention(const uint16_t *qkv_new, const uint16_t *q_norm_w,
     p.max_splits = max_splits;
     p.eps = eps;
     p.scale_log2 = scale * 1.4426950408889634f;
+    return CRAG_OK;
+}
+
+// The fork checks of decode_attention_shared and the units of its split launch (p.seqs is checked and filled).  Unit
+// b < n_seqs is sequence b alone over the splits no group unit covers; behind them the group units: the sequences of
+// the call that read one parent -- the parent itself counts when it is in the call: all of its rows are its own -- in
+// units of FORK_UNIT_MEMBERS, over the splits that lie wholly below the shared length of every one of them.
+int fork_plan(const DecodeSeqs &seqs, const int32_t *h_parent, const int32_t *h_shared_len, int n_seqs, int n_slots,
+              ForkUnits &u, int &n_units) {
+    const char *what = "decode_attention_shared";
+    if (!h_parent || !h_shared_len) return efail("%s: NULL pointer", what);
+    int from[DECODE_MAX_SEQS], below[DECODE_MAX_SEQS];   // the slot the leading rows come from, and how many rows do
+    for (int b = 0; b < n_seqs; ++b) {
+        const int parent = h_parent[b], shared = h_shared_len[b];
+        if (parent < 0 || parent >= n_slots)
+            return efail("%s: parent %d of sequence %d is outside 0..%d", what, parent, b, n_slots - 1);
+        if (shared < 0 || shared > seqs.len[b])
+            return efail("%s: shared length %d of sequence %d is outside 0..its cache length %d", what, shared, b, seqs.len[b]);
+        const bool forked = parent != seqs.slot[b] && shared > 0;
+        from[b] = forked ? parent : seqs.slot[b];
+        below[b] = forked ? shared : seqs.len[b];
+        for (int a = 0; forked && a < n_seqs; ++a)   // a shared row must not be the one a parent appends in this call
+            if (seqs.slot[a] == parent && seqs.len[a] < shared)
+                return efail("%s: sequence %d shares %d rows of slot %d, which holds %d", what, b, shared, parent, seqs.len[a]);
+    }
+    int covered[DECODE_MAX_SEQS] = {};   // leading splits a group unit computes for the sequence
+    memset(&u, 0, sizeof(u));
+    n_units = n_seqs;
+    for (int b = 0; b < n_seqs; ++b) {
+        int members[DECODE_MAX_SEQS], count = 0, lowest = below[b];
+        for (int a = 0; a < n_seqs; ++a)
+            if (from[a] == from[b]) {
+                lowest = below[a] < lowest ? below[a] : lowest;
+                members[count++] = a;
+            }
+        const int splits = lowest / DECODE_SPLIT;
+        if (members[0] != b || splits == 0) continue;
+        // group units of FORK_UNIT_MEMBERS sequences, the rest one more if it is two or more: every unit holds at least
+        // two of the n_seqs sequences, so at most DECODE_MAX_SEQS / 2 units are made in all
+        for (int m0 = 0; count - m0 >= 2; m0 += FORK_UNIT_MEMBERS) {
+            const int n = count - m0 < FORK_UNIT_MEMBERS ? count - m0 : FORK_UNIT_MEMBERS;
+            u.n_members[n_units] = n;
+            u.s_end[n_units] = splits;
+            u.parent[n_units] = u.own[n_units] = from[b];
+            u.shared[n_units] = u.n_keys[n_units] = splits * DECODE_SPLIT;
+            for (int m = 0; m < n; ++m) {
+                u.member[n_units][m] = (int8_t)members[m0 + m];
+                covered[members[m0 + m]] = splits;
+            }
+            ++n_units;
+        }
+    }
+    for (int b = 0; b < n_seqs; ++b) {
+        u.n_members[b] = 1;
+        u.member[b][0] = (int8_t)b;
+        u.s_begin[b] = covered[b];
+        u.s_end[b] = seqs.len[b] / DECODE_SPLIT + 1;
+        u.parent[b] = from[b];
+        u.own[b] = seqs.slot[b];
+        u.shared[b] = from[b] == seqs.slot[b] ? 0 : below[b];
+        u.n_keys[b] = seqs.len[b] + 1;
+    }
+    return CRAG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t crag_enc_decode_workspace_bytes(int n_seqs, int hq, int max_len) {
+    if (n_seqs <= 0 || n_seqs > DECODE_MAX_SEQS || hq <= 0 || max_len <= 0) return 0;
+    const int64_t splits = ((int64_t)max_len + DECODE_SPLIT - 1) / DECODE_SPLIT;
+    const int64_t heads = (int64_t)n_seqs * hq;
+    // q_rot (bf16, rounded up to 16 bytes per head anyway) + partial o + partial (m, l)
+    return heads * CRAG_HEAD_DIM * 2 + heads * splits * CRAG_HEAD_DIM * 4 + heads * splits * 2 * 4;
+}
+
+int crag_enc_decode_attention(const uint16_t *qkv_new, const uint16_t *q_norm_w, const uint16_t *k_norm_w,
+                              const float *cos_sin, int max_pos, uint16_t *k_cache, uint16_t *v_cache, int n_slots,
+                              int max_len, const int32_t *h_slots, const int32_t *h_cache_len, int n_seqs, int hq, int hkv,
+                              float eps, float scale, void *workspace, int64_t workspace_bytes, uint16_t *out,
+                              void *stream) {
+    DecodeParams p;
+    const int rc = decode_setup("decode_attention", qkv_new, q_norm_w, k_norm_w, cos_sin, max_pos, k_cache, v_cache, n_slots,
+                                max_len, h_slots, h_cache_len, n_seqs, hq, hkv, eps, scale, workspace, workspace_bytes, out, p);
+    if (rc != CRAG_OK) return rc;
     int longest = 0;
     for (int b = 0; b < n_seqs; ++b) longest = p.seqs.len[b] > longest ? p.seqs.len[b] : longest;
     const int splits = longest / DECODE_SPLIT + 1;
@@ -362,6 +649,33 @@ int crag_enc_decode_attention(const uint16_t *qkv_new, const uint16_t *q_norm_w,
         hipLaunchKernelGGL(decode_split_kernel<4>, grid, dim3(DECODE_THREADS), 0, st, p);
     hipLaunchKernelGGL(decode_combine_kernel, dim3((unsigned)hq, (unsigned)n_seqs), dim3(CRAG_HEAD_DIM), 0, st, p);
     return hip_ok("decode_attention");
+}
+
+int crag_enc_decode_attention_shared(const uint16_t *qkv_new, const uint16_t *q_norm_w, const uint16_t *k_norm_w,
+                                     const float *cos_sin, int max_pos, uint16_t *k_cache, uint16_t *v_cache, int n_slots,
+                                     int max_len, const int32_t *h_slots, const int32_t *h_cache_len,
+                                     const int32_t *h_parent, const int32_t *h_shared_len, int n_seqs, int hq, int hkv,
+                                     float eps, float scale, void *workspace, int64_t workspace_bytes, uint16_t *out,
+                                     void *stream) {
+    DecodeParams p;
+    ForkUnits u;
+    int n_units = 0;
+    int rc = decode_setup("decode_attention_shared", qkv_new, q_norm_w, k_norm_w, cos_sin, max_pos, k_cache, v_cache, n_slots,
+                          max_len, h_slots, h_cache_len, n_seqs, hq, hkv, eps, scale, workspace, workspace_bytes, out, p);
+    if (rc == CRAG_OK) rc = fork_plan(p.seqs, h_parent, h_shared_len, n_seqs, n_slots, u, n_units);
+    if (rc != CRAG_OK) return rc;
+    int longest = 0;
+    for (int b = 0; b < n_seqs; ++b) longest = p.seqs.len[b] > longest ? p.seqs.len[b] : longest;
+    const int splits = longest / DECODE_SPLIT + 1;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(decode_prepare_kernel, dim3((unsigned)n_seqs), dim3(DECODE_THREADS), 0, st, p);
+    const dim3 grid((unsigned)splits, (unsigned)hkv, (unsigned)n_units);
+    if (hq / hkv == 2)
+        hipLaunchKernelGGL(decode_split_shared_kernel<2>, grid, dim3(DECODE_THREADS), 0, st, p, u);
+    else
+        hipLaunchKernelGGL(decode_split_shared_kernel<4>, grid, dim3(DECODE_THREADS), 0, st, p, u);
+    hipLaunchKernelGGL(decode_combine_kernel, dim3((unsigned)hq, (unsigned)n_seqs), dim3(CRAG_HEAD_DIM), 0, st, p);
+    return hip_ok("decode_attention_shared");
 }
 
 int crag_enc_lm_head(const uint16_t *hidden_states, const uint16_t *delta, const uint16_t *final_norm_w,

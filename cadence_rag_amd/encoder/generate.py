@@ -18,6 +18,10 @@ kernels) with a full-vocabulary head -- the in-process LLM behind /answer (caden
                         among the tokens the sequence's automaton state allows, on the logits prefill / extend / step
                         return; the states live on the device.  Under a grammar a sampled token is drawn among the
                         tokens the state allows, and crag_enc_grammar_advance moves the state behind it.
+  generate_samples(...) n continuations of one prompt from one prefill: slots 1..n-1 are forked from slot 0
+                        (KvCache.fork: no copy), and step reads a child's shared rows in its parent's slot through
+                        crag_enc_decode_attention_shared, which loads every wholly shared 128-key split once for two
+                        sequences of a parent.  generate's own token loop (_token_loop).
 
 The cache layout ([layer][slot][kv head][max_len][128] bf16, keys and values apart) sits behind KvCache.keys / .values.
 At most MAX_SEQS = 8 sequences decode at a time.
@@ -60,7 +64,14 @@ def plan_reuse(resident_ids: Sequence[int], prompt_ids: Sequence[int], min_reuse
 
 class KvCache:
     """Keys (normed, rotated) and raw values of every layer for n_slots sequences of up to max_len tokens.  `lens[slot]`
-    (host) is the number of tokens a slot holds."""
+    (host) is the number of tokens a slot holds.
+
+    Forks.  A slot can be a CHILD of another: its first shared[slot] logical rows are rows of slot parent[slot], never
+    copied, and only the rows behind them are its own (crag_enc_decode_attention_shared reads both in place).  A slot
+    that is not forked has parent[slot] == slot and shared[slot] == 0.  Chains are one deep: a parent is never a child.
+    The one rule that keeps a child's rows valid: whatever shortens or overwrites rows of a slot that children still
+    share (release(slot, keep): a prefill into it, a truncation below a child's shared length) empties those children
+    -- lens 0, no longer forked.  Appending to a parent is free: its new rows lie behind every child's shared length."""
 
     def __init__(self, n_layers: int, n_slots: int, hkv: int, max_len: int, device) -> None:
         shape = (n_layers, n_slots, hkv, max_len, 128)
@@ -68,17 +79,65 @@ class KvCache:
         self.v = torch.zeros(shape, dtype=torch.bfloat16, device=device)
         self.n_slots, self.max_len = int(n_slots), int(max_len)
         self.lens: List[int] = [0] * n_slots
+        self.parent: List[int] = list(range(n_slots))
+        self.shared: List[int] = [0] * n_slots
 
     def layer(self, i: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """The two [n_slots, hkv, max_len, 128] arrays crag_enc_decode_attention takes."""
         return self.k[i], self.v[i]
 
+    def _rows(self, store: torch.Tensor, layer: int, slot: int) -> torch.Tensor:
+        own = store[layer, slot, :, :self.lens[slot]].transpose(0, 1)
+        if not self.forked(slot):
+            return own
+        n = self.shared[slot]
+        return torch.cat([store[layer, self.parent[slot], :, :n].transpose(0, 1), own[n:]])
+
     def keys(self, layer: int, slot: int) -> torch.Tensor:
-        """[len, hkv, 128]: the cached keys of a slot, token-major."""
-        return self.k[layer, slot, :, :self.lens[slot]].transpose(0, 1)
+        """[len, hkv, 128]: the cached keys of a slot, token-major -- the logical rows: of a child the parent's first
+        `shared` rows, then its own (a copy; of a slot that is not forked a view of the cache)."""
+        return self._rows(self.k, layer, slot)
 
     def values(self, layer: int, slot: int) -> torch.Tensor:
-        return self.v[layer, slot, :, :self.lens[slot]].transpose(0, 1)
+        return self._rows(self.v, layer, slot)
+
+    # -- forks (host only) ----------------------------------------------------------------------------------------
+    def forked(self, slot: int) -> bool:
+        return self.shared[slot] > 0 and self.parent[slot] != slot
+
+    def children(self, slot: int) -> List[int]:
+        return [c for c in range(self.n_slots) if self.forked(c) and self.parent[c] == slot]
+
+    def unfork(self, slot: int) -> None:
+        self.parent[slot], self.shared[slot] = slot, 0
+
+    def release(self, slot: int, keep: int) -> None:
+        """Rows keep.. of `slot` are about to change or go: the children that share any of them are emptied."""
+        for c in self.children(slot):
+            if self.shared[c] > keep:
+                self.lens[c] = 0
+                self.unfork(c)
+
+    def fork(self, src: int, dst_slots: Sequence[int]) -> None:
+        """Every slot of dst_slots becomes a child that holds what src holds, without a copy: lens = lens[src], shared =
+        lens[src], parent = src -- or src's own parent when src is a child, which must then hold no row of its own.
+        What a dst held is gone (its own children are emptied).  ValueError: dst == src, a duplicate dst, a dst outside
+        the cache, a dst that is the parent of a live child other than the dsts themselves."""
+        src, dsts = int(src), [int(d) for d in dst_slots]
+        if not 0 <= src < self.n_slots or any(not 0 <= d < self.n_slots for d in dsts):
+            raise ValueError(f"fork takes slots in 0..{self.n_slots - 1}")
+        if src in dsts or len(set(dsts)) != len(dsts):
+            raise ValueError("fork: every dst must be a slot of its own, and none the source")
+        root = self.parent[src] if self.forked(src) else src
+        if root != src and self.lens[src] > self.shared[src]:
+            raise ValueError(f"fork: slot {src} is a child with rows of its own; only its parent's rows can be shared")
+        for d in dsts:
+            if d == root or any(c not in dsts and self.lens[c] > 0 for c in self.children(d)):
+                raise ValueError(f"fork: slot {d} is the parent of a live child")
+        for d in dsts:
+            self.release(d, 0)
+            self.lens[d] = self.lens[src]
+            self.parent[d], self.shared[d] = (root, self.lens[src]) if self.lens[src] else (d, 0)
 
     def append_prefill(self, layer: int, slot: int, k_rows: torch.Tensor, v_rows: torch.Tensor) -> None:
         """k_rows / v_rows [n, hkv, 128]: a prompt's keys and values as crag_enc_qk_rope_vt left them in qkv -> rows
@@ -141,6 +200,7 @@ class Qwen3Generator:
 
     supports_grammar = True   # generate / generate_text take grammar=TokenGrammar (answer.py asks before passing one)
     supports_sampling = True  # ... and sampling=SamplingParams
+    supports_samples = True   # generate_text_samples: n replies from one prefill
 
     def __init__(self, encoder: Qwen3Encoder, lm_head: torch.Tensor, tokenizer=None, *, max_context: Optional[int] = None,
                  max_seqs: int = MAX_SEQS, model_id: Optional[str] = None, prefix_cache: bool = False) -> None:
@@ -302,6 +362,9 @@ class Qwen3Generator:
             raise ValueError("every prompt needs at least one token")
         if max(lens) >= self.max_context:
             raise PromptTooLong(f"a prompt of {max(lens)} tokens leaves no room in a context of {self.max_context}")
+        for slot in slots:   # rows 0.. of the slot are overwritten: it is nobody's child and nobody's parent afterwards
+            self.cache.unfork(slot)
+            self.cache.release(slot, 0)
         batch = PackedBatch.build(lens, dev)
         t = batch.n_tokens
         x = self._embed(token_lists)
@@ -347,6 +410,8 @@ class Qwen3Generator:
         news = [len(tl) for tl in token_lists]
         if min(news) <= 0:
             raise ValueError("every sequence needs at least one new token")
+        if any(self.cache.forked(s) for s in slots):
+            raise ValueError("extend cannot continue a forked slot: the extend kernel reads no parent")
         held = [self.cache.lens[s] for s in slots]
         full = max(h + m for h, m in zip(held, news))
         if full >= self.max_context:
@@ -397,7 +462,12 @@ class Qwen3Generator:
         if not 0 <= n <= self.cache.lens[slot]:
             raise ValueError(f"slot {slot} holds {self.cache.lens[slot]} tokens: cannot truncate to {n}")
         self._forget_stale(slot)
+        self.cache.release(slot, n)      # children that share rows behind n are emptied
         self.cache.lens[slot] = n
+        if self.cache.forked(slot):
+            self.cache.shared[slot] = min(self.cache.shared[slot], n)
+            if n == 0:
+                self.cache.unfork(slot)
         del self.tokens[slot][n:]
 
     @torch.no_grad()
@@ -416,6 +486,17 @@ class Qwen3Generator:
         ids = torch.tensor([int(t) for t in tokens], dtype=torch.int32).to(dev)
         scale = 1.0 / math.sqrt(c.head_dim)
         width = c.q_size + 2 * c.kv_size
+        if any(self.cache.forked(s) for s in slots):   # a child reads its parent's rows in place
+            parents, shared = [self.cache.parent[s] for s in slots], [self.cache.shared[s] for s in slots]
+
+            def attention(qkv, L, kc, vc):
+                ops.decode_attention_shared(qkv, L["q_norm"], L["k_norm"], enc._cos_sin, kc, vc, slots, lens, parents,
+                                            shared, attn, c.num_heads, c.num_kv_heads, c.rms_norm_eps, scale,
+                                            self._workspace)
+        else:
+            def attention(qkv, L, kc, vc):
+                ops.decode_attention(qkv, L["q_norm"], L["k_norm"], enc._cos_sin, kc, vc, slots, lens, attn, c.num_heads,
+                                     c.num_kv_heads, c.rms_norm_eps, scale, self._workspace)
         skinny = None if self.force_library else enc._skinny_weights()
         if skinny is not None and not enc._skinny_v1:
             # the five-launch layer of Qwen3Encoder._forward_small_rows at 16 padded rows, the decode attention in the middle
@@ -434,8 +515,7 @@ class Qwen3Generator:
                 kc, vc = self.cache.layer(i)
                 ops.small_gemm(res_a, W["qkv"], qkv, n, width, 12, delta=delta0 if i == 0 else delta_d, norm_w=L["ln1"],
                                res_out=res_b, eps=c.rms_norm_eps)
-                ops.decode_attention(qkv, L["q_norm"], L["k_norm"], enc._cos_sin, kc, vc, slots, lens, attn, c.num_heads,
-                                     c.num_kv_heads, c.rms_norm_eps, scale, self._workspace)
+                attention(qkv, L, kc, vc)
                 ops.small_gemm(attn, W["o"], delta_o, n, c.hidden_size, 10)
                 ops.small_gemm(res_b, W["gate_up"], act, n, 2 * c.intermediate_size, 16, swiglu=True, delta=delta_o,
                                norm_w=L["ln2"], res_out=res_a, eps=c.rms_norm_eps)
@@ -448,8 +528,7 @@ class Qwen3Generator:
             attn = torch.empty(n, c.q_size, dtype=bf, device=dev)
 
             def attend(i, L, normed):
-                ops.decode_attention(F.linear(normed, L["qkv"]), L["q_norm"], L["k_norm"], enc._cos_sin, *self.cache.layer(i),
-                                     slots, lens, attn, c.num_heads, c.num_kv_heads, c.rms_norm_eps, scale, self._workspace)
+                attention(F.linear(normed, L["qkv"]), L, *self.cache.layer(i))
                 return attn
 
             hidden, delta = self._layers(x, attend)
@@ -502,10 +581,19 @@ class Qwen3Generator:
             logits = self.prefill(prompts)
         self.last_reuse = {"reused": list(keeps), "computed": [len(p) - keep for p, keep in zip(prompts, keeps)]} \
             if reuse_prefix else None
-        out: List[List[int]] = [[] for _ in prompts]
-        live = list(range(len(prompts)))          # slot b holds prompt b
-        accepted = [False] * len(prompts)
-        greedy, produced = self.last_tokens, 0    # produced: tokens every live sequence has so far, the step of the next draw
+        out, accepted = self._token_loop(pick, len(prompts), logits, self.last_tokens, max_new_tokens, stop)
+        self.last_grammar = {"accepted": accepted} if grammar is not None else None
+        return out
+
+    def _token_loop(self, pick: _Picker, n: int, logits: torch.Tensor, greedy: torch.Tensor, max_new_tokens: int,
+                    stop: set) -> Tuple[List[List[int]], List[bool]]:
+        """The steps of generate and generate_samples behind the prompt: sequence b sits in slot b, `logits` / `greedy`
+        [n] are what the prompt's last rows gave.  Returns (the new ids per sequence, whether each ended on a stop token
+        of the grammar's table)."""
+        out: List[List[int]] = [[] for _ in range(n)]
+        live = list(range(n))
+        accepted = [False] * n
+        produced = 0    # tokens every live sequence has so far, the step of the next draw
         while live:
             feed, keep = [], []
             for b, tok in zip(live, pick(live, logits, greedy, produced)):
@@ -524,8 +612,65 @@ class Qwen3Generator:
                 greedy, logits = self.step(feed)
                 produced += 1
         self.live = []
+        return out, accepted
+
+    def fork(self, src: int, dst_slots: Sequence[int]) -> None:
+        """KvCache.fork: the dst slots hold what src holds without a copy.  Their ids count as unknown, so plan_reuse
+        never keeps a child's rows."""
+        self.cache.fork(src, dst_slots)
+        for d in dst_slots:
+            self.tokens[int(d)] = [-1] * self.cache.lens[int(d)]
+
+    @torch.no_grad()
+    def generate_samples(self, prompt: Sequence[int], n: int, max_new_tokens: int, stop_ids: Sequence[int] = (),
+                         reuse_prefix: bool = False, grammar: Optional[TokenGrammar] = None,
+                         sampling=None, streams: Optional[Sequence[int]] = None) -> List[List[int]]:
+        """n (1..max_seqs) continuations of ONE prompt from one prefill: the prompt goes into slot 0 (prefill, or extend
+        behind what plan_reuse keeps under reuse_prefix, as in generate), slots 1..n-1 are forked from it, the one row
+        of logits serves every sequence's first pick, and generate's token loop runs over the n slots: a child reads
+        the prompt's rows in the parent's slot (crag_enc_decode_attention_shared) and appends to its own.  Sequence i
+        draws on streams[i] (default i).  A sequence that stops -- slot 0 too -- leaves the others running on its rows.
+        Afterwards the children are empty and slot 0 holds the prompt and continuation 0 with their ids, for a later
+        reuse_prefix.  last_reuse / last_grammar hold one entry per sample (the prompt's rows were reused / computed
+        once, for all of them).  n = 1 is generate([prompt], ...)."""
+        n, max_new_tokens = int(n), int(max_new_tokens)
+        if not 1 <= n <= self.max_seqs:
+            raise ValueError(f"generate_samples takes n in 1..{self.max_seqs}")
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be positive")
+        room = self.max_context - max_new_tokens
+        if len(prompt) > room:
+            raise PromptTooLong(f"a prompt of {len(prompt)} tokens does not fit: max_context {self.max_context} - "
+                                f"max_new_tokens {max_new_tokens} leaves {room}")
+        pick = _Picker(self, n, grammar, sampling, streams)
+        keep = plan_reuse(self.resident(0), prompt, PREFIX_MIN_REUSE) if reuse_prefix else 0
+        if keep:
+            self.truncate(0, keep)
+            logits = self.extend([list(prompt[keep:])])
+        else:
+            logits = self.prefill([prompt])
+        self.last_reuse = {"reused": [keep] * n, "computed": [len(prompt) - keep] * n} if reuse_prefix else None
+        greedy = self.last_tokens
+        try:
+            if n > 1:
+                self.fork(0, range(1, n))
+                logits, greedy = logits.repeat(n, 1), greedy.repeat(n)
+            out, accepted = self._token_loop(pick, n, logits, greedy, max_new_tokens, {int(s) for s in stop_ids})
+        finally:
+            self.live = []
+            for child in range(1, n):
+                self.truncate(child, 0)
         self.last_grammar = {"accepted": accepted} if grammar is not None else None
         return out
+
+    def generate_text_samples(self, messages: Sequence[Dict[str, str]], n: int, max_new_tokens: int,
+                              grammar: Optional[TokenGrammar] = None, sampling: Optional[SamplingParams] = None,
+                              streams: Optional[Sequence[int]] = None) -> List[str]:
+        """One chat -> n replies as text from one prefill (generate_samples), reply i drawn on noise stream streams[i]."""
+        ids = self.generate_samples(self.chat_ids(messages), n, max_new_tokens, self.stop_ids(),
+                                    reuse_prefix=self.prefix_cache, grammar=grammar, sampling=sampling, streams=streams)
+        tok = self._tokenizer()
+        return [tok.decode(x, skip_special_tokens=True) for x in ids]
 
     def generate_text(self, messages: Sequence[Dict[str, str]], max_new_tokens: int,
                       grammar: Optional[TokenGrammar] = None, sampling: Optional[SamplingParams] = None,

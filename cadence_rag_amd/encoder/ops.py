@@ -345,6 +345,34 @@ def decode_attention(qkv_new, q_w, k_w, cos_sin, k_cache, v_cache, slots, cache_
     return out
 
 
+def decode_attention_shared(qkv_new, q_w, k_w, cos_sin, k_cache, v_cache, slots, cache_len, parents, shared_len, out,
+                            hq: int, hkv: int, eps: float, scale: float, workspace):
+    """decode_attention over forked sequences (crag_enc_decode_attention_shared).  parents / shared_len: HOST ints per
+    sequence -- logical row j of sequence b is row j of slot parents[b] when j < shared_len[b] and of slots[b] otherwise;
+    parents[b] == slots[b] or shared_len[b] == 0: not forked.  The new key and value go to row cache_len of slots[b].
+    The bits of out and of the appended rows are decode_attention's on private copies of the logical rows; two
+    sequences of one parent read every wholly shared split with one load.  The workspace is decode_workspace's."""
+    _req(qkv_new, torch.bfloat16, "qkv_new"); _req(cos_sin, torch.float32, "cos_sin"); _req(out, torch.bfloat16, "out")
+    _req(k_cache, torch.bfloat16, "k_cache"); _req(v_cache, torch.bfloat16, "v_cache")
+    _req(q_w, torch.bfloat16, "q_w"); _req(k_w, torch.bfloat16, "k_w"); _req(workspace, torch.uint8, "workspace")
+    n = len(slots)
+    if len(cache_len) != n or len(parents) != n or len(shared_len) != n:
+        raise ValueError("slots, cache_len, parents and shared_len need one entry per sequence")
+    n_slots, kv_heads, max_len, dim = k_cache.shape
+    if v_cache.shape != k_cache.shape or kv_heads != hkv or dim != 128:
+        raise ValueError("k_cache and v_cache must both be [n_slots, hkv, max_len, 128]")
+    if n <= _native.CRAG_DECODE_MAX_SEQS and (qkv_new.shape[0] < n or out.shape[0] < n
+                                              or qkv_new.shape[1] != (hq + 2 * hkv) * 128 or out.shape[1] != hq * 128):
+        raise ValueError("qkv_new must be [n, (hq + 2 hkv) * 128] and out [n, hq * 128]")
+    h_slots, h_lens, h_parents, h_shared = ((ctypes.c_int32 * max(n, 1))(*[int(x) for x in xs])
+                                            for xs in (slots, cache_len, parents, shared_len))
+    _native.check(_native.load().crag_enc_decode_attention_shared(
+        _p(qkv_new), _p(q_w), _p(k_w), _p(cos_sin), int(cos_sin.shape[0]), _p(k_cache), _p(v_cache), int(n_slots),
+        int(max_len), h_slots, h_lens, h_parents, h_shared, n, int(hq), int(hkv), float(eps), float(scale), _p(workspace),
+        int(workspace.numel()), _p(out), _stream()), "crag_enc_decode_attention_shared")
+    return out
+
+
 def lm_head(hidden_states, final_norm_w, lm, logits, token, eps: float, delta=None, banned=None):
     """Final RMSNorm of hidden_states [n <= 8, hidden] (+ delta), fp32 logits [n, vocab] against lm [vocab, hidden] and the
     greedy token [n] int32: lowest id among the maxima, `banned` (int32 device list) left out (crag_enc_lm_head)."""

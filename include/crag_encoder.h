@@ -213,6 +213,23 @@ int crag_enc_rerank_head(const uint16_t *hidden_states, const uint16_t *delta, c
  *   workspace: crag_enc_decode_workspace_bytes(n_seqs, hq, max_len) bytes of device scratch, 16-byte aligned.
  *   CRAG_EINVAL, nothing enqueued: a NULL pointer, n_seqs outside 1..8, a length < 0 or >= max_len (or >= max_pos, the
  *   rows of cos_sin), a slot outside 0..n_slots - 1 or named twice in the call.  CRAG_E2BIG: the workspace is too small.
+ * crag_enc_decode_attention_shared: crag_enc_decode_attention over FORKED sequences, which share leading cache rows
+ *   without holding copies of them.  Two more HOST arrays per sequence: sequence b reads its logical row j from slot
+ *   h_parent[b] when j < h_shared_len[b] and from its own slot h_slots[b] otherwise; the new token is appended at row
+ *   cache_len of its own slot.  h_parent[b] == h_slots[b] or h_shared_len[b] == 0: not forked.  Rows below shared_len of
+ *   a forked sequence's own slot are never read, nor any row at or beyond cache_len + 1.
+ *   Output bits and appended bits are those crag_enc_decode_attention gives on a slot that holds a private copy of the
+ *   same logical rows: the same splits, every row read by the same lanes and dotted in the same order, the same
+ *   combine; only the address of a row changes, and how many sequences one load serves.  The sequences of a call that
+ *   read one parent (the parent itself included when it is in the call) form a group: a split that lies wholly below
+ *   the shared length of every member is computed by one workgroup per (split, kv head, two members of the group -- the
+ *   kernel takes up to eight; two is what measures best), which loads each key and value row once for its
+ *   members' query heads.  The other splits run per sequence.  Three launches, no atomics; the workspace of
+ *   crag_enc_decode_workspace_bytes.
+ *   CRAG_EINVAL, nothing enqueued: every refusal of crag_enc_decode_attention; a NULL h_parent / h_shared_len; a parent
+ *   outside 0..n_slots - 1; a shared_len outside 0..cache_len; a forked sequence whose parent slot is a sequence of the
+ *   call with cache_len < that shared_len (a shared row would be written during the call).  A parent slot that is not
+ *   in the call is allowed.
  * crag_enc_lm_head: per row r < n_rows (1..8): x = bf16(hidden_states[r] + delta[r]) (delta nullable), the final RMSNorm
  *   with crag_enc_rerank_head's roundings, logits[r, v] = fp32 dot with lm_head[v] for EVERY v < vocab (lm_head
  *   [vocab, hidden] bf16; a tied model passes embed_tokens), token[r] = the lowest id among the maxima of logits[r]
@@ -228,6 +245,12 @@ int crag_enc_decode_attention(const uint16_t *qkv_new, const uint16_t *q_norm_w,
                               int max_len, const int32_t *h_slots, const int32_t *h_cache_len, int n_seqs, int hq, int hkv,
                               float eps, float scale, void *workspace, int64_t workspace_bytes, uint16_t *out,
                               void *stream);
+int crag_enc_decode_attention_shared(const uint16_t *qkv_new, const uint16_t *q_norm_w, const uint16_t *k_norm_w,
+                                     const float *cos_sin, int max_pos, uint16_t *k_cache, uint16_t *v_cache, int n_slots,
+                                     int max_len, const int32_t *h_slots, const int32_t *h_cache_len,
+                                     const int32_t *h_parent, const int32_t *h_shared_len, int n_seqs, int hq, int hkv,
+                                     float eps, float scale, void *workspace, int64_t workspace_bytes, uint16_t *out,
+                                     void *stream);
 int crag_enc_lm_head(const uint16_t *hidden_states, const uint16_t *delta, const uint16_t *final_norm_w,
                      const uint16_t *lm_head, float *logits, int32_t *token, const int32_t *banned, int n_banned,
                      int n_rows, int hidden, int64_t vocab, float eps, void *stream);
