@@ -29,6 +29,7 @@ CRAG_FACET_MAX_NAMESPACES = 16
 CRAG_FACET_MAX_TOP = 64
 CRAG_E2BIG = -5
 CRAG_DECODE_MAX_SEQS = 8
+CRAG_DECODE_MAX_ROWS = 8
 CRAG_DECODE_SPLIT = 128
 CRAG_LM_HEAD_MAX_BANNED = 64
 CRAG_EXTEND_BLOCK = 32
@@ -137,6 +138,9 @@ SIGNATURES = {
     "crag_enc_decode_attention_shared": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _P,
                                                     _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _P, _c.c_int64,
                                                     _P, _P]),
+    "crag_enc_decode_attention_rows": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _P, _P,
+                                                  _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _P, _c.c_int64,
+                                                  _P, _P]),
     "crag_enc_lm_head": (_c.c_int, [_P, _P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_float, _P]),
     "crag_enc_extend_workspace_bytes": (_c.c_int64, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "crag_enc_extend_attention": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _c.c_int,

@@ -22,6 +22,11 @@ is not INSUFFICIENT_EVIDENCE goes into the repair turn.  notes.samples = {"drawn
 attempt; llm_calls counts calls, not candidates.  An HTTP service, or a native model without supports_samples, gives one
 candidate as ever and notes.samples = {"applied": False}.  With one sample nothing changes.
 
+Speculative decoding (`speculate` of the request, ANSWER_SPECULATE; 0..7, off at 0): a native model with
+supports_speculation verifies up to that many prompt-lookup drafts per forward (cadence_rag_amd.speculate); the reply
+does not depend on it.  notes.speculation echoes the model's last_speculation; anything else decodes as ever and says
+notes.speculation = {"applied": False}.  With 0 and no field the response and the notes are what they were.
+
 ANSWER_CONSTRAINED (native backend, a model with supports_grammar): the reply is decoded under the citation grammar of
 the evidence ids in the prompt (cadence_rag_amd.grammar.citation_grammar), which makes a failing answer unrepresentable
 whenever the model stops by itself.  The gate and the repair loop run unchanged on whatever comes back.
@@ -187,7 +192,7 @@ def _chat_http(messages: List[Dict[str, str]], max_new_tokens: int, sampling: Op
 
 
 def _chat_native(messages: List[Dict[str, str]], max_new_tokens: int, grammar: Optional[TokenGrammar] = None,
-                 sampling: Optional[SamplingParams] = None, stream: int = 0) -> Tuple[str, str]:
+                 sampling: Optional[SamplingParams] = None, stream: int = 0, speculate: int = 0) -> Tuple[str, str]:
     """ValueError (the prompt does not fit) passes through to the caller, which drops evidence."""
     llm = _llm
     if llm is None:
@@ -197,6 +202,8 @@ def _chat_native(messages: List[Dict[str, str]], max_new_tokens: int, grammar: O
             extra: Dict[str, Any] = {} if grammar is None else {"grammar": grammar}
             if sampling is not None:
                 extra.update(sampling=sampling, stream=int(stream))
+            if speculate:
+                extra.update(speculate=int(speculate))
             text = llm.generate_text(messages, max_new_tokens, **extra)
     except (AnswerClientError, ValueError):
         raise
@@ -209,9 +216,9 @@ def _chat_native(messages: List[Dict[str, str]], max_new_tokens: int, grammar: O
 
 def chat_samples(messages: List[Dict[str, str]], n: int, max_new_tokens: Optional[int] = None,
                  grammar: Optional[TokenGrammar] = None, sampling: Optional[SamplingParams] = None,
-                 streams: Optional[Sequence[int]] = None) -> Tuple[List[str], str]:
+                 streams: Optional[Sequence[int]] = None, speculate: int = 0) -> Tuple[List[str], str]:
     """(n replies, model id) from the registered native model's generate_text_samples (native_samples()).  ValueError
-    (the prompt does not fit) passes through, as from chat()."""
+    (the prompt does not fit) passes through, as from chat().  speculate > 0: a model with supports_speculation only."""
     llm = _llm
     if not llm_enabled() or not _is_native(settings.llm_base_url) or llm is None:
         raise AnswerClientError("native LLM is not loaded (call set_llm)")
@@ -219,7 +226,8 @@ def chat_samples(messages: List[Dict[str, str]], n: int, max_new_tokens: Optiona
         with _llm_lock:
             texts = llm.generate_text_samples(messages, int(n), int(max_new_tokens or settings.llm_max_new_tokens),
                                               grammar=grammar, sampling=sampling,
-                                              streams=None if streams is None else [int(x) for x in streams])
+                                              streams=None if streams is None else [int(x) for x in streams],
+                                              **({"speculate": int(speculate)} if speculate else {}))
     except (AnswerClientError, ValueError):
         raise
     except Exception as exc:  # noqa: BLE001 - callers rely on a single error type
@@ -230,15 +238,16 @@ def chat_samples(messages: List[Dict[str, str]], n: int, max_new_tokens: Optiona
 
 
 def chat(messages: List[Dict[str, str]], max_new_tokens: Optional[int] = None, grammar: Optional[TokenGrammar] = None,
-         sampling: Optional[SamplingParams] = None, stream: int = 0) -> Tuple[str, str]:
+         sampling: Optional[SamplingParams] = None, stream: int = 0, speculate: int = 0) -> Tuple[str, str]:
     """(reply, model id) from the configured LLM.  grammar: native backend only (an HTTP service cannot take one).
+    speculate > 0: native backend only, a model with supports_speculation (native_speculation()).
     sampling: None is greedy; a native model must have supports_sampling (native_sampling()), and draws on noise stream
     `stream`; an HTTP service gets temperature, top_p and seed."""
     if not llm_enabled():
         raise AnswerClientError("LLM_BASE_URL is not configured")
     budget = int(max_new_tokens or settings.llm_max_new_tokens)
     if _is_native(settings.llm_base_url):
-        return _chat_native(messages, budget, grammar, sampling, stream)
+        return _chat_native(messages, budget, grammar, sampling, stream, speculate)
     return _chat_http(messages, budget, sampling)
 
 
@@ -256,6 +265,21 @@ def native_sampling() -> bool:
 def native_samples() -> bool:
     """The backend is native and the registered model has generate_text_samples."""
     return _is_native(settings.llm_base_url) and bool(getattr(_llm, "supports_samples", False))
+
+
+def native_speculation() -> bool:
+    """The backend is native and the registered model takes speculate=k."""
+    return _is_native(settings.llm_base_url) and bool(getattr(_llm, "supports_speculation", False))
+
+
+def speculate_for(request: Any) -> int:
+    """The request's `speculate` over ANSWER_SPECULATE: drafted tokens verified per forward.  AnswerRequestError: outside
+    0..7."""
+    given = getattr(request, "speculate", None)
+    k = settings.answer_speculate if given is None else given
+    if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= 7:
+        raise AnswerRequestError(f"speculate must be an integer in 0..7 (got {k!r})")
+    return k
 
 
 def samples_for(request: Any) -> int:
@@ -302,8 +326,8 @@ def _grammar_for(items: Sequence[Dict[str, Any]], notes: Dict[str, Any]) -> Opti
 # ---- /answer ----------------------------------------------------------------------------------------------------
 @dataclass
 class AnswerRequest(_retrieve.RetrieveRequest):
-    """The /retrieve request plus echo_evidence, the optional sampling fields and `samples`, the candidates per attempt
-    (None: the ANSWER_* default)."""
+    """The /retrieve request plus echo_evidence, the optional sampling fields, `samples`, the candidates per attempt, and
+    `speculate`, the drafts per forward (None: the ANSWER_* default)."""
     echo_evidence: bool = False
     temperature: Optional[float] = None
     top_p: Optional[float] = None
@@ -311,6 +335,7 @@ class AnswerRequest(_retrieve.RetrieveRequest):
     min_p: Optional[float] = None
     seed: Optional[int] = None
     samples: Optional[int] = None
+    speculate: Optional[int] = None
 
 
 def _evidence_items(pack: Dict[str, Any]) -> List[Dict[str, Any]]:
@@ -348,6 +373,7 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
         raise AnswerClientError("LLM_BASE_URL is not configured")
     sampling = sampling_for(request)
     n_samples = samples_for(request)
+    speculate = speculate_for(request)
     pack_request = _retrieve.RetrieveRequest(query=request.query, intent=request.intent, filters=request.filters,
                                              budget=request.budget, return_style="evidence_pack_json", debug=request.debug,
                                              facets=request.facets, facet_top=request.facet_top)
@@ -365,6 +391,9 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
     multi = n_samples > 1 and sampling is not None and native_samples()
     if n_samples > 1 and not multi:
         notes["samples"] = {"applied": False}
+    if speculate and not native_speculation():   # off by default: no such note
+        notes["speculation"] = {"applied": False}
+        speculate = 0
     out: Dict[str, Any] = {"query_id": pack["query_id"], "answer": None, "status": STATUS_INSUFFICIENT, "citations": [],
                            "repairs": 0, "model": None, "notes": notes}
     if getattr(request, "echo_evidence", False):
@@ -386,9 +415,12 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
                 if multi:
                     texts, model = chat_samples(build_messages(query, items, turns), n_samples, grammar=grammar,
                                                 sampling=sampling,
-                                                streams=[attempt * n_samples + i for i in range(n_samples)])
+                                                streams=[attempt * n_samples + i for i in range(n_samples)],
+                                                speculate=speculate)
                 else:
                     extra = {} if sampling is None else {"sampling": sampling, "stream": attempt}
+                    if speculate:
+                        extra["speculate"] = speculate
                     text, model = chat(build_messages(query, items, turns), grammar=grammar, **extra)
                     texts = [text]
             except ValueError as exc:   # the prompt does not fit the model's context: the lowest-ranked item goes
@@ -405,6 +437,8 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
                 # (under `multi` every candidate reports the one prompt's rows: they were reused once)
                 notes["prefix_reused_tokens"] = notes.get("prefix_reused_tokens", 0) + \
                     int(reuse["reused"][0] if multi else sum(reuse["reused"]))
+            if speculate:   # what the last call drafted and kept
+                notes["speculation"] = getattr(_llm, "last_speculation", None)
             return texts
 
     max_repairs = max(int(settings.answer_max_repairs), 0)

@@ -79,6 +79,10 @@ class Settings:
     # candidates drawn per attempt (1..8; a request's `samples` overrides it).  Above 1 -- sampling on, a native model with
     # generate_text_samples -- one prefill serves all of them and the first that passes the citation check is the answer
     answer_samples: int = 1
+    # speculative decoding of /answer (0..7; a request's `speculate` overrides it): a native model with
+    # supports_speculation verifies up to that many prompt-lookup drafts per forward.  The reply does not depend on it;
+    # 0 = off, the plain token loop
+    answer_speculate: int = 0
 
     def __post_init__(self) -> None:
         if self.rerank_device < 0:

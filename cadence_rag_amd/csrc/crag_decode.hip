@@ -13,6 +13,10 @@
 //                               one parent form group units, each of which loads every row of a wholly shared split
 //                               once for its members' query heads; every sequence is a unit of its own for its other
 //                               splits.
+//   crag_enc_decode_attention_rows     the same with SEVERAL new rows per sequence (a pending token and its drafts): row i
+//                               sees the keys up to its own position, the rows appended before it in the call among
+//                               them.  A unit of the split launch is a run of consecutive rows of one sequence, with
+//                               one key more for each member.
 //
 // Nothing here depends on the number of sequences, on the slot or on a launch size chosen at run time: a split is
 // always DECODE_SPLIT keys, its keys are always walked by the same lanes in the same order, and the splits are summed
@@ -203,6 +207,24 @@ struct ForkUnits {
     int32_t parent[FORK_MAX_UNITS], own[FORK_MAX_UNITS];   // slots
     int32_t shared[FORK_MAX_UNITS], n_keys[FORK_MAX_UNITS];
     int8_t member[FORK_MAX_UNITS][DECODE_MAX_SEQS];         // sequence indices
+    static constexpr bool ragged = false;                   // every member of a unit sees the same keys
+    __device__ int row(int unit, int m) const { return member[unit][m]; }
+    __device__ int keys(int unit, int) const { return n_keys[unit]; }
+};
+
+// The units of crag_enc_decode_attention_rows: up to M consecutive new rows of ONE sequence.  Member m is row row0 + m
+// of the call and sees one key more than member m - 1: n_keys is what the LAST member sees.
+constexpr int ROWS_MAX = CRAG_DECODE_MAX_ROWS;
+static_assert(ROWS_MAX == DECODE_MAX_SEQS, "the rows of a call travel in DecodeSeqs, one entry per row");
+struct RowUnits {
+    int32_t n_members[ROWS_MAX];
+    int32_t s_begin[ROWS_MAX], s_end[ROWS_MAX];
+    int32_t parent[ROWS_MAX], own[ROWS_MAX];   // slots
+    int32_t shared[ROWS_MAX], n_keys[ROWS_MAX];
+    int32_t row0[ROWS_MAX];
+    static constexpr bool ragged = true;
+    __device__ int row(int unit, int m) const { return row0[unit] + m; }
+    __device__ int keys(int unit, int m) const { return n_keys[unit] - (n_members[unit] - 1 - m); }
 };
 
 // Lane i of every 16-lane row <- lane (i + N) % 16 of the row, on the VALU (DPP row_ror).  In a butterfly over the
@@ -214,16 +236,22 @@ __device__ __forceinline__ float row_ror(float v) {
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x120 + N, 0xF, 0xF, true));
 }
 
-template <int G>
-__global__ __launch_bounds__(DECODE_THREADS) void decode_split_shared_kernel(const DecodeParams p, const ForkUnits u) {
-    __shared__ float sc[FORK_UNIT_MEMBERS][G][DECODE_SPLIT];    // raw dot products, then the weights
+// The body serves both kinds of unit (Units = ForkUnits or RowUnits) with up to M members.  Under Units::ragged member
+// m sees the keys below u.keys(unit, m) only, ascending in m up to the unit's n_keys: a key behind them scores -inf for
+// that member and its value is skipped, as decode_split_kernel does past its n_keys; the members that see no key of
+// the split -- the first m_first -- are left out of it, as decode_split_kernel leaves a sequence out.
+template <int G, int M, class Units>
+__device__ __forceinline__ void split_units(const DecodeParams &p, const Units &u) {
+    __shared__ float sc[M][G][DECODE_SPLIT];                    // raw dot products, then the weights
     __shared__ float red[DECODE_GROUPS][G][CRAG_HEAD_DIM];      // 32 KiB at G = 4
-    __shared__ float ml[FORK_UNIT_MEMBERS][G][2];
-    __shared__ __align__(16) u16 qs[FORK_UNIT_MEMBERS][G][CRAG_HEAD_DIM];   // the members' rotated queries
+    __shared__ float ml[M][G][2];
+    __shared__ __align__(16) u16 qs[M][G][CRAG_HEAD_DIM];       // the members' rotated queries
     const int s = blockIdx.x, kvh = blockIdx.y, unit = blockIdx.z;
     if (s < u.s_begin[unit] || s >= u.s_end[unit]) return;   // (uniform)
     const int n_mem = u.n_members[unit], n_keys = u.n_keys[unit], shared = u.shared[unit];
     const int k0 = s * DECODE_SPLIT;
+    int m_first = 0;
+    if constexpr (Units::ragged) m_first = k0 - n_keys + n_mem > 0 ? k0 - n_keys + n_mem : 0;
     const int grp = threadIdx.x >> 4, sub = threadIdx.x & 15;
     const u16 *kp = p.k_cache + kv_row(p.hkv, p.max_len, u.parent[unit], kvh, 0);
     const u16 *vp = p.v_cache + kv_row(p.hkv, p.max_len, u.parent[unit], kvh, 0);
@@ -233,7 +261,7 @@ __global__ __launch_bounds__(DECODE_THREADS) void decode_split_shared_kernel(con
     for (int i = threadIdx.x; i < n_mem * G * 16; i += DECODE_THREADS) {
         const int m = i / (G * 16), g = i / 16 % G, ch = i % 16;
         *reinterpret_cast<Pack8 *>(&qs[m][g][ch * 8]) = *reinterpret_cast<const Pack8 *>(
-            p.q_rot + ((int64_t)u.member[unit][m] * p.hq + kvh * G + g) * CRAG_HEAD_DIM + ch * 8);
+            p.q_rot + ((int64_t)u.row(unit, m) * p.hq + kvh * G + g) * CRAG_HEAD_DIM + ch * 8);
     }
     Pack8 rows[DECODE_ITERS];
 #pragma unroll
@@ -246,7 +274,8 @@ __global__ __launch_bounds__(DECODE_THREADS) void decode_split_shared_kernel(con
     }
     __syncthreads();
     // scores
-    for (int m = 0; m < n_mem; ++m) {
+    for (int m = m_first; m < n_mem; ++m) {
+        const int m_keys = Units::ragged ? u.keys(unit, m) : n_keys;
         float q[G][8];
 #pragma unroll
         for (int g = 0; g < G; ++g) {
@@ -277,7 +306,7 @@ __global__ __launch_bounds__(DECODE_THREADS) void decode_split_shared_kernel(con
             for (int it = 0; it < DECODE_ITERS; ++it) {
                 const int j = it * DECODE_GROUPS + grp;
 #pragma unroll
-                for (int g = 0; g < G; ++g) sc[m][g][j] = k0 + j < n_keys ? d[it][g] : -INFINITY;
+                for (int g = 0; g < G; ++g) sc[m][g][j] = k0 + j < m_keys ? d[it][g] : -INFINITY;
             }
         }
     }
@@ -293,10 +322,10 @@ __global__ __launch_bounds__(DECODE_THREADS) void decode_split_shared_kernel(con
     // their reductions overlap (the strides 32 and 16 cross the 16-lane rows: shuffles; below them row_ror)
     {
         constexpr int WAVES = DECODE_THREADS / 64;
-        constexpr int SM_HEADS = FORK_UNIT_MEMBERS * G >= 4 * WAVES ? 4 : FORK_UNIT_MEMBERS * G > WAVES ? 2 : 1;
+        constexpr int SM_HEADS = M * G >= 4 * WAVES ? 4 : M * G > WAVES ? 2 : 1;
         const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
         const int n_heads = n_mem * G;
-        for (int h0 = w; h0 < n_heads; h0 += SM_HEADS * WAVES) {   // (uniform in the wave)
+        for (int h0 = m_first * G + w; h0 < n_heads; h0 += SM_HEADS * WAVES) {   // (uniform in the wave)
             float x[SM_HEADS][DECODE_SPLIT / 64], mx[SM_HEADS], l[SM_HEADS];
 #pragma unroll
             for (int t = 0; t < SM_HEADS; ++t) {
@@ -349,7 +378,8 @@ __global__ __launch_bounds__(DECODE_THREADS) void decode_split_shared_kernel(con
     }
     __syncthreads();
     // weighted values, member after member
-    for (int m = 0; m < n_mem; ++m) {
+    for (int m = m_first; m < n_mem; ++m) {
+        const int m_keys = Units::ragged ? u.keys(unit, m) : n_keys;
         float acc[G][8];
 #pragma unroll
         for (int g = 0; g < G; ++g)
@@ -358,7 +388,7 @@ __global__ __launch_bounds__(DECODE_THREADS) void decode_split_shared_kernel(con
 #pragma unroll
         for (int it = 0; it < DECODE_ITERS; ++it) {
             const int j = it * DECODE_GROUPS + grp;
-            if (k0 + j < n_keys) {
+            if (k0 + j < m_keys) {
 #pragma unroll
                 for (int g = 0; g < G; ++g) {
                     const float pr = sc[m][g][j];
@@ -367,13 +397,13 @@ __global__ __launch_bounds__(DECODE_THREADS) void decode_split_shared_kernel(con
                 }
             }
         }
-        if (m) __syncthreads();   // the sums of the member before have been read
+        if (m > m_first) __syncthreads();   // the sums of the member before have been read
 #pragma unroll
         for (int g = 0; g < G; ++g)
 #pragma unroll
             for (int e = 0; e < 8; ++e) red[grp][g][sub * 8 + e] = acc[g][e];
         __syncthreads();
-        const int b = u.member[unit][m];
+        const int b = u.row(unit, m);
         for (int i = threadIdx.x; i < G * CRAG_HEAD_DIM; i += DECODE_THREADS) {
             const int g = i / CRAG_HEAD_DIM, d = i % CRAG_HEAD_DIM;
             float o = 0.f;
@@ -384,6 +414,24 @@ __global__ __launch_bounds__(DECODE_THREADS) void decode_split_shared_kernel(con
             if (d < 2) p.part_ml[part * 2 + d] = ml[m][g][d];
         }
     }
+}
+
+template <int G>
+__global__ __launch_bounds__(DECODE_THREADS) void decode_split_shared_kernel(const DecodeParams p, const ForkUnits u) {
+    split_units<G, FORK_UNIT_MEMBERS>(p, u);
+}
+
+// Rows one unit of crag_enc_decode_attention_rows serves.  Measured at 32 / 8 heads with a library built at each value
+// (profiles/speculate_bench.jsonl, the lines with "unit_rows"): 8 rows of one sequence take 18 / 21 / 43 us
+// at 128 / 1024 / 4096 cached tokens in units of 2, 19 / 23 / 45 in units of 1, 23 / 25 / 47 in units of 4 and 34 / 36 /
+// 51 in units of 8 -- as with forks a unit works its members off one after the other, and a launch of at most 33 splits
+// x 8 kv heads has too few workgroups to hide that.  Two is the size that loses nowhere; the kernel takes 1..8.
+constexpr int ROWS_UNIT_MEMBERS = 2;
+static_assert(ROWS_UNIT_MEMBERS >= 1 && ROWS_UNIT_MEMBERS <= ROWS_MAX, "a unit holds 1..8 rows");
+
+template <int G>
+__global__ __launch_bounds__(DECODE_THREADS) void decode_split_rows_kernel(const DecodeParams p, const RowUnits u) {
+    split_units<G, ROWS_UNIT_MEMBERS>(p, u);
 }
 
 // combine: workgroup (q head, sequence), 128 threads = the 128 output elements; the splits in ascending order
@@ -501,60 +549,112 @@ __global__ __launch_bounds__(ARGMAX_THREADS) void lm_argmax_kernel(const float *
     if (threadIdx.x == 0) token[blockIdx.x] = best.id;
 }
 
-// the checks the two attention entries share, and the parameter block they launch with; `what` names the entry
-int decode_setup(const char *what, const uint16_t *qkv_new, const uint16_t *q_norm_w, const uint16_t *k_norm_w,
-                 const float *cos_sin, int max_pos, uint16_t *k_cache, uint16_t *v_cache, int n_slots, int max_len,
-                 const int32_t *h_slots, const int32_t *h_cache_len, int n_seqs, int hq, int hkv, float eps, float scale,
-                 void *workspace, int64_t workspace_bytes, uint16_t *out, DecodeParams &p) {
-    if (!qkv_new || !q_norm_w || !k_norm_w || !cos_sin || !k_cache || !v_cache || !h_slots || !h_cache_len || !workspace ||
-        !out)
+// The checks the three attention entries share, in the order they are made.  `what` names the entry.
+struct DecodeArgs {
+    const uint16_t *qkv_new, *q_norm_w, *k_norm_w;
+    const float *cos_sin;
+    int max_pos;
+    uint16_t *k_cache, *v_cache;
+    int n_slots, max_len;
+    const int32_t *h_slots, *h_cache_len;
+    int n_seqs, hq, hkv;
+    float eps, scale;
+    void *workspace;
+    int64_t workspace_bytes;
+    uint16_t *out;
+};
+
+int decode_check_shape(const char *what, const DecodeArgs &a) {
+    if (!a.qkv_new || !a.q_norm_w || !a.k_norm_w || !a.cos_sin || !a.k_cache || !a.v_cache || !a.h_slots || !a.h_cache_len ||
+        !a.workspace || !a.out)
         return efail("%s: NULL pointer", what);
-    if (n_seqs < 1 || n_seqs > DECODE_MAX_SEQS)
-        return efail("%s: n_seqs must be in 1..%d (got %d)", what, DECODE_MAX_SEQS, n_seqs);
-    if (hq <= 0 || hkv <= 0 || hq % hkv || (hq / hkv != 2 && hq / hkv != 4))
-        return efail("%s: hq / hkv must be 2 or 4 (got %d / %d)", what, hq, hkv);
-    if (n_slots <= 0 || max_len <= 0 || max_pos <= 0) return efail("%s: n_slots, max_len and max_pos must be positive", what);
-    if (((uintptr_t)qkv_new | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)workspace | (uintptr_t)q_norm_w |
-         (uintptr_t)k_norm_w) & 15)
+    if (a.n_seqs < 1 || a.n_seqs > DECODE_MAX_SEQS)
+        return efail("%s: n_seqs must be in 1..%d (got %d)", what, DECODE_MAX_SEQS, a.n_seqs);
+    if (a.hq <= 0 || a.hkv <= 0 || a.hq % a.hkv || (a.hq / a.hkv != 2 && a.hq / a.hkv != 4))
+        return efail("%s: hq / hkv must be 2 or 4 (got %d / %d)", what, a.hq, a.hkv);
+    if (a.n_slots <= 0 || a.max_len <= 0 || a.max_pos <= 0)
+        return efail("%s: n_slots, max_len and max_pos must be positive", what);
+    if (((uintptr_t)a.qkv_new | (uintptr_t)a.k_cache | (uintptr_t)a.v_cache | (uintptr_t)a.workspace | (uintptr_t)a.q_norm_w |
+         (uintptr_t)a.k_norm_w) & 15)
         return efail("%s: qkv_new, the norm weights, the cache and the workspace must be 16-byte aligned", what);
-    for (int b = 0; b < n_seqs; ++b) {
-        const int len = h_cache_len[b], slot = h_slots[b];
-        if (len < 0 || len >= max_len)
-            return efail("%s: cache length %d of sequence %d is outside 0..max_len - 1 = %d", what, len, b, max_len - 1);
-        if (len >= max_pos) return efail("%s: position %d of sequence %d is beyond the RoPE table (%d rows)", what, len, b, max_pos);
-        if (slot < 0 || slot >= n_slots) return efail("%s: slot %d of sequence %d is outside 0..%d", what, slot, b, n_slots - 1);
-        for (int a = 0; a < b; ++a)
-            if (h_slots[a] == slot) return efail("%s: slot %d is named twice in one call", what, slot);
-        p.seqs.len[b] = len;
-        p.seqs.slot[b] = slot;
-    }
-    for (int b = n_seqs; b < DECODE_MAX_SEQS; ++b) p.seqs.len[b] = p.seqs.slot[b] = 0;
-    const int64_t need = crag_enc_decode_workspace_bytes(n_seqs, hq, max_len);
-    if (workspace_bytes < need)
-        return fail(CRAG_E2BIG, "%s: the workspace holds %lld bytes, %lld are needed", what, (long long)workspace_bytes,
-                    (long long)need);
-    const int max_splits = (max_len + DECODE_SPLIT - 1) / DECODE_SPLIT;
-    const int64_t heads = (int64_t)n_seqs * hq;
-    p.qkv_new = qkv_new;
-    p.qw = q_norm_w;
-    p.kw = k_norm_w;
-    p.cos_sin = cos_sin;
-    p.k_cache = k_cache;
-    p.v_cache = v_cache;
-    p.q_rot = (u16 *)workspace;
-    p.part_o = (float *)((char *)workspace + heads * CRAG_HEAD_DIM * 2);
-    p.part_ml = p.part_o + heads * max_splits * CRAG_HEAD_DIM;
-    p.out = out;
-    p.hq = hq;
-    p.hkv = hkv;
-    p.max_len = max_len;
-    p.max_splits = max_splits;
-    p.eps = eps;
-    p.scale_log2 = scale * 1.4426950408889634f;
     return CRAG_OK;
 }
 
-// The fork checks of decode_attention_shared and the units of its split launch (p.seqs is checked and filled).  Unit
+int decode_check_slot(const char *what, const DecodeArgs &a, int b) {
+    const int slot = a.h_slots[b];
+    if (slot < 0 || slot >= a.n_slots) return efail("%s: slot %d of sequence %d is outside 0..%d", what, slot, b, a.n_slots - 1);
+    for (int c = 0; c < b; ++c)
+        if (a.h_slots[c] == slot) return efail("%s: slot %d is named twice in one call", what, slot);
+    return CRAG_OK;
+}
+
+// the workspace check and the parameter block of a launch over n_rows query rows (p.seqs is the caller's)
+int decode_fill(const char *what, const DecodeArgs &a, int n_rows, DecodeParams &p) {
+    const int64_t need = crag_enc_decode_workspace_bytes(n_rows, a.hq, a.max_len);
+    if (a.workspace_bytes < need)
+        return fail(CRAG_E2BIG, "%s: the workspace holds %lld bytes, %lld are needed", what, (long long)a.workspace_bytes,
+                    (long long)need);
+    const int max_splits = (a.max_len + DECODE_SPLIT - 1) / DECODE_SPLIT;
+    const int64_t heads = (int64_t)n_rows * a.hq;
+    p.qkv_new = a.qkv_new;
+    p.qw = a.q_norm_w;
+    p.kw = a.k_norm_w;
+    p.cos_sin = a.cos_sin;
+    p.k_cache = a.k_cache;
+    p.v_cache = a.v_cache;
+    p.q_rot = (u16 *)a.workspace;
+    p.part_o = (float *)((char *)a.workspace + heads * CRAG_HEAD_DIM * 2);
+    p.part_ml = p.part_o + heads * max_splits * CRAG_HEAD_DIM;
+    p.out = a.out;
+    p.hq = a.hq;
+    p.hkv = a.hkv;
+    p.max_len = a.max_len;
+    p.max_splits = max_splits;
+    p.eps = a.eps;
+    p.scale_log2 = a.scale * 1.4426950408889634f;
+    return CRAG_OK;
+}
+
+// one new row per sequence: the checks of decode_attention and decode_attention_shared, p.seqs per sequence
+int decode_setup(const char *what, const DecodeArgs &a, DecodeParams &p) {
+    const int rc = decode_check_shape(what, a);
+    if (rc != CRAG_OK) return rc;
+    for (int b = 0; b < a.n_seqs; ++b) {
+        const int len = a.h_cache_len[b];
+        if (len < 0 || len >= a.max_len)
+            return efail("%s: cache length %d of sequence %d is outside 0..max_len - 1 = %d", what, len, b, a.max_len - 1);
+        if (len >= a.max_pos)
+            return efail("%s: position %d of sequence %d is beyond the RoPE table (%d rows)", what, len, b, a.max_pos);
+        const int bad = decode_check_slot(what, a, b);
+        if (bad != CRAG_OK) return bad;
+        p.seqs.len[b] = len;
+        p.seqs.slot[b] = a.h_slots[b];
+    }
+    for (int b = a.n_seqs; b < DECODE_MAX_SEQS; ++b) p.seqs.len[b] = p.seqs.slot[b] = 0;
+    return decode_fill(what, a, a.n_seqs, p);
+}
+
+// The fork checks: sequence b (slot slots[b], lens[b] rows) reads its first h_shared_len[b] rows in slot h_parent[b].
+// from[b] / below[b]: the slot its leading rows come from, and how many rows do.
+int fork_check(const char *what, const int32_t *slots, const int32_t *lens, const int32_t *h_parent,
+               const int32_t *h_shared_len, int n_seqs, int n_slots, int *from, int *below) {
+    for (int b = 0; b < n_seqs; ++b) {
+        const int parent = h_parent[b], shared = h_shared_len[b];
+        if (parent < 0 || parent >= n_slots)
+            return efail("%s: parent %d of sequence %d is outside 0..%d", what, parent, b, n_slots - 1);
+        if (shared < 0 || shared > lens[b])
+            return efail("%s: shared length %d of sequence %d is outside 0..its cache length %d", what, shared, b, lens[b]);
+        const bool forked = parent != slots[b] && shared > 0;
+        from[b] = forked ? parent : slots[b];
+        below[b] = forked ? shared : lens[b];
+        for (int a = 0; forked && a < n_seqs; ++a)   // a shared row must not be the one a parent appends in this call
+            if (slots[a] == parent && lens[a] < shared)
+                return efail("%s: sequence %d shares %d rows of slot %d, which holds %d", what, b, shared, parent, lens[a]);
+    }
+    return CRAG_OK;
+}
+
+// fork_check for decode_attention_shared and the units of its split launch (p.seqs is checked and filled).  Unit
 // b < n_seqs is sequence b alone over the splits no group unit covers; behind them the group units: the sequences of
 // the call that read one parent -- the parent itself counts when it is in the call: all of its rows are its own -- in
 // units of FORK_UNIT_MEMBERS, over the splits that lie wholly below the shared length of every one of them.
@@ -562,20 +662,9 @@ int fork_plan(const DecodeSeqs &seqs, const int32_t *h_parent, const int32_t *h_
               ForkUnits &u, int &n_units) {
     const char *what = "decode_attention_shared";
     if (!h_parent || !h_shared_len) return efail("%s: NULL pointer", what);
-    int from[DECODE_MAX_SEQS], below[DECODE_MAX_SEQS];   // the slot the leading rows come from, and how many rows do
-    for (int b = 0; b < n_seqs; ++b) {
-        const int parent = h_parent[b], shared = h_shared_len[b];
-        if (parent < 0 || parent >= n_slots)
-            return efail("%s: parent %d of sequence %d is outside 0..%d", what, parent, b, n_slots - 1);
-        if (shared < 0 || shared > seqs.len[b])
-            return efail("%s: shared length %d of sequence %d is outside 0..its cache length %d", what, shared, b, seqs.len[b]);
-        const bool forked = parent != seqs.slot[b] && shared > 0;
-        from[b] = forked ? parent : seqs.slot[b];
-        below[b] = forked ? shared : seqs.len[b];
-        for (int a = 0; forked && a < n_seqs; ++a)   // a shared row must not be the one a parent appends in this call
-            if (seqs.slot[a] == parent && seqs.len[a] < shared)
-                return efail("%s: sequence %d shares %d rows of slot %d, which holds %d", what, b, shared, parent, seqs.len[a]);
-    }
+    int from[DECODE_MAX_SEQS], below[DECODE_MAX_SEQS];
+    const int rc = fork_check(what, seqs.slot, seqs.len, h_parent, h_shared_len, n_seqs, n_slots, from, below);
+    if (rc != CRAG_OK) return rc;
     int covered[DECODE_MAX_SEQS] = {};   // leading splits a group unit computes for the sequence
     memset(&u, 0, sizeof(u));
     n_units = n_seqs;
@@ -616,6 +705,59 @@ int fork_plan(const DecodeSeqs &seqs, const int32_t *h_parent, const int32_t *h_
     return CRAG_OK;
 }
 
+// crag_enc_decode_attention_rows: every check of the entry, p.seqs per ROW (len = the row's position, slot = its
+// sequence's) and the units of the split launch: the rows of a sequence in runs of ROWS_UNIT_MEMBERS.
+int rows_setup(const DecodeArgs &a, const int32_t *h_new_len, const int32_t *h_parent, const int32_t *h_shared_len,
+               DecodeParams &p, RowUnits &u, int &n_rows, int &n_units, int &splits) {
+    const char *what = "decode_attention_rows";
+    int rc = decode_check_shape(what, a);
+    if (rc != CRAG_OK) return rc;
+    if (!h_new_len || !h_parent != !h_shared_len) return efail("%s: NULL pointer", what);
+    n_rows = 0;
+    for (int b = 0; b < a.n_seqs; ++b) {
+        const int len = a.h_cache_len[b], add = h_new_len[b];
+        if (len < 0) return efail("%s: cache length %d of sequence %d is negative", what, len, b);
+        if (add < 1) return efail("%s: sequence %d brings %d new rows, at least one is needed", what, b, add);
+        if (add > ROWS_MAX - n_rows)
+            return efail("%s: a call takes at most %d new rows in all (sequence %d brings %d behind %d)", what, ROWS_MAX, b,
+                         add, n_rows);
+        if (len > a.max_len - add || len > a.max_pos - add)
+            return efail("%s: rows %d..%d of sequence %d do not fit max_len %d and the RoPE table (%d rows)", what, len,
+                         len + add - 1, b, a.max_len, a.max_pos);
+        if ((rc = decode_check_slot(what, a, b)) != CRAG_OK) return rc;
+        n_rows += add;
+    }
+    int from[DECODE_MAX_SEQS], below[DECODE_MAX_SEQS];
+    for (int b = 0; b < a.n_seqs; ++b) from[b] = a.h_slots[b], below[b] = 0;
+    if (h_parent &&
+        (rc = fork_check(what, a.h_slots, a.h_cache_len, h_parent, h_shared_len, a.n_seqs, a.n_slots, from, below)) != CRAG_OK)
+        return rc;
+    if ((rc = decode_fill(what, a, n_rows, p)) != CRAG_OK) return rc;
+    memset(&p.seqs, 0, sizeof(p.seqs));
+    memset(&u, 0, sizeof(u));
+    n_units = splits = 0;
+    for (int b = 0, row = 0; b < a.n_seqs; ++b) {
+        const int len = a.h_cache_len[b], add = h_new_len[b], slot = a.h_slots[b];
+        for (int i = 0; i < add; ++i) {
+            p.seqs.len[row + i] = len + i;
+            p.seqs.slot[row + i] = slot;
+        }
+        for (int i0 = 0; i0 < add; i0 += ROWS_UNIT_MEMBERS, ++n_units) {
+            const int n = add - i0 < ROWS_UNIT_MEMBERS ? add - i0 : ROWS_UNIT_MEMBERS;
+            u.n_members[n_units] = n;
+            u.row0[n_units] = row + i0;
+            u.n_keys[n_units] = len + i0 + n;   // the last row of the unit sees itself and everything before it
+            u.s_end[n_units] = (u.n_keys[n_units] + DECODE_SPLIT - 1) / DECODE_SPLIT;
+            u.parent[n_units] = from[b];
+            u.own[n_units] = slot;
+            u.shared[n_units] = from[b] == slot ? 0 : below[b];
+            splits = u.s_end[n_units] > splits ? u.s_end[n_units] : splits;
+        }
+        row += add;
+    }
+    return CRAG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -634,8 +776,9 @@ int crag_enc_decode_attention(const uint16_t *qkv_new, const uint16_t *q_norm_w,
                               float eps, float scale, void *workspace, int64_t workspace_bytes, uint16_t *out,
                               void *stream) {
     DecodeParams p;
-    const int rc = decode_setup("decode_attention", qkv_new, q_norm_w, k_norm_w, cos_sin, max_pos, k_cache, v_cache, n_slots,
-                                max_len, h_slots, h_cache_len, n_seqs, hq, hkv, eps, scale, workspace, workspace_bytes, out, p);
+    const DecodeArgs a{qkv_new, q_norm_w, k_norm_w, cos_sin, max_pos, k_cache, v_cache, n_slots, max_len, h_slots,
+                       h_cache_len, n_seqs, hq, hkv, eps, scale, workspace, workspace_bytes, out};
+    const int rc = decode_setup("decode_attention", a, p);
     if (rc != CRAG_OK) return rc;
     int longest = 0;
     for (int b = 0; b < n_seqs; ++b) longest = p.seqs.len[b] > longest ? p.seqs.len[b] : longest;
@@ -660,8 +803,9 @@ int crag_enc_decode_attention_shared(const uint16_t *qkv_new, const uint16_t *q_
     DecodeParams p;
     ForkUnits u;
     int n_units = 0;
-    int rc = decode_setup("decode_attention_shared", qkv_new, q_norm_w, k_norm_w, cos_sin, max_pos, k_cache, v_cache, n_slots,
-                          max_len, h_slots, h_cache_len, n_seqs, hq, hkv, eps, scale, workspace, workspace_bytes, out, p);
+    const DecodeArgs a{qkv_new, q_norm_w, k_norm_w, cos_sin, max_pos, k_cache, v_cache, n_slots, max_len, h_slots,
+                       h_cache_len, n_seqs, hq, hkv, eps, scale, workspace, workspace_bytes, out};
+    int rc = decode_setup("decode_attention_shared", a, p);
     if (rc == CRAG_OK) rc = fork_plan(p.seqs, h_parent, h_shared_len, n_seqs, n_slots, u, n_units);
     if (rc != CRAG_OK) return rc;
     int longest = 0;
@@ -676,6 +820,31 @@ int crag_enc_decode_attention_shared(const uint16_t *qkv_new, const uint16_t *q_
         hipLaunchKernelGGL(decode_split_shared_kernel<4>, grid, dim3(DECODE_THREADS), 0, st, p, u);
     hipLaunchKernelGGL(decode_combine_kernel, dim3((unsigned)hq, (unsigned)n_seqs), dim3(CRAG_HEAD_DIM), 0, st, p);
     return hip_ok("decode_attention_shared");
+}
+
+int crag_enc_decode_attention_rows(const uint16_t *qkv_new, const uint16_t *q_norm_w, const uint16_t *k_norm_w,
+                                   const float *cos_sin, int max_pos, uint16_t *k_cache, uint16_t *v_cache, int n_slots,
+                                   int max_len, const int32_t *h_slots, const int32_t *h_cache_len, const int32_t *h_new_len,
+                                   const int32_t *h_parent, const int32_t *h_shared_len, int n_seqs, int hq, int hkv,
+                                   float eps, float scale, void *workspace, int64_t workspace_bytes, uint16_t *out,
+                                   void *stream) {
+    DecodeParams p;
+    RowUnits u;
+    int n_rows = 0, n_units = 0, splits = 0;
+    const DecodeArgs a{qkv_new, q_norm_w, k_norm_w, cos_sin, max_pos, k_cache, v_cache, n_slots, max_len, h_slots,
+                       h_cache_len, n_seqs, hq, hkv, eps, scale, workspace, workspace_bytes, out};
+    const int rc = rows_setup(a, h_new_len, h_parent, h_shared_len, p, u, n_rows, n_units, splits);
+    if (rc != CRAG_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    // prepare and combine see the rows of the call as sequences of their own: row r sits at position p.seqs.len[r]
+    hipLaunchKernelGGL(decode_prepare_kernel, dim3((unsigned)n_rows), dim3(DECODE_THREADS), 0, st, p);
+    const dim3 grid((unsigned)splits, (unsigned)hkv, (unsigned)n_units);
+    if (hq / hkv == 2)
+        hipLaunchKernelGGL(decode_split_rows_kernel<2>, grid, dim3(DECODE_THREADS), 0, st, p, u);
+    else
+        hipLaunchKernelGGL(decode_split_rows_kernel<4>, grid, dim3(DECODE_THREADS), 0, st, p, u);
+    hipLaunchKernelGGL(decode_combine_kernel, dim3((unsigned)hq, (unsigned)n_rows), dim3(CRAG_HEAD_DIM), 0, st, p);
+    return hip_ok("decode_attention_rows");
 }
 
 int crag_enc_lm_head(const uint16_t *hidden_states, const uint16_t *delta, const uint16_t *final_norm_w,

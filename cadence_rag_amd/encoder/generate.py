@@ -22,6 +22,10 @@ kernels) with a full-vocabulary head -- the in-process LLM behind /answer (caden
                         (KvCache.fork: no copy), and step reads a child's shared rows in its parent's slot through
                         crag_enc_decode_attention_shared, which loads every wholly shared 128-key split once for two
                         sequences of a parent.  generate's own token loop (_token_loop).
+  step_rows(token_rows) step with several new tokens per sequence, at most 8 in all: a pending token and drafted ones
+                        behind it, through crag_enc_decode_attention_rows.  generate(speculate=k) drafts by prompt
+                        lookup (cadence_rag_amd.speculate), verifies the drafts in one such forward and keeps the
+                        tokens the plain loop would have produced (_speculative_loop); off by default.
 
 The cache layout ([layer][slot][kv head][max_len][128] bf16, keys and values apart) sits behind KvCache.keys / .values.
 At most MAX_SEQS = 8 sequences decode at a time.
@@ -37,10 +41,12 @@ import torch.nn.functional as F
 
 from ..grammar import KIND_STOP, TokenGrammar, TokenTable
 from ..sampling import SamplingParams
+from ..speculate import MAX_SPECULATE, propose_drafts
 from . import ops
 from .qwen3 import QKV_ROW_CHUNK, PackedBatch, Qwen3Config, Qwen3Encoder
 
 MAX_SEQS = 8
+MAX_ROWS = 8             # CRAG_DECODE_MAX_ROWS: the rows of one step_rows -- pending tokens and drafts together
 PREFIX_MIN_REUSE = 32    # one query block of the extend kernel: below it a plain prefill is no dearer
 CHAT_SYSTEM = "<|im_start|>system\n{system}<|im_end|>\n"
 CHAT_USER = "<|im_start|>user\n{user}<|im_end|>\n"
@@ -201,6 +207,7 @@ class Qwen3Generator:
     supports_grammar = True   # generate / generate_text take grammar=TokenGrammar (answer.py asks before passing one)
     supports_sampling = True  # ... and sampling=SamplingParams
     supports_samples = True   # generate_text_samples: n replies from one prefill
+    supports_speculation = True   # ... and speculate=k: up to k prompt-lookup drafts verified per forward
 
     def __init__(self, encoder: Qwen3Encoder, lm_head: torch.Tensor, tokenizer=None, *, max_context: Optional[int] = None,
                  max_seqs: int = MAX_SEQS, model_id: Optional[str] = None, prefix_cache: bool = False) -> None:
@@ -227,11 +234,13 @@ class Qwen3Generator:
         self.cache = KvCache(c.num_layers, self.max_seqs, c.num_kv_heads, self.max_context, self.device)
         self._workspace = ops.decode_workspace(self.max_seqs, c.num_heads, self.max_context, self.device)
         self._extend_ws: Optional[torch.Tensor] = None   # extend's scratch: grows to the largest call
+        self._rows_ws: Optional[torch.Tensor] = None     # step_rows' scratch for MAX_ROWS rows: made on first use
         self.live: List[int] = []          # slots of the sequences the next step() advances
         self.tokens: List[List[int]] = [[] for _ in range(self.max_seqs)]   # the token ids every slot holds
         self.prefix_cache = bool(prefix_cache)   # generate_text reuses a slot's rows (generate(reuse_prefix=True))
         self.last_reuse: Optional[Dict[str, List[int]]] = None   # per prompt of the last generate(reuse_prefix=True)
         self.last_grammar: Optional[Dict[str, List[bool]]] = None   # per prompt of the last generate(grammar=...)
+        self.last_speculation: Optional[Dict[str, object]] = None   # of the last generate(speculate=k > 0)
         self._token_table: Optional[TokenTable] = None   # the vocabulary's bytes: built once, its tensors stay in HBM
         self.force_library = False         # tests: keep the 4B widths off the small_gemm path
         self.last_path = ""
@@ -540,9 +549,83 @@ class Qwen3Generator:
         return token, logits
 
     @torch.no_grad()
+    def step_rows(self, token_rows: Sequence[Sequence[int]], slots: Optional[Sequence[int]] = None,
+                  banned: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """step with SEVERAL new tokens per sequence: token_rows[b] (at least one id) goes behind what slot slots[b]
+        (default the live ones, in order) holds, R = the total number of ids <= MAX_ROWS.  Returns (next tokens int32
+        [R], logits [R, vocab] fp32) in call order: row i of a sequence is what step would return after feeding it the
+        ids 0..i one at a time -- to the bit on the small_gemm path, where every row of a GEMM, of lm_head and of
+        crag_enc_decode_attention_rows depends on that row alone.  The cache of every slot grows by its row count; the
+        caller cuts back what it does not keep (truncate).  Forked slots are allowed."""
+        c, enc, dev, bf = self.cfg, self.encoder, self.device, torch.bfloat16
+        slots = list(self.live) if slots is None else [int(s) for s in slots]
+        news = [len(row) for row in token_rows]
+        n = sum(news)
+        if not slots or len(token_rows) != len(slots) or min(news) < 1 or n > MAX_ROWS:
+            raise ValueError(f"step_rows needs at least one token per live sequence and at most {MAX_ROWS} in all")
+        lens = [self.cache.lens[s] for s in slots]
+        full = max(m + r for m, r in zip(lens, news))
+        if full > self.max_context:
+            raise PromptTooLong(f"a sequence of {full} tokens does not fit the context of {self.max_context}")
+        if self._rows_ws is None:   # the constructor's scratch holds max_seqs rows
+            self._rows_ws = self._workspace if self.max_seqs >= MAX_ROWS else \
+                ops.decode_workspace(MAX_ROWS, c.num_heads, self.max_context, dev)
+        ids = torch.tensor([int(t) for row in token_rows for t in row], dtype=torch.int32).to(dev)
+        scale = 1.0 / math.sqrt(c.head_dim)
+        width = c.q_size + 2 * c.kv_size
+        forked = any(self.cache.forked(s) for s in slots)
+        parents = [self.cache.parent[s] for s in slots] if forked else None
+        shared = [self.cache.shared[s] for s in slots] if forked else None
+
+        def attention(qkv, L, kc, vc):
+            ops.decode_attention_rows(qkv, L["q_norm"], L["k_norm"], enc._cos_sin, kc, vc, slots, lens, news, attn,
+                                      c.num_heads, c.num_kv_heads, c.rms_norm_eps, scale, self._rows_ws, parents=parents,
+                                      shared_len=shared)
+        skinny = None if self.force_library else enc._skinny_weights()
+        if skinny is not None and not enc._skinny_v1:
+            # step's small_gemm layer: the same launches over n rows of the same 16 padded ones
+            self.last_path = "small_gemm"
+            bufs = self.__dict__.get("_small_bufs")
+            if bufs is None:
+                z = lambda cols: torch.zeros(16, cols, dtype=bf, device=dev)   # noqa: E731
+                bufs = self._small_bufs = tuple(z(cols) for cols in (c.hidden_size,) * 5 + (width, c.q_size,
+                                                                                            c.intermediate_size))
+            res_a, res_b, delta_o, delta_d, delta0, qkv, attn, act = bufs
+            ops.embed_gather(ids, enc.embed, res_a[:n])
+            for i, L in enumerate(enc.layers):
+                W = skinny[i]
+                kc, vc = self.cache.layer(i)
+                ops.small_gemm(res_a, W["qkv"], qkv, n, width, 12, delta=delta0 if i == 0 else delta_d, norm_w=L["ln1"],
+                               res_out=res_b, eps=c.rms_norm_eps)
+                attention(qkv, L, kc, vc)
+                ops.small_gemm(attn, W["o"], delta_o, n, c.hidden_size, 10)
+                ops.small_gemm(res_b, W["gate_up"], act, n, 2 * c.intermediate_size, 16, swiglu=True, delta=delta_o,
+                               norm_w=L["ln2"], res_out=res_a, eps=c.rms_norm_eps)
+                ops.small_gemm(act, W["down"], delta_d, n, c.hidden_size, 10)
+            hidden, delta = res_a[:n], delta_d[:n]
+        else:
+            self.last_path = "library"
+            x = torch.empty(n, c.hidden_size, dtype=bf, device=dev)
+            ops.embed_gather(ids, enc.embed, x)
+            attn = torch.empty(n, c.q_size, dtype=bf, device=dev)
+
+            def attend(i, L, normed):
+                attention(F.linear(normed, L["qkv"]), L, *self.cache.layer(i))
+                return attn
+
+            hidden, delta = self._layers(x, attend)
+        for s, row in zip(slots, token_rows):
+            self._forget_stale(s)
+            self.cache.lens[s] += len(row)
+            self.tokens[s].extend(int(t) for t in row)
+        logits, token = self._head(hidden, delta, banned)
+        return token, logits
+
+    @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_ids: Sequence[int] = (),
                  reuse_prefix: bool = False, grammar: Optional[TokenGrammar] = None,
-                 sampling=None, streams: Optional[Sequence[int]] = None) -> List[List[int]]:
+                 sampling=None, streams: Optional[Sequence[int]] = None, speculate: int = 0,
+                 drafter=None) -> List[List[int]]:
         """Greedy continuation of every prompt (token ids): at most max_new_tokens ids each, ending before the first
         stop id.  A prompt longer than max_context - max_new_tokens raises PromptTooLong (a ValueError): the caller
         shortens its prompt, nothing is truncated here.
@@ -559,8 +642,12 @@ class Qwen3Generator:
         return and the later ones on step's; a temperature of 0 gives the greedy token.  Under a grammar the draw is
         among the tokens the state allows: grammar_argmax hands out their bits (its own token is dropped and the state
         it moved is discarded), sample draws under the bits, grammar_advance moves the state behind the drawn token.
-        None: greedy, the code path without sampling."""
-        max_new_tokens = int(max_new_tokens)
+        None: greedy, the code path without sampling.
+        speculate: k in 0..7 -- up to k drafted tokens per sequence are verified in one forward (_speculative_loop); the
+        ids returned are those of speculate=0 whatever is drafted.  drafter: (ids, max_draft) -> ids, default
+        speculate.propose_drafts.  last_speculation then holds the forwards and the drafted / accepted counts per
+        prompt (None with 0, which runs the plain loop)."""
+        max_new_tokens, speculate = int(max_new_tokens), self._check_speculate(speculate)
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be positive")
         room = self.max_context - max_new_tokens
@@ -581,9 +668,25 @@ class Qwen3Generator:
             logits = self.prefill(prompts)
         self.last_reuse = {"reused": list(keeps), "computed": [len(p) - keep for p, keep in zip(prompts, keeps)]} \
             if reuse_prefix else None
-        out, accepted = self._token_loop(pick, len(prompts), logits, self.last_tokens, max_new_tokens, stop)
+        out, accepted = self._decode(pick, [list(p) for p in prompts], logits, self.last_tokens, max_new_tokens, stop,
+                                     speculate, drafter)
         self.last_grammar = {"accepted": accepted} if grammar is not None else None
         return out
+
+    @staticmethod
+    def _check_speculate(speculate: int) -> int:
+        if not 0 <= int(speculate) <= MAX_SPECULATE:
+            raise ValueError(f"speculate must be in 0..{MAX_SPECULATE}")
+        return int(speculate)
+
+    def _decode(self, pick: _Picker, prompts: List[List[int]], logits, greedy, max_new_tokens: int, stop: set,
+                speculate: int, drafter) -> Tuple[List[List[int]], List[bool]]:
+        """The token loop of generate and generate_samples: the plain one, or the speculative one under speculate > 0."""
+        self.last_speculation = None
+        if speculate == 0:
+            return self._token_loop(pick, len(prompts), logits, greedy, max_new_tokens, stop)
+        return self._speculative_loop(pick, prompts, logits, greedy, max_new_tokens, stop, speculate,
+                                      drafter or propose_drafts)
 
     def _token_loop(self, pick: _Picker, n: int, logits: torch.Tensor, greedy: torch.Tensor, max_new_tokens: int,
                     stop: set) -> Tuple[List[List[int]], List[bool]]:
@@ -614,6 +717,78 @@ class Qwen3Generator:
         self.live = []
         return out, accepted
 
+    def _speculative_loop(self, pick: _Picker, prompts: List[List[int]], logits: torch.Tensor, greedy: torch.Tensor,
+                          max_new_tokens: int, stop: set, speculate: int, drafter
+                          ) -> Tuple[List[List[int]], List[bool]]:
+        """_token_loop with drafts.  Sequence b (slot b, prompt prompts[b]) with the pending token t gets up to D_b =
+        min(speculate, MAX_ROWS // live - 1, tokens still allowed - 1, context room) drafts d1..dm from drafter(prompt +
+        output, D_b) -- the output ends in t -- and one step_rows feeds [t, d1..dm]; row i's logits are the logits behind
+        t, d1..di.  The rows of a sequence are then picked in order through `pick`, each with the sequence's own count
+        of produced tokens as the draw's step, and every pick is emitted exactly as _token_loop emits it; picking goes
+        on to row i + 1 only when pick i equals draft i + 1, so a token is only ever picked on logits computed behind
+        the tokens actually emitted, and the grammar state moves behind emitted tokens only.  The slot is cut back to
+        the rows of t and the accepted drafts (truncate).  If nobody has a draft the iteration is a plain step."""
+        n = len(prompts)
+        out: List[List[int]] = [[] for _ in range(n)]
+        accepted = [False] * n
+        produced = [0] * n           # tokens picked per sequence: the step of its next draw
+        stats = {"forwards": 0, "drafted": [0] * n, "accepted": [0] * n}
+        pending = {b: (logits[b:b + 1], greedy[b:b + 1], [], 0) for b in range(n)}   # rows, greedy, drafts, cache length before
+        live = list(range(n))
+        while live:
+            feed, keep = [], []
+            for b in live:
+                rows, tokens, drafts, base = pending[b]
+                right, alive = 0, False
+                for i in range(rows.shape[0]):
+                    tok = pick([b], rows[i:i + 1], tokens[i:i + 1], produced[b])[0]
+                    produced[b] += 1
+                    if pick.table is not None and tok >= 0 and pick.table.kind[tok] == KIND_STOP:
+                        accepted[b] = True
+                        break
+                    if tok in stop or tok < 0:
+                        break
+                    out[b].append(int(tok))
+                    if len(out[b]) >= max_new_tokens:
+                        break
+                    if i < len(drafts) and drafts[i] == tok:   # row i + 1 was computed behind the right token
+                        right += 1
+                        continue
+                    alive = True
+                    break
+                if drafts:
+                    self.truncate(b, base + 1 + right)
+                    stats["accepted"][b] += right
+                if alive:
+                    keep.append(b)
+                    feed.append(out[b][-1])
+            live = keep
+            if not live:
+                break
+            self.live = list(live)
+            token_rows = []
+            for b, tok in zip(live, feed):
+                room = min(speculate, MAX_ROWS // len(live) - 1, max_new_tokens - len(out[b]) - 1,
+                           self.max_context - self.cache.lens[b] - 1)
+                drafts = [int(d) for d in drafter(prompts[b] + out[b], room)][:room] if room > 0 else []
+                bad = [i for i, d in enumerate(drafts) if not 0 <= d < self.cfg.vocab_size]
+                token_rows.append([tok] + (drafts[:bad[0]] if bad else drafts))
+            stats["forwards"] += 1
+            if all(len(row) == 1 for row in token_rows):
+                greedy, logits = self.step(feed)
+            else:
+                bases = [self.cache.lens[b] for b in live]
+                greedy, logits = self.step_rows(token_rows)
+            lo = 0
+            for k, (b, row) in enumerate(zip(live, token_rows)):
+                hi = lo + len(row)
+                pending[b] = (logits[lo:hi], greedy[lo:hi], row[1:], bases[k] if len(row) > 1 else 0)
+                stats["drafted"][b] += len(row) - 1
+                lo = hi
+        self.live = []
+        self.last_speculation = stats
+        return out, accepted
+
     def fork(self, src: int, dst_slots: Sequence[int]) -> None:
         """KvCache.fork: the dst slots hold what src holds without a copy.  Their ids count as unknown, so plan_reuse
         never keeps a child's rows."""
@@ -624,7 +799,8 @@ class Qwen3Generator:
     @torch.no_grad()
     def generate_samples(self, prompt: Sequence[int], n: int, max_new_tokens: int, stop_ids: Sequence[int] = (),
                          reuse_prefix: bool = False, grammar: Optional[TokenGrammar] = None,
-                         sampling=None, streams: Optional[Sequence[int]] = None) -> List[List[int]]:
+                         sampling=None, streams: Optional[Sequence[int]] = None, speculate: int = 0,
+                         drafter=None) -> List[List[int]]:
         """n (1..max_seqs) continuations of ONE prompt from one prefill: the prompt goes into slot 0 (prefill, or extend
         behind what plan_reuse keeps under reuse_prefix, as in generate), slots 1..n-1 are forked from it, the one row
         of logits serves every sequence's first pick, and generate's token loop runs over the n slots: a child reads
@@ -632,8 +808,9 @@ class Qwen3Generator:
         draws on streams[i] (default i).  A sequence that stops -- slot 0 too -- leaves the others running on its rows.
         Afterwards the children are empty and slot 0 holds the prompt and continuation 0 with their ids, for a later
         reuse_prefix.  last_reuse / last_grammar hold one entry per sample (the prompt's rows were reused / computed
-        once, for all of them).  n = 1 is generate([prompt], ...)."""
-        n, max_new_tokens = int(n), int(max_new_tokens)
+        once, for all of them).  n = 1 is generate([prompt], ...).  speculate / drafter: as in generate; every sample
+        drafts from the prompt and its own output."""
+        n, max_new_tokens, speculate = int(n), int(max_new_tokens), self._check_speculate(speculate)
         if not 1 <= n <= self.max_seqs:
             raise ValueError(f"generate_samples takes n in 1..{self.max_seqs}")
         if max_new_tokens < 1:
@@ -655,7 +832,8 @@ class Qwen3Generator:
             if n > 1:
                 self.fork(0, range(1, n))
                 logits, greedy = logits.repeat(n, 1), greedy.repeat(n)
-            out, accepted = self._token_loop(pick, n, logits, greedy, max_new_tokens, {int(s) for s in stop_ids})
+            out, accepted = self._decode(pick, [list(prompt)] * n, logits, greedy, max_new_tokens,
+                                         {int(s) for s in stop_ids}, speculate, drafter)
         finally:
             self.live = []
             for child in range(1, n):
@@ -665,19 +843,21 @@ class Qwen3Generator:
 
     def generate_text_samples(self, messages: Sequence[Dict[str, str]], n: int, max_new_tokens: int,
                               grammar: Optional[TokenGrammar] = None, sampling: Optional[SamplingParams] = None,
-                              streams: Optional[Sequence[int]] = None) -> List[str]:
+                              streams: Optional[Sequence[int]] = None, speculate: int = 0, drafter=None) -> List[str]:
         """One chat -> n replies as text from one prefill (generate_samples), reply i drawn on noise stream streams[i]."""
         ids = self.generate_samples(self.chat_ids(messages), n, max_new_tokens, self.stop_ids(),
-                                    reuse_prefix=self.prefix_cache, grammar=grammar, sampling=sampling, streams=streams)
+                                    reuse_prefix=self.prefix_cache, grammar=grammar, sampling=sampling, streams=streams,
+                                    speculate=speculate, drafter=drafter)
         tok = self._tokenizer()
         return [tok.decode(x, skip_special_tokens=True) for x in ids]
 
     def generate_text(self, messages: Sequence[Dict[str, str]], max_new_tokens: int,
                       grammar: Optional[TokenGrammar] = None, sampling: Optional[SamplingParams] = None,
-                      stream: int = 0) -> str:
+                      stream: int = 0, speculate: int = 0, drafter=None) -> str:
         """One chat -> the assistant's reply as text; under `grammar` when one is given, drawn with `sampling` on noise
         stream `stream` when that is given (generate)."""
         ids = self.generate([self.chat_ids(messages)], max_new_tokens, self.stop_ids(),
                             reuse_prefix=self.prefix_cache, grammar=grammar, sampling=sampling,
-                            streams=None if sampling is None else [int(stream)])[0]
+                            streams=None if sampling is None else [int(stream)], speculate=speculate,
+                            drafter=drafter)[0]
         return self._tokenizer().decode(ids, skip_special_tokens=True)

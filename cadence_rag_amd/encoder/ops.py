@@ -373,6 +373,37 @@ def decode_attention_shared(qkv_new, q_w, k_w, cos_sin, k_cache, v_cache, slots,
     return out
 
 
+def decode_attention_rows(qkv_new, q_w, k_w, cos_sin, k_cache, v_cache, slots, cache_len, new_len, out, hq: int, hkv: int,
+                          eps: float, scale: float, workspace, parents=None, shared_len=None):
+    """decode_attention_shared with new_len[b] >= 1 new rows per sequence (crag_enc_decode_attention_rows): the R =
+    sum(new_len) <= 8 rows of qkv_new / out lie back to back in call order, row i of sequence b is appended at row
+    cache_len[b] + i of slots[b] and attends the logical rows up to itself.  parents / shared_len: None together (nobody
+    is forked), or as in decode_attention_shared.  The bits of out and of the appended rows are those of new_len[b]
+    successive decode_attention calls.  The workspace is decode_workspace(R, ...)'s, indexed by row."""
+    _req(qkv_new, torch.bfloat16, "qkv_new"); _req(cos_sin, torch.float32, "cos_sin"); _req(out, torch.bfloat16, "out")
+    _req(k_cache, torch.bfloat16, "k_cache"); _req(v_cache, torch.bfloat16, "v_cache")
+    _req(q_w, torch.bfloat16, "q_w"); _req(k_w, torch.bfloat16, "k_w"); _req(workspace, torch.uint8, "workspace")
+    n = len(slots)
+    if (parents is None) != (shared_len is None):
+        raise ValueError("parents and shared_len come together")
+    lists = [slots, cache_len, new_len] + ([] if parents is None else [parents, shared_len])
+    if any(len(xs) != n for xs in lists):
+        raise ValueError("slots, cache_len, new_len, parents and shared_len need one entry per sequence")
+    n_slots, kv_heads, max_len, dim = k_cache.shape
+    if v_cache.shape != k_cache.shape or kv_heads != hkv or dim != 128:
+        raise ValueError("k_cache and v_cache must both be [n_slots, hkv, max_len, 128]")
+    rows = sum(max(int(m), 0) for m in new_len)
+    if rows <= _native.CRAG_DECODE_MAX_ROWS and (qkv_new.shape[0] < rows or out.shape[0] < rows
+                                                 or qkv_new.shape[1] != (hq + 2 * hkv) * 128 or out.shape[1] != hq * 128):
+        raise ValueError("qkv_new must be [R, (hq + 2 hkv) * 128] and out [R, hq * 128]")
+    h = [(ctypes.c_int32 * max(n, 1))(*[int(x) for x in xs]) for xs in lists] + [None, None]
+    _native.check(_native.load().crag_enc_decode_attention_rows(
+        _p(qkv_new), _p(q_w), _p(k_w), _p(cos_sin), int(cos_sin.shape[0]), _p(k_cache), _p(v_cache), int(n_slots),
+        int(max_len), h[0], h[1], h[2], h[3], h[4], n, int(hq), int(hkv), float(eps), float(scale), _p(workspace),
+        int(workspace.numel()), _p(out), _stream()), "crag_enc_decode_attention_rows")
+    return out
+
+
 def lm_head(hidden_states, final_norm_w, lm, logits, token, eps: float, delta=None, banned=None):
     """Final RMSNorm of hidden_states [n <= 8, hidden] (+ delta), fp32 logits [n, vocab] against lm [vocab, hidden] and the
     greedy token [n] int32: lowest id among the maxima, `banned` (int32 device list) left out (crag_enc_lm_head)."""

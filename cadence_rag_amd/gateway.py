@@ -156,13 +156,15 @@ class AnswerRequestModel(RetrieveRequestModel):
     min_p: Optional[float] = Field(default=None, ge=0.0, le=1.0)
     seed: Optional[int] = Field(default=None, ge=0, lt=2 ** 64)
     samples: Optional[int] = Field(default=None, ge=1, le=8)   # candidates per attempt (ANSWER_SAMPLES when absent)
+    speculate: Optional[int] = Field(default=None, ge=0, le=7)   # drafts per forward (ANSWER_SPECULATE when absent)
 
 
 @app.post("/answer")
 def answer_endpoint(payload: AnswerRequestModel) -> dict:
     request = _answer.AnswerRequest(**_request_fields(payload), echo_evidence=payload.echo_evidence,
                                     temperature=payload.temperature, top_p=payload.top_p, top_k=payload.top_k,
-                                    min_p=payload.min_p, seed=payload.seed, samples=payload.samples)
+                                    min_p=payload.min_p, seed=payload.seed, samples=payload.samples,
+                                    speculate=payload.speculate)
     try:
         return _answer.answer_question(request)
     except _answer.AnswerRequestError as exc:

@@ -230,12 +230,29 @@ int crag_enc_rerank_head(const uint16_t *hidden_states, const uint16_t *delta, c
  *   outside 0..n_slots - 1; a shared_len outside 0..cache_len; a forked sequence whose parent slot is a sequence of the
  *   call with cache_len < that shared_len (a shared row would be written during the call).  A parent slot that is not
  *   in the call is allowed.
+ * crag_enc_decode_attention_rows: crag_enc_decode_attention_shared with h_new_len[b] >= 1 new rows per sequence (HOST
+ *   array), appended back to back behind h_cache_len[b]: R = the sum of h_new_len, 1..CRAG_DECODE_MAX_ROWS.  qkv_new
+ *   [R, (hq + 2 hkv) * 128] and out [R, hq * 128] hold the sequences' rows in call order.  h_parent / h_shared_len are
+ *   nullable TOGETHER: nobody is forked.  Row i of sequence b has position cache_len + i; its key and raw value go to
+ *   that row of the sequence's own slot, and it attends the logical rows 0 .. cache_len + i -- the parent's below
+ *   shared_len, its own otherwise, the rows appended earlier in this call among them.  The bits of out and of every
+ *   appended row are those new_len[b] successive calls of crag_enc_decode_attention (_shared for a forked sequence) give
+ *   on a private copy of the logical rows: the same 128-key splits, every row read by the same 16-lane group and dotted
+ *   in the same order, the same combine.  A workgroup of the split launch serves a run of consecutive rows of ONE
+ *   sequence (DESIGN 6d for how many) and loads each key and value row once for all of them; a key behind a row's own
+ *   position scores -inf for that row only.  Nothing at or beyond cache_len + new_len is read, nor a forked sequence's
+ *   own rows below shared_len.  Three launches (prepare: one workgroup per row; split; combine), no atomics; the
+ *   workspace is crag_enc_decode_workspace_bytes(R, hq, max_len), indexed by row.
+ *   CRAG_EINVAL, nothing enqueued: every refusal of crag_enc_decode_attention_shared (a NULL h_parent with a NULL
+ *   h_shared_len excepted); a NULL h_new_len; new_len < 1; R > CRAG_DECODE_MAX_ROWS; cache_len + new_len > max_len or
+ *   > max_pos.  CRAG_E2BIG: the workspace is too small.
  * crag_enc_lm_head: per row r < n_rows (1..8): x = bf16(hidden_states[r] + delta[r]) (delta nullable), the final RMSNorm
  *   with crag_enc_rerank_head's roundings, logits[r, v] = fp32 dot with lm_head[v] for EVERY v < vocab (lm_head
  *   [vocab, hidden] bf16; a tied model passes embed_tokens), token[r] = the lowest id among the maxima of logits[r]
  *   that is not in banned[n_banned] (device int32, nullable with n_banned 0; at most CRAG_LM_HEAD_MAX_BANNED) -- -1 when
  *   no id is left.  hidden % 64 == 0, n_rows * (hidden + 8) <= CRAG_LM_HEAD_MAX_ELEMS (the rows live in LDS). */
 #define CRAG_DECODE_MAX_SEQS 8
+#define CRAG_DECODE_MAX_ROWS 8
 #define CRAG_DECODE_SPLIT 128
 #define CRAG_LM_HEAD_MAX_BANNED 64
 #define CRAG_LM_HEAD_MAX_ELEMS 32760
@@ -251,6 +268,12 @@ int crag_enc_decode_attention_shared(const uint16_t *qkv_new, const uint16_t *q_
                                      const int32_t *h_parent, const int32_t *h_shared_len, int n_seqs, int hq, int hkv,
                                      float eps, float scale, void *workspace, int64_t workspace_bytes, uint16_t *out,
                                      void *stream);
+int crag_enc_decode_attention_rows(const uint16_t *qkv_new, const uint16_t *q_norm_w, const uint16_t *k_norm_w,
+                                   const float *cos_sin, int max_pos, uint16_t *k_cache, uint16_t *v_cache, int n_slots,
+                                   int max_len, const int32_t *h_slots, const int32_t *h_cache_len, const int32_t *h_new_len,
+                                   const int32_t *h_parent, const int32_t *h_shared_len, int n_seqs, int hq, int hkv,
+                                   float eps, float scale, void *workspace, int64_t workspace_bytes, uint16_t *out,
+                                   void *stream);
 int crag_enc_lm_head(const uint16_t *hidden_states, const uint16_t *delta, const uint16_t *final_norm_w,
                      const uint16_t *lm_head, float *logits, int32_t *token, const int32_t *banned, int n_banned,
                      int n_rows, int hidden, int64_t vocab, float eps, void *stream);
