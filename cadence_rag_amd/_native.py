@@ -149,6 +149,7 @@ SIGNATURES = {
                                            _P]),
     "crag_enc_sample": (_c.c_int, [_P, _c.c_int64, _P, _P, _P, _P, _P, _P, _c.c_uint64, _c.c_uint32, _P, _P, _P, _c.c_int, _P]),
     "crag_enc_grammar_advance": (_c.c_int, [_P, _P, _P, _c.c_int64, _P, _P, _c.c_int, _c.c_int, _P, _P, _c.c_int, _P]),
+    "crag_enc_logprobs": (_c.c_int, [_P, _c.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _P]),
 }
 
 

@@ -27,6 +27,17 @@ supports_speculation verifies up to that many prompt-lookup drafts per forward (
 does not depend on it.  notes.speculation echoes the model's last_speculation; anything else decodes as ever and says
 notes.speculation = {"applied": False}.  With 0 and no field the response and the notes are what they were.
 
+Token log-probabilities (`logprobs` of the request, ANSWER_LOGPROBS; off by default): a native model with
+supports_logprobs scores every token it produces on the GPU (crag_enc_logprobs: the model's own distribution at
+temperature 1, whatever picked the token) and notes.logprobs = {"tokens", "mean_logprob", "min_logprob"} describes the
+judged candidate, under the grammar also {"mean_allowed_logmass", "min_allowed_logmass"}: how much probability the
+automaton left allowed, i.e. how hard it had to push.  Anything else says notes.logprobs = {"applied": False}.
+`sample_rank` (ANSWER_SAMPLE_RANK): "first" judges candidates in index order as ever; "logprob" -- several candidates
+from such a model -- takes the valid candidate with the highest mean token log-probability (the lowest index among
+equals), ranks the candidate quoted into a repair turn the same way among those that tried to answer, and
+notes.samples gains "scores" (one mean per candidate) and "ranked": True.  "logprob" with one sample, or on a backend
+without the capability, behaves as "first" and says notes.samples["ranked"] = False.
+
 ANSWER_CONSTRAINED (native backend, a model with supports_grammar): the reply is decoded under the citation grammar of
 the evidence ids in the prompt (cadence_rag_amd.grammar.citation_grammar), which makes a failing answer unrepresentable
 whenever the model stops by itself.  The gate and the repair loop run unchanged on whatever comes back.
@@ -42,6 +53,7 @@ from . import retrieve as _retrieve
 from .config import settings
 from .grammar import INSUFFICIENT as _INSUFFICIENT_BYTES
 from .grammar import TokenGrammar, citation_grammar
+from .logprobs import mean_logprob, summarise
 from .sampling import SamplingParams
 
 INSUFFICIENT = _INSUFFICIENT_BYTES.decode("ascii")   # "INSUFFICIENT_EVIDENCE": one definition, the grammar's
@@ -74,7 +86,9 @@ class ChatModel(Protocol):
     Optional: a model whose class sets `supports_sampling = True` also takes `sampling=SamplingParams, stream=int`.
     Optional: a model whose class sets `supports_samples = True` also has `generate_text_samples(messages, n,
     max_new_tokens, grammar=None, sampling=None, streams=None) -> List[str]`: n replies to one chat, reply i drawn on
-    noise stream streams[i]; the same exceptions as generate_text."""
+    noise stream streams[i]; the same exceptions as generate_text.
+    Optional: a model whose class sets `supports_logprobs = True` also takes `logprobs=int` in both and then leaves
+    `last_logprobs`: per reply a list of cadence_rag_amd.logprobs.TokenLogprob, one per produced token."""
 
     model_id: str
 
@@ -192,7 +206,8 @@ def _chat_http(messages: List[Dict[str, str]], max_new_tokens: int, sampling: Op
 
 
 def _chat_native(messages: List[Dict[str, str]], max_new_tokens: int, grammar: Optional[TokenGrammar] = None,
-                 sampling: Optional[SamplingParams] = None, stream: int = 0, speculate: int = 0) -> Tuple[str, str]:
+                 sampling: Optional[SamplingParams] = None, stream: int = 0, speculate: int = 0,
+                 logprobs: Optional[int] = None) -> Tuple[str, str]:
     """ValueError (the prompt does not fit) passes through to the caller, which drops evidence."""
     llm = _llm
     if llm is None:
@@ -204,6 +219,8 @@ def _chat_native(messages: List[Dict[str, str]], max_new_tokens: int, grammar: O
                 extra.update(sampling=sampling, stream=int(stream))
             if speculate:
                 extra.update(speculate=int(speculate))
+            if logprobs is not None:
+                extra.update(logprobs=int(logprobs))
             text = llm.generate_text(messages, max_new_tokens, **extra)
     except (AnswerClientError, ValueError):
         raise
@@ -216,9 +233,10 @@ def _chat_native(messages: List[Dict[str, str]], max_new_tokens: int, grammar: O
 
 def chat_samples(messages: List[Dict[str, str]], n: int, max_new_tokens: Optional[int] = None,
                  grammar: Optional[TokenGrammar] = None, sampling: Optional[SamplingParams] = None,
-                 streams: Optional[Sequence[int]] = None, speculate: int = 0) -> Tuple[List[str], str]:
+                 streams: Optional[Sequence[int]] = None, speculate: int = 0, logprobs: Optional[int] = None
+                 ) -> Tuple[List[str], str]:
     """(n replies, model id) from the registered native model's generate_text_samples (native_samples()).  ValueError
-    (the prompt does not fit) passes through, as from chat().  speculate > 0: a model with supports_speculation only."""
+    (the prompt does not fit) passes through, as from chat().  speculate > 0: a model with supports_speculation only; logprobs: one with supports_logprobs only."""
     llm = _llm
     if not llm_enabled() or not _is_native(settings.llm_base_url) or llm is None:
         raise AnswerClientError("native LLM is not loaded (call set_llm)")
@@ -227,7 +245,8 @@ def chat_samples(messages: List[Dict[str, str]], n: int, max_new_tokens: Optiona
             texts = llm.generate_text_samples(messages, int(n), int(max_new_tokens or settings.llm_max_new_tokens),
                                               grammar=grammar, sampling=sampling,
                                               streams=None if streams is None else [int(x) for x in streams],
-                                              **({"speculate": int(speculate)} if speculate else {}))
+                                              **({"speculate": int(speculate)} if speculate else {}),
+                                              **({} if logprobs is None else {"logprobs": int(logprobs)}))
     except (AnswerClientError, ValueError):
         raise
     except Exception as exc:  # noqa: BLE001 - callers rely on a single error type
@@ -238,16 +257,19 @@ def chat_samples(messages: List[Dict[str, str]], n: int, max_new_tokens: Optiona
 
 
 def chat(messages: List[Dict[str, str]], max_new_tokens: Optional[int] = None, grammar: Optional[TokenGrammar] = None,
-         sampling: Optional[SamplingParams] = None, stream: int = 0, speculate: int = 0) -> Tuple[str, str]:
+         sampling: Optional[SamplingParams] = None, stream: int = 0, speculate: int = 0,
+         logprobs: Optional[int] = None) -> Tuple[str, str]:
     """(reply, model id) from the configured LLM.  grammar: native backend only (an HTTP service cannot take one).
     speculate > 0: native backend only, a model with supports_speculation (native_speculation()).
     sampling: None is greedy; a native model must have supports_sampling (native_sampling()), and draws on noise stream
-    `stream`; an HTTP service gets temperature, top_p and seed."""
+    `stream`; an HTTP service gets temperature, top_p and seed.
+    logprobs: native backend only, a model with supports_logprobs (native_logprobs()); its records are in the model's
+    last_logprobs."""
     if not llm_enabled():
         raise AnswerClientError("LLM_BASE_URL is not configured")
     budget = int(max_new_tokens or settings.llm_max_new_tokens)
     if _is_native(settings.llm_base_url):
-        return _chat_native(messages, budget, grammar, sampling, stream, speculate)
+        return _chat_native(messages, budget, grammar, sampling, stream, speculate, logprobs)
     return _chat_http(messages, budget, sampling)
 
 
@@ -270,6 +292,26 @@ def native_samples() -> bool:
 def native_speculation() -> bool:
     """The backend is native and the registered model takes speculate=k."""
     return _is_native(settings.llm_base_url) and bool(getattr(_llm, "supports_speculation", False))
+
+
+def native_logprobs() -> bool:
+    """The backend is native and the registered model takes logprobs=n."""
+    return _is_native(settings.llm_base_url) and bool(getattr(_llm, "supports_logprobs", False))
+
+
+def logprobs_for(request: Any) -> bool:
+    """The request's `logprobs` over ANSWER_LOGPROBS."""
+    given = getattr(request, "logprobs", None)
+    return bool(settings.answer_logprobs if given is None else given)
+
+
+def sample_rank_for(request: Any) -> str:
+    """The request's `sample_rank` over ANSWER_SAMPLE_RANK.  AnswerRequestError: neither "first" nor "logprob"."""
+    given = getattr(request, "sample_rank", None)
+    rank = settings.answer_sample_rank if given is None else given
+    if rank not in ("first", "logprob"):
+        raise AnswerRequestError(f'sample_rank must be "first" or "logprob" (got {rank!r})')
+    return rank
 
 
 def speculate_for(request: Any) -> int:
@@ -327,7 +369,7 @@ def _grammar_for(items: Sequence[Dict[str, Any]], notes: Dict[str, Any]) -> Opti
 @dataclass
 class AnswerRequest(_retrieve.RetrieveRequest):
     """The /retrieve request plus echo_evidence, the optional sampling fields, `samples`, the candidates per attempt, and
-    `speculate`, the drafts per forward (None: the ANSWER_* default)."""
+    `speculate`, the drafts per forward, `logprobs` and `sample_rank` (None: the ANSWER_* default)."""
     echo_evidence: bool = False
     temperature: Optional[float] = None
     top_p: Optional[float] = None
@@ -336,6 +378,8 @@ class AnswerRequest(_retrieve.RetrieveRequest):
     seed: Optional[int] = None
     samples: Optional[int] = None
     speculate: Optional[int] = None
+    logprobs: Optional[bool] = None
+    sample_rank: Optional[str] = None
 
 
 def _evidence_items(pack: Dict[str, Any]) -> List[Dict[str, Any]]:
@@ -374,6 +418,8 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
     sampling = sampling_for(request)
     n_samples = samples_for(request)
     speculate = speculate_for(request)
+    want_logprobs = logprobs_for(request)
+    rank_mode = sample_rank_for(request)
     pack_request = _retrieve.RetrieveRequest(query=request.query, intent=request.intent, filters=request.filters,
                                              budget=request.budget, return_style="evidence_pack_json", debug=request.debug,
                                              facets=request.facets, facet_top=request.facet_top)
@@ -394,6 +440,13 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
     if speculate and not native_speculation():   # off by default: no such note
         notes["speculation"] = {"applied": False}
         speculate = 0
+    ranked = rank_mode == "logprob" and multi and native_logprobs()
+    if rank_mode == "logprob" and not ranked:    # "first" by default: no such entry
+        notes["samples"] = dict(notes.get("samples") or {}, ranked=False)
+    if want_logprobs and not native_logprobs():  # off by default: no such note
+        notes["logprobs"] = {"applied": False}
+        want_logprobs = False
+    scoring = 0 if (want_logprobs or ranked) else None   # the model's logprobs=: the records, no top entries
     out: Dict[str, Any] = {"query_id": pack["query_id"], "answer": None, "status": STATUS_INSUFFICIENT, "citations": [],
                            "repairs": 0, "model": None, "notes": notes}
     if getattr(request, "echo_evidence", False):
@@ -406,8 +459,9 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
 
     constrained = constrained_decoding()
 
-    def call(attempt: int) -> List[str]:
-        """The candidates of one attempt: one reply, or under `multi` n_samples from one call."""
+    def call(attempt: int) -> Tuple[List[str], Optional[List[list]]]:
+        """The candidates of one attempt: one reply, or under `multi` n_samples from one call; and under `scoring` the
+        TokenLogprob records of each."""
         while True:
             try:
                 # the grammar of the items in THIS prompt: rebuilt when an item has been dropped for length
@@ -416,11 +470,13 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
                     texts, model = chat_samples(build_messages(query, items, turns), n_samples, grammar=grammar,
                                                 sampling=sampling,
                                                 streams=[attempt * n_samples + i for i in range(n_samples)],
-                                                speculate=speculate)
+                                                speculate=speculate, logprobs=scoring)
                 else:
                     extra = {} if sampling is None else {"sampling": sampling, "stream": attempt}
                     if speculate:
                         extra["speculate"] = speculate
+                    if scoring is not None:
+                        extra["logprobs"] = scoring
                     text, model = chat(build_messages(query, items, turns), grammar=grammar, **extra)
                     texts = [text]
             except ValueError as exc:   # the prompt does not fit the model's context: the lowest-ranked item goes
@@ -439,24 +495,41 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
                     int(reuse["reused"][0] if multi else sum(reuse["reused"]))
             if speculate:   # what the last call drafted and kept
                 notes["speculation"] = getattr(_llm, "last_speculation", None)
-            return texts
+            records = None
+            if scoring is not None:
+                records = getattr(_llm, "last_logprobs", None)
+                if not isinstance(records, list) or len(records) != len(texts):
+                    raise AnswerClientError(f"native LLM left no token log-probabilities for its {len(texts)} replies")
+            return texts, records
 
     max_repairs = max(int(settings.answer_max_repairs), 0)
     for attempt in range(max_repairs + 1):
-        texts = [t.strip() for t in call(attempt)]
+        texts, records = call(attempt)
+        texts = [t.strip() for t in texts]
         out["repairs"] = attempt
         ids = [i["evidence_id"] for i in items]
         # judged in index order; None: the candidate says INSUFFICIENT_EVIDENCE
         reports = [None if t.strip(" .\"'`*") == INSUFFICIENT else validate_citations(t, ids) for t in texts]
-        chosen = next((i for i, r in enumerate(reports) if r is not None and r["valid"]), None)
+        order = list(range(len(texts)))
+        if ranked:   # by mean token log-probability, the lowest index among equals (a reply without a token last)
+            scores = [mean_logprob(rec) for rec in records]
+            order.sort(key=lambda i: -(scores[i] if scores[i] is not None and scores[i] == scores[i] else float("-inf")))
+        chosen = next((i for i in order if reports[i] is not None and reports[i]["valid"]), None)
         if multi:
             notes["samples"] = {"drawn": len(texts), "valid": sum(1 for r in reports if r is not None and r["valid"]),
                                 "chosen": chosen}
+            if ranked:
+                notes["samples"].update(scores=scores, ranked=True)
+            elif rank_mode == "logprob":
+                notes["samples"]["ranked"] = False
+        if want_logprobs:   # of the judged candidate: the chosen one, or the one the repair turn will quote
+            judged = chosen if chosen is not None else next((i for i in order if reports[i] is not None), order[0])
+            notes["logprobs"] = summarise(records[judged])
         if all(r is None for r in reports):
             out["status"] = STATUS_INSUFFICIENT
             return out
-        if chosen is None:   # the repair turn quotes the first candidate that tried to answer
-            chosen = next(i for i, r in enumerate(reports) if r is not None)
+        if chosen is None:   # the repair turn quotes the first candidate, in that order, that tried to answer
+            chosen = next(i for i in order if reports[i] is not None)
         text, report = texts[chosen], reports[chosen]
         notes["validator"] = report
         if report["valid"]:

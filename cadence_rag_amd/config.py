@@ -83,6 +83,13 @@ class Settings:
     # supports_speculation verifies up to that many prompt-lookup drafts per forward.  The reply does not depend on it;
     # 0 = off, the plain token loop
     answer_speculate: int = 0
+    # token log-probabilities of /answer (a request's `logprobs` overrides it): a native model with supports_logprobs
+    # scores every token it produces (crag_enc_logprobs) and notes.logprobs describes the returned answer.  Off: nothing
+    # is launched and there is no such note
+    answer_logprobs: bool = False
+    # how the answer is chosen among several valid candidates (a request's `sample_rank` overrides it): "first" -- the
+    # lowest index -- or "logprob" -- the highest mean token log-probability, which needs samples > 1 and such a model
+    answer_sample_rank: str = "first"
 
     def __post_init__(self) -> None:
         if self.rerank_device < 0:

@@ -1,8 +1,8 @@
 // crag_enc_common.h — the small helpers shared by the encoder-lane translation units (crag_encoder.hip,
 // crag_attention.hip, crag_encoder_small.hip, crag_encoder_wide.hip, crag_rerank.hip, crag_decode.hip, crag_extend.hip,
-// crag_grammar.hip, crag_sample.hip): vector types, error reporting, bf16 conversion, fragment load, block and half-wave
-// reductions, the per-head RMSNorm + RoPE of one head vector, the append of a row to the KV cache, the (value, id)
-// order of every greedy selection and its workgroup merge.  Internal linkage: nothing here is exported.
+// crag_grammar.hip, crag_sample.hip, crag_logprobs.hip): vector types, error reporting, bf16 conversion, fragment load,
+// block and half-wave reductions, the per-head RMSNorm + RoPE of one head vector, the append of a row to the KV cache, the
+// order-preserving key of a float, the (value, id) order of every greedy selection and its workgroup merge.  Internal linkage: nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -131,6 +131,17 @@ __device__ __forceinline__ void kv_append_row(const u16 *row, const u16 *qw, con
         *reinterpret_cast<Pack8 *>(v_cache + kv_row(hkv, max_len, slot, kvh, pos) + ch * 8) =
             *reinterpret_cast<const Pack8 *>(row + (int64_t)(heads + kvh) * CRAG_HEAD_DIM + ch * 8);
     }
+}
+
+// float <-> key (crag_sample.hip's cuts, crag_logprobs.hip's rank and top entries): a > b as floats exactly when
+// key(a) > key(b); -0 and +0 share a key
+__device__ __forceinline__ uint32_t fkey(float f) {
+    uint32_t b = __float_as_uint(f);
+    if (b == 0x80000000u) b = 0;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float kfloat(uint32_t k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -61,16 +61,6 @@ struct Pick {
     int nocut;
 };
 
-// float <-> key: a > b as floats exactly when key(a) > key(b); -0 and +0 share a key
-__device__ __forceinline__ uint32_t fkey(float f) {
-    uint32_t b = __float_as_uint(f);
-    if (b == 0x80000000u) b = 0;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float kfloat(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
 // word 0 of Philox4x32-10
 __device__ __forceinline__ uint32_t philox_x0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #pragma unroll

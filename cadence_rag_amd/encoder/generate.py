@@ -26,6 +26,9 @@ kernels) with a full-vocabulary head -- the in-process LLM behind /answer (caden
                         behind it, through crag_enc_decode_attention_rows.  generate(speculate=k) drafts by prompt
                         lookup (cadence_rag_amd.speculate), verifies the drafts in one such forward and keeps the
                         tokens the plain loop would have produced (_speculative_loop); off by default.
+  logprobs=n            generate / generate_samples score every produced token with crag_enc_logprobs on the logits it
+                        was picked from (last_logprobs: token, logprob, rank, the mass a grammar left allowed, the n most
+                        likely ids); score(prompts, continuations) gives the same records for text it is handed.
 
 The cache layout ([layer][slot][kv head][max_len][128] bf16, keys and values apart) sits behind KvCache.keys / .values.
 At most MAX_SEQS = 8 sequences decode at a time.
@@ -40,6 +43,7 @@ import torch
 import torch.nn.functional as F
 
 from ..grammar import KIND_STOP, TokenGrammar, TokenTable
+from ..logprobs import TokenLogprob
 from ..sampling import SamplingParams
 from ..speculate import MAX_SPECULATE, propose_drafts
 from . import ops
@@ -159,9 +163,17 @@ class _Picker:
     by ops.sample, the allowed greedy one by ops.grammar_argmax, or drawn among the allowed ones.  It holds the draws and
     streams per prompt, and under a grammar the tables and every prompt's automaton state on the device."""
 
-    def __init__(self, gen: "Qwen3Generator", n: int, grammar: Optional[TokenGrammar], sampling, streams) -> None:
+    def __init__(self, gen: "Qwen3Generator", n: int, grammar: Optional[TokenGrammar], sampling, streams,
+                 logprobs: Optional[int] = None) -> None:
         self.device = gen.device
         self.table = self.draws = None
+        # logprobs = n_top: every pick is scored by ops.logprobs on the logits it was picked from; `scores` then holds the
+        # TokenLogprob of every row of the last pick, and the token loops file those of the tokens they emit in `records`
+        self.n_top = None if logprobs is None else _check_logprobs(logprobs, gen.cfg.vocab_size)
+        self.scores: Optional[List[TokenLogprob]] = None
+        self.records: Optional[List[List[TokenLogprob]]] = None if logprobs is None else [[] for _ in range(n)]
+        if logprobs is not None and n > gen.max_seqs:
+            raise ValueError(f"logprobs takes 1..{gen.max_seqs} prompts")
         if grammar is not None:
             self.table = grammar.table if grammar.table is not None else gen.token_table()
             if self.table.vocab != gen.cfg.vocab_size:
@@ -186,19 +198,58 @@ class _Picker:
 
     def __call__(self, rows: List[int], logits: torch.Tensor, greedy_tokens: torch.Tensor, step: int) -> List[int]:
         if self.table is None:
-            return (greedy_tokens if self.draws is None else self._draw(rows, logits, step)).tolist()
+            token = greedy_tokens if self.draws is None else self._draw(rows, logits, step)
+            if self.n_top is not None:
+                self.scores = score_rows(logits, token, self.n_top)
+            return token.tolist()
         idx = torch.tensor(rows, dtype=torch.int64).to(self.device)
         cur = self.state.index_select(0, idx)      # the states of `rows`: they move on behind the chosen tokens
         token = torch.empty(len(rows), dtype=torch.int32, device=self.device)
-        if self.draws is None:
-            ops.grammar_argmax(logits, *self.tables, cur, token)
-        else:   # grammar_argmax hands out the bits on a copy of the states; its own token is dropped
+        bits = None
+        if self.draws is not None or self.n_top is not None:
             bits = torch.empty(len(rows), (self.table.vocab + 31) // 32, dtype=torch.int32, device=self.device)
+        if self.draws is None:
+            ops.grammar_argmax(logits, *self.tables, cur, token, allowed_bits=bits)
+        else:   # grammar_argmax hands out the bits on a copy of the states; its own token is dropped
             ops.grammar_argmax(logits, *self.tables, cur.clone(), token, allowed_bits=bits)
             token = self._draw(rows, logits, step, bits)
             ops.grammar_advance(*self.tables[:5], cur, token)
         self.state.index_copy_(0, idx, cur)
+        if self.n_top is not None:   # the bits grammar_argmax handed out: the mass the automaton left allowed
+            self.scores = score_rows(logits, token, self.n_top, bits)
         return token.tolist()
+
+    def file(self, b: int, k: int) -> None:
+        """The token loop emitted row k of the last pick as a token of prompt b: its record is kept."""
+        if self.records is not None:
+            self.records[b].append(self.scores[k])
+
+
+def _check_logprobs(logprobs, vocab: int) -> int:
+    if isinstance(logprobs, bool) or int(logprobs) != logprobs or not 0 <= int(logprobs) <= min(ops.MAX_TOP_LOGPROBS, vocab):
+        raise ValueError(f"logprobs must be None or an integer in 0..{min(ops.MAX_TOP_LOGPROBS, vocab)} (got {logprobs!r})")
+    return int(logprobs)
+
+
+def score_rows(logits: torch.Tensor, token: torch.Tensor, n_top: int, bits: Optional[torch.Tensor] = None
+               ) -> List[TokenLogprob]:
+    """One TokenLogprob per row of logits [n <= 8, vocab] for the ids token [n] (int32, device): ops.logprobs, its
+    float outputs in one buffer and its integer outputs in another, so that two copies bring everything to the host.
+    bits: the allowed flags of a grammar; the records then carry allowed_logmass = lse_allowed - lse_all."""
+    n, dev = logits.shape[0], logits.device
+    f = torch.empty(n * (3 + n_top), dtype=torch.float32, device=dev)
+    i = torch.empty(n * (1 + n_top), dtype=torch.int32, device=dev)
+    top_lp = f[3 * n:].view(n, n_top) if n_top else None
+    top_id = i[n:].view(n, n_top) if n_top else None
+    ops.logprobs(logits, token.contiguous(), f[:n], allowed_bits=bits, lse_all=f[n:2 * n],
+                 lse_allowed=f[2 * n:3 * n] if bits is not None else None, rank=i[:n], top_id=top_id, top_logprob=top_lp)
+    ids, fh, ih = token.tolist(), f.tolist(), i.tolist()
+    out = []
+    for r in range(n):
+        top = [(ih[n + r * n_top + k], fh[3 * n + r * n_top + k]) for k in range(n_top)]
+        mass = fh[2 * n + r] - fh[n + r] if bits is not None else None
+        out.append(TokenLogprob(int(ids[r]), fh[r], ih[r], mass, top))
+    return out
 
 
 class Qwen3Generator:
@@ -208,6 +259,7 @@ class Qwen3Generator:
     supports_sampling = True  # ... and sampling=SamplingParams
     supports_samples = True   # generate_text_samples: n replies from one prefill
     supports_speculation = True   # ... and speculate=k: up to k prompt-lookup drafts verified per forward
+    supports_logprobs = True      # ... and logprobs=n: last_logprobs holds a TokenLogprob per produced token
 
     def __init__(self, encoder: Qwen3Encoder, lm_head: torch.Tensor, tokenizer=None, *, max_context: Optional[int] = None,
                  max_seqs: int = MAX_SEQS, model_id: Optional[str] = None, prefix_cache: bool = False) -> None:
@@ -241,6 +293,8 @@ class Qwen3Generator:
         self.last_reuse: Optional[Dict[str, List[int]]] = None   # per prompt of the last generate(reuse_prefix=True)
         self.last_grammar: Optional[Dict[str, List[bool]]] = None   # per prompt of the last generate(grammar=...)
         self.last_speculation: Optional[Dict[str, object]] = None   # of the last generate(speculate=k > 0)
+        self.last_logprobs: Optional[List[List[TokenLogprob]]] = None   # per prompt of the last generate(logprobs=n)
+        self.last_score_logits: Optional[List[torch.Tensor]] = None     # of the last score(keep_logits=True)
         self._token_table: Optional[TokenTable] = None   # the vocabulary's bytes: built once, its tensors stay in HBM
         self.force_library = False         # tests: keep the 4B widths off the small_gemm path
         self.last_path = ""
@@ -364,8 +418,17 @@ class Qwen3Generator:
     def prefill(self, token_lists: Sequence[Sequence[int]], slots: Optional[Sequence[int]] = None) -> torch.Tensor:
         """Fills slot slots[b] (default b) with prompt b and makes these the live sequences.  Returns the last-token
         logits [n, vocab] fp32 on the device; .last_tokens holds their greedy tokens (int32 [n], device)."""
-        c, enc, dev, bf = self.cfg, self.encoder, self.device, torch.bfloat16
         slots = self._check_slots("prefill takes 1..%d prompts, each in a slot of its own", len(token_lists), slots)
+        resid, delta, batch = self._prefill_rows(token_lists, slots)
+        logits, self.last_tokens = self._head(resid.index_select(0, batch.last_tok),
+                                              delta.index_select(0, batch.last_tok))
+        return logits
+
+    def _prefill_rows(self, token_lists: Sequence[Sequence[int]], slots: List[int]):
+        """prefill's layers over every row of the prompts: fills the slots, makes them the live sequences and returns
+        (resid, delta, batch) -- the hidden state of packed row i is resid[i] + delta[i] (prefill heads the last rows,
+        score the rows that predict a continuation)."""
+        c, enc, dev, bf = self.cfg, self.encoder, self.device, torch.bfloat16
         lens = [len(tl) for tl in token_lists]
         if min(lens) <= 0:
             raise ValueError("every prompt needs at least one token")
@@ -403,9 +466,7 @@ class Qwen3Generator:
             self.cache.lens[slot] = m
             self.tokens[slot] = [int(x) for x in tl]
         self.live = list(slots)
-        logits, self.last_tokens = self._head(resid.index_select(0, batch.last_tok),
-                                              delta.index_select(0, batch.last_tok))
-        return logits
+        return resid, delta, batch
 
     @torch.no_grad()
     def extend(self, token_lists: Sequence[Sequence[int]], slots: Optional[Sequence[int]] = None) -> torch.Tensor:
@@ -625,7 +686,7 @@ class Qwen3Generator:
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_ids: Sequence[int] = (),
                  reuse_prefix: bool = False, grammar: Optional[TokenGrammar] = None,
                  sampling=None, streams: Optional[Sequence[int]] = None, speculate: int = 0,
-                 drafter=None) -> List[List[int]]:
+                 drafter=None, logprobs: Optional[int] = None) -> List[List[int]]:
         """Greedy continuation of every prompt (token ids): at most max_new_tokens ids each, ending before the first
         stop id.  A prompt longer than max_context - max_new_tokens raises PromptTooLong (a ValueError): the caller
         shortens its prompt, nothing is truncated here.
@@ -646,7 +707,12 @@ class Qwen3Generator:
         speculate: k in 0..7 -- up to k drafted tokens per sequence are verified in one forward (_speculative_loop); the
         ids returned are those of speculate=0 whatever is drafted.  drafter: (ids, max_draft) -> ids, default
         speculate.propose_drafts.  last_speculation then holds the forwards and the drafted / accepted counts per
-        prompt (None with 0, which runs the plain loop)."""
+        prompt (None with 0, which runs the plain loop).
+        logprobs: None launches nothing.  n in 0..16: every produced token is scored by ops.logprobs on the logits it was
+        picked from, the picked id still on the device -- in every picking mode and in both loops; under speculation a
+        token is scored on the row that verified it, and a rejected draft leaves nothing.  last_logprobs[b] then holds one
+        TokenLogprob (token, logprob, rank, allowed_logmass under a grammar, the n most likely (id, logprob)) per id
+        returned for prompt b; a stop token leaves none.  The ids returned do not depend on it."""
         max_new_tokens, speculate = int(max_new_tokens), self._check_speculate(speculate)
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be positive")
@@ -656,7 +722,7 @@ class Qwen3Generator:
             raise PromptTooLong(f"a prompt of {longest} tokens does not fit: max_context {self.max_context} - "
                                 f"max_new_tokens {max_new_tokens} leaves {room}")
         stop = {int(s) for s in stop_ids}
-        pick = _Picker(self, len(prompts), grammar, sampling, streams)
+        pick = _Picker(self, len(prompts), grammar, sampling, streams, logprobs)
         keeps = [0] * len(prompts)
         if reuse_prefix and len(prompts) <= self.max_seqs:
             keeps = [plan_reuse(self.resident(b), p, PREFIX_MIN_REUSE) for b, p in enumerate(prompts)]
@@ -671,6 +737,7 @@ class Qwen3Generator:
         out, accepted = self._decode(pick, [list(p) for p in prompts], logits, self.last_tokens, max_new_tokens, stop,
                                      speculate, drafter)
         self.last_grammar = {"accepted": accepted} if grammar is not None else None
+        self.last_logprobs = pick.records
         return out
 
     @staticmethod
@@ -699,13 +766,14 @@ class Qwen3Generator:
         produced = 0    # tokens every live sequence has so far, the step of the next draw
         while live:
             feed, keep = [], []
-            for b, tok in zip(live, pick(live, logits, greedy, produced)):
+            for k, (b, tok) in enumerate(zip(live, pick(live, logits, greedy, produced))):
                 if pick.table is not None and tok >= 0 and pick.table.kind[tok] == KIND_STOP:
                     accepted[b] = True
                     continue
                 if tok in stop or tok < 0:
                     continue
                 out[b].append(int(tok))
+                pick.file(b, k)
                 if len(out[b]) < max_new_tokens:
                     keep.append(b)
                     feed.append(int(tok))
@@ -749,6 +817,7 @@ class Qwen3Generator:
                     if tok in stop or tok < 0:
                         break
                     out[b].append(int(tok))
+                    pick.file(b, 0)   # scored on row i, the row that verified it; a rejected draft is never picked
                     if len(out[b]) >= max_new_tokens:
                         break
                     if i < len(drafts) and drafts[i] == tok:   # row i + 1 was computed behind the right token
@@ -789,6 +858,51 @@ class Qwen3Generator:
         self.last_speculation = stats
         return out, accepted
 
+    @torch.no_grad()
+    def score(self, prompts: Sequence[Sequence[int]], continuations: Sequence[Sequence[int]],
+              slots: Optional[Sequence[int]] = None, top: int = 0, keep_logits: bool = False
+              ) -> List[List[TokenLogprob]]:
+        """Teacher-forced records of given continuations: for each of the 1..max_seqs sequences one TokenLogprob per id
+        of continuations[b], scored behind prompts[b] and the ids before it, with the `top` (0..16) most likely ids of
+        its row -- generate(logprobs=top)'s records for text the generator is handed.  prefill's layers run over prompt +
+        continuation (PromptTooLong as from prefill); crag_enc_lm_head and crag_enc_logprobs then run over the rows that
+        predict a continuation id in blocks of at most 8, so [rows, vocab] never exists beyond one block.  Afterwards
+        slot slots[b] (default b) holds prompt + continuation as after a prefill, ids and all, for a following
+        generate(reuse_prefix=True).  keep_logits (tests with tiny vocabularies): last_score_logits[b] keeps the fp32
+        logits [len(continuations[b]), vocab] that were scored; None otherwise."""
+        n = len(prompts)
+        slots = self._check_slots("score takes 1..%d sequences, each in a slot of its own", n, slots)
+        top = _check_logprobs(top, self.cfg.vocab_size)
+        if len(continuations) != n or any(len(p) < 1 for p in prompts) or any(len(c) < 1 for c in continuations):
+            raise ValueError("score needs one continuation per prompt, and at least one token in each of them")
+        conts = [[int(t) for t in c] for c in continuations]
+        full = [[int(t) for t in p] + c for p, c in zip(prompts, conts)]
+        resid, delta, _ = self._prefill_rows(full, slots)
+        # packed row start + len(prompt) - 1 + j predicts continuation id j
+        rows, ids, start = [], [], 0
+        for p, c, seq in zip(prompts, conts, full):
+            rows += [start + len(p) - 1 + j for j in range(len(c))]
+            ids += c
+            start += len(seq)
+        records: List[TokenLogprob] = []
+        kept: List[torch.Tensor] = []
+        for lo in range(0, len(rows), MAX_ROWS):
+            idx = torch.tensor(rows[lo:lo + MAX_ROWS], dtype=torch.int64).to(self.device)
+            logits, _ = self._head(resid.index_select(0, idx), delta.index_select(0, idx))
+            token = torch.tensor(ids[lo:lo + MAX_ROWS], dtype=torch.int32).to(self.device)
+            records += score_rows(logits, token, top)
+            if keep_logits:
+                kept.append(logits)
+        out, logit_rows, lo = [], [], 0
+        every = torch.cat(kept) if keep_logits else None
+        for c in conts:
+            out.append(records[lo:lo + len(c)])
+            if keep_logits:
+                logit_rows.append(every[lo:lo + len(c)])
+            lo += len(c)
+        self.last_score_logits = logit_rows if keep_logits else None
+        return out
+
     def fork(self, src: int, dst_slots: Sequence[int]) -> None:
         """KvCache.fork: the dst slots hold what src holds without a copy.  Their ids count as unknown, so plan_reuse
         never keeps a child's rows."""
@@ -800,7 +914,7 @@ class Qwen3Generator:
     def generate_samples(self, prompt: Sequence[int], n: int, max_new_tokens: int, stop_ids: Sequence[int] = (),
                          reuse_prefix: bool = False, grammar: Optional[TokenGrammar] = None,
                          sampling=None, streams: Optional[Sequence[int]] = None, speculate: int = 0,
-                         drafter=None) -> List[List[int]]:
+                         drafter=None, logprobs: Optional[int] = None) -> List[List[int]]:
         """n (1..max_seqs) continuations of ONE prompt from one prefill: the prompt goes into slot 0 (prefill, or extend
         behind what plan_reuse keeps under reuse_prefix, as in generate), slots 1..n-1 are forked from it, the one row
         of logits serves every sequence's first pick, and generate's token loop runs over the n slots: a child reads
@@ -809,7 +923,7 @@ class Qwen3Generator:
         Afterwards the children are empty and slot 0 holds the prompt and continuation 0 with their ids, for a later
         reuse_prefix.  last_reuse / last_grammar hold one entry per sample (the prompt's rows were reused / computed
         once, for all of them).  n = 1 is generate([prompt], ...).  speculate / drafter: as in generate; every sample
-        drafts from the prompt and its own output."""
+        drafts from the prompt and its own output.  logprobs: as in generate, last_logprobs[i] for sample i."""
         n, max_new_tokens, speculate = int(n), int(max_new_tokens), self._check_speculate(speculate)
         if not 1 <= n <= self.max_seqs:
             raise ValueError(f"generate_samples takes n in 1..{self.max_seqs}")
@@ -819,7 +933,7 @@ class Qwen3Generator:
         if len(prompt) > room:
             raise PromptTooLong(f"a prompt of {len(prompt)} tokens does not fit: max_context {self.max_context} - "
                                 f"max_new_tokens {max_new_tokens} leaves {room}")
-        pick = _Picker(self, n, grammar, sampling, streams)
+        pick = _Picker(self, n, grammar, sampling, streams, logprobs)
         keep = plan_reuse(self.resident(0), prompt, PREFIX_MIN_REUSE) if reuse_prefix else 0
         if keep:
             self.truncate(0, keep)
@@ -839,25 +953,28 @@ class Qwen3Generator:
             for child in range(1, n):
                 self.truncate(child, 0)
         self.last_grammar = {"accepted": accepted} if grammar is not None else None
+        self.last_logprobs = pick.records
         return out
 
     def generate_text_samples(self, messages: Sequence[Dict[str, str]], n: int, max_new_tokens: int,
                               grammar: Optional[TokenGrammar] = None, sampling: Optional[SamplingParams] = None,
-                              streams: Optional[Sequence[int]] = None, speculate: int = 0, drafter=None) -> List[str]:
-        """One chat -> n replies as text from one prefill (generate_samples), reply i drawn on noise stream streams[i]."""
+                              streams: Optional[Sequence[int]] = None, speculate: int = 0, drafter=None,
+                              logprobs: Optional[int] = None) -> List[str]:
+        """One chat -> n replies as text from one prefill (generate_samples), reply i drawn on noise stream streams[i];
+        logprobs: last_logprobs[i] holds reply i's records."""
         ids = self.generate_samples(self.chat_ids(messages), n, max_new_tokens, self.stop_ids(),
                                     reuse_prefix=self.prefix_cache, grammar=grammar, sampling=sampling, streams=streams,
-                                    speculate=speculate, drafter=drafter)
+                                    speculate=speculate, drafter=drafter, logprobs=logprobs)
         tok = self._tokenizer()
         return [tok.decode(x, skip_special_tokens=True) for x in ids]
 
     def generate_text(self, messages: Sequence[Dict[str, str]], max_new_tokens: int,
                       grammar: Optional[TokenGrammar] = None, sampling: Optional[SamplingParams] = None,
-                      stream: int = 0, speculate: int = 0, drafter=None) -> str:
+                      stream: int = 0, speculate: int = 0, drafter=None, logprobs: Optional[int] = None) -> str:
         """One chat -> the assistant's reply as text; under `grammar` when one is given, drawn with `sampling` on noise
-        stream `stream` when that is given (generate)."""
+        stream `stream` when that is given (generate); logprobs: last_logprobs[0] holds the reply's records."""
         ids = self.generate([self.chat_ids(messages)], max_new_tokens, self.stop_ids(),
                             reuse_prefix=self.prefix_cache, grammar=grammar, sampling=sampling,
                             streams=None if sampling is None else [int(stream)], speculate=speculate,
-                            drafter=drafter)[0]
+                            drafter=drafter, logprobs=logprobs)[0]
         return self._tokenizer().decode(ids, skip_special_tokens=True)

@@ -515,6 +515,48 @@ def grammar_advance(tok_offsets, tok_bytes, tok_kind, class_of, trans, state, to
     return state
 
 
+# -- token log-probabilities (csrc/crag_logprobs.hip) -------------------------------------------------------------------
+MAX_TOP_LOGPROBS = 16   # CRAG_LOGPROBS_MAX_TOP
+
+
+def logprobs(logits, token, logprob, *, allowed_bits=None, lse_all=None, lse_allowed=None, rank=None, top_id=None,
+             top_logprob=None):
+    """Per row of logits [n <= 8, vocab] fp32: logprob[r] (float32) = the log-probability of token[r] (int32, device)
+    under the row's own softmax (crag_enc_logprobs; the rule: cadence_rag_amd.logprobs.logprobs_host).  Optional outputs:
+    lse_all / lse_allowed float32 [n] (the log-sum-exp over every id that is not NaN, and over those whose bit is set in
+    allowed_bits [n, ceil(vocab / 32)] int32, grammar_argmax's flags); rank int32 [n] (1 = the most likely id); top_id
+    int32 / top_logprob float32 [n, n_top], n_top <= 16, given together: the most likely ids over the whole row."""
+    _req(logits, torch.float32, "logits"); _req(token, torch.int32, "token"); _req(logprob, torch.float32, "logprob")
+    if logits.dim() != 2:
+        raise ValueError("logits must be [n, vocab]")
+    n, vocab = logits.shape
+    if token.numel() != n or logprob.numel() != n:
+        raise ValueError("token and logprob must be [n]")
+    if allowed_bits is not None:
+        _req(allowed_bits, torch.int32, "allowed_bits")
+        if allowed_bits.shape != (n, (vocab + 31) // 32):
+            raise ValueError("allowed_bits must be [n, ceil(vocab / 32)]")
+    for name, t, dtype in (("lse_all", lse_all, torch.float32), ("lse_allowed", lse_allowed, torch.float32),
+                           ("rank", rank, torch.int32)):
+        if t is not None:
+            _req(t, dtype, name)
+            if t.numel() != n:
+                raise ValueError(f"{name} must be [n]")
+    if (top_id is None) != (top_logprob is None):
+        raise ValueError("top_id and top_logprob are given together")
+    n_top = 0
+    if top_id is not None:
+        _req(top_id, torch.int32, "top_id"); _req(top_logprob, torch.float32, "top_logprob")
+        if top_id.dim() != 2 or top_id.shape[0] != n or top_logprob.shape != top_id.shape:
+            raise ValueError("top_id and top_logprob must both be [n, n_top]")
+        n_top = int(top_id.shape[1])
+    _native.check(_native.load().crag_enc_logprobs(
+        _p(logits), int(vocab), _p(allowed_bits), _p(token), _p(logprob), _p(lse_all), _p(lse_allowed), _p(rank),
+        _p(top_id) if n_top else None, _p(top_logprob) if n_top else None, n_top, int(n), _stream()),
+        "crag_enc_logprobs")
+    return logprob
+
+
 # -- continuing cached sequences (csrc/crag_extend.hip) ---------------------------------------------------------------
 def extend_workspace_bytes(n_seqs: int, hq: int, max_new_rows: int, max_len: int) -> int:
     """Bytes of scratch extend_attention needs at most for up to n_seqs sequences with up to max_new_rows new rows in

@@ -157,6 +157,8 @@ class AnswerRequestModel(RetrieveRequestModel):
     seed: Optional[int] = Field(default=None, ge=0, lt=2 ** 64)
     samples: Optional[int] = Field(default=None, ge=1, le=8)   # candidates per attempt (ANSWER_SAMPLES when absent)
     speculate: Optional[int] = Field(default=None, ge=0, le=7)   # drafts per forward (ANSWER_SPECULATE when absent)
+    logprobs: Optional[bool] = None      # score the answer's tokens (ANSWER_LOGPROBS when absent)
+    sample_rank: Optional[str] = None    # "first" or "logprob" (ANSWER_SAMPLE_RANK when absent); anything else is a 422
 
 
 @app.post("/answer")
@@ -164,7 +166,8 @@ def answer_endpoint(payload: AnswerRequestModel) -> dict:
     request = _answer.AnswerRequest(**_request_fields(payload), echo_evidence=payload.echo_evidence,
                                     temperature=payload.temperature, top_p=payload.top_p, top_k=payload.top_k,
                                     min_p=payload.min_p, seed=payload.seed, samples=payload.samples,
-                                    speculate=payload.speculate)
+                                    speculate=payload.speculate, logprobs=payload.logprobs,
+                                    sample_rank=payload.sample_rank)
     try:
         return _answer.answer_question(request)
     except _answer.AnswerRequestError as exc:

@@ -379,6 +379,37 @@ int crag_enc_grammar_advance(const int32_t *tok_offsets, const uint8_t *tok_byte
                              const uint8_t *class_of, const uint16_t *trans, int n_states, int n_classes, int32_t *state,
                              const int32_t *token, int n_rows, void *stream);
 
+/* ---- token log-probabilities: csrc/crag_logprobs.hip ----
+ *
+ * crag_enc_logprobs: per row r < n_rows (1..CRAG_DECODE_MAX_SEQS) of logits [n_rows, vocab] fp32, the model's own
+ *   distribution (temperature 1, no cut) at the id token[r] (device int32), whatever picked that id.
+ *   A CANDIDATE is an id whose logit is not NaN (-inf is one); an ALLOWED candidate has its bit set in allowed_bits[r]
+ *   ([n_rows, ceil(vocab / 32)], crag_enc_grammar_argmax's layout; NULL: every candidate).  m_all / m_alw = the maximum
+ *   logit of the two sets.  Every output is a device array; all but logprob are nullable.
+ *     lse_all[r]      m_all + ln sum exp(l - m_all) over the candidates
+ *     lse_allowed[r]  the same over the allowed candidates, relative to m_alw: finite however far they lie below m_all
+ *                     (lse_allowed - lse_all <= 0 is the log of the probability mass a grammar left allowed)
+ *                     Either: -inf for an empty set and for a set of -inf alone, +inf for a set whose maximum is +inf.
+ *     logprob[r]      l_token - lse_all[r] in fp32, by IEEE rules (finite - +inf = -inf, inf - inf = NaN); NaN when
+ *                     token[r] is outside 0..vocab - 1 or its logit is NaN
+ *     rank[r]         int32, 1 + the candidates whose logit is strictly greater than l_token (-0 == +0); 0 for a token
+ *                     outside 0..vocab - 1 or with a NaN logit
+ *     top_id [n_rows, n_top] int32 / top_logprob [n_rows, n_top] fp32: the n_top (0..CRAG_LOGPROBS_MAX_TOP) first
+ *                     candidates -- of all ids, not of the allowed ones -- in the order (logit descending, id
+ *                     ascending), each with l - lse_all[r]; a row with fewer candidates is padded with id -1 and NaN.
+ *   The weights are expf(l - m) summed as 64-bit fixed-point integers (unit 2^-40; crag_enc_sample's coarser unit for a
+ *   vocabulary whose sum would not fit), the counts integer sums, the top entries an exact selection on the
+ *   order-preserving key of the logit.  One workgroup per row; integer adds on LDS are the only atomics; every store is
+ *   a plain vector store.  The same inputs give the same bits on every run, and a row's outputs depend on its own
+ *   logits, bits and token alone -- not on n_rows or its position.
+ *   CRAG_EINVAL, nothing enqueued: a NULL logits, token or logprob; n_rows outside 1..8; vocab outside 1..2^31 - 1;
+ *   n_top outside 0..CRAG_LOGPROBS_MAX_TOP or above vocab; n_top > 0 with top_id or top_logprob NULL; a pointer that is
+ *   not aligned to its element. */
+#define CRAG_LOGPROBS_MAX_TOP 16
+int crag_enc_logprobs(const float *logits, int64_t vocab, const uint32_t *allowed_bits, const int32_t *token,
+                      float *logprob, float *lse_all, float *lse_allowed, int32_t *rank, int32_t *top_id,
+                      float *top_logprob, int n_top, int n_rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
