@@ -87,6 +87,7 @@ SIGNATURES = {
     "crag_index_profile_read_ex": (_c.c_int, [_P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_double),
                                               _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
     "crag_index_last_scan_kernel": (_c.c_char_p, [_P]),
+    "crag_index_scan_waits": (_c.c_char_p, [_P]),
     "crag_index_prefilter_row_bytes": (_c.c_int64, [_P]),
     "crag_index_search_pipelined": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _P, _c.c_int64, _P, _P, _P, _P, _c.c_int]),
     "crag_index_join": (_c.c_int, [_P, _P]),

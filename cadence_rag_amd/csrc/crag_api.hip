@@ -34,6 +34,10 @@ int init_index(crag_index *ix) {
     ix->sw.no_prefilter = getenv("CRAG_NO_PREFILTER") != nullptr;
     ix->sw.no_rsplit = getenv("CRAG_NO_RSPLIT") != nullptr;
     if (const char *v = getenv("CRAG_PF_NT")) ix->sw.pf_nt = atoi(v) ? 1 : 0;
+    if (const char *v = getenv("CRAG_PF_WAITS")) {
+        if (!strcmp(v, "tile")) ix->sw.pf_waits = crag::PF_WAITS_TILE;
+        else if (!strcmp(v, "fragment")) ix->sw.pf_waits = crag::PF_WAITS_FRAGMENT;
+    }
     if (const char *v = getenv("CRAG_PF_LAGS")) {
         int d = 0, r = 0;
         if (sscanf(v, "%d,%d", &d, &r) == 2 && d >= 1 && r > d && r <= 4) {
@@ -281,6 +285,7 @@ int crag_index_phase_trace(crag_index *ix, uint64_t *out128) {
 }
 
 const char *crag_index_last_scan_kernel(const crag_index *ix) { return ix ? ix->last_scan_kernel : ""; }
+const char *crag_index_scan_waits(const crag_index *ix) { return ix ? ix->last_scan_waits : ""; }
 
 int64_t crag_index_prefilter_row_bytes(const crag_index *ix) {
     if (!ix || ix->sw.no_prefilter) return 0;

@@ -254,7 +254,10 @@ int search_device(crag_index *ix, const SearchArgs &a, hipStream_t st) {
         const crag::PfParams fp = pf_params(ix, ws, pl, a, reverse);
         const int nqb = pl.wide ? 2 : 1;
         ws->dirty = true;   // until the selection launch is in the stream
-        HIP_TRY(crag::launch_prefilter(fp, nqb, pl.nq_pad / (32 * nqb), st, &ix->last_scan_kernel));
+        const int waits = pf_waits_for(ix->size * (int64_t)crag::DIM * 2, ix->corpus16 != nullptr, pl.nt, ix->sw.pf_waits);
+        HIP_TRY(crag::launch_prefilter(fp, nqb, pl.nq_pad / (32 * nqb), waits == crag::PF_WAITS_FRAGMENT, st,
+                                       &ix->last_scan_kernel));
+        ix->last_scan_waits = waits == crag::PF_WAITS_FRAGMENT ? "fragment" : "tile";
         if (ix->env_fail_after_scan > 0 && ++ix->pf_searches == ix->env_fail_after_scan)
             return fail(CRAG_EHIP, "injected failure behind the scan launch (CRAG_TEST_FAIL_AFTER_SCAN)");
         if (ev) HIP_TRY(hipEventRecord(ev->e2, st));
@@ -262,6 +265,7 @@ int search_device(crag_index *ix, const SearchArgs &a, hipStream_t st) {
         ws->dirty = false;
     } else {
         HIP_TRY(crag::launch_scan(sp, pl.q_blocks, st, &ix->last_scan_kernel));
+        ix->last_scan_waits = "tile";
         if (ev) HIP_TRY(hipEventRecord(ev->e2, st));
         HIP_TRY(crag::launch_merge_partials(mp, a.nq, st));
     }
@@ -300,6 +304,12 @@ int crag_search_plan_(int64_t size, int n_cu, int nq, int k, int has_mirror, int
     if (out) *out = plan_search(size, n_cu, nq, k, has_mirror != 0, irregular != 0, sw);
     return (int)sizeof(SearchPlan);
 }
+
+int crag_pf_waits_(int64_t mirror_bytes, int has_mirror, int nt, int pf_waits_switch) {
+    return pf_waits_for(mirror_bytes, has_mirror != 0, nt, pf_waits_switch);
+}
+
+int64_t crag_pf_frag_waits_max_bytes_(void) { return crag::PF_FRAG_WAITS_MAX_BYTES; }
 
 int crag_index_search_async(crag_index *ix, const float *d_queries, int nq, int k,
                             const uint8_t *d_row_mask, int64_t mask_stride, int64_t *d_out_ids,

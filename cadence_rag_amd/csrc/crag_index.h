@@ -79,6 +79,7 @@ struct crag_index {
     unsigned long long *pf_stats = nullptr;  // device: PF_STAT_SLOTS x {candidates, rescored rows, searches}
     unsigned long long *phase_trace = nullptr;  // device, 128 words; only with CRAG_PHASE_TRACE=1 (developer probe)
     const char *last_scan_kernel = "";  // name of the scan kernel the most recent search launched
+    const char *last_scan_waits = "";   // wait schedule of that scan's corpus loads: "tile" or "fragment"
     DevBuf stage_q, stage_rows, stage_ids, stage_mask, stage_out, scratch;
     // in-place edits (crag_index_remove / compact / insert): destination rows per chunk (CRAG_EDIT_CHUNK_ROWS; the default
     // keeps the bounce buffer, 6 156 bytes per row, below 128 MiB), the bounce buffer (held only during an edit), the

@@ -60,6 +60,11 @@ constexpr int PF_BOUND_CELLS = 160;
 constexpr int PF_STAT_WS = 8;                 // search workspaces per index (crag_index.h MAX_WS): a block of records each
 constexpr int PF_STAT_SLOTS = 2048;           // per-query statistics records (summed on the host when read)
 constexpr int PF_MIN_ROWS_PER_GROUP = 128;    // below this many rows per workgroup the plain fp32 scan is used
+// Wait schedule of the mirror scan (prefilter_kernel's FRAG).  A mirror up to the size of the 256 MiB Infinity Cache
+// takes the per-fragment waits, a larger one whole-tile bursts.  From the sweep in DESIGN.md 4.1: the per-fragment
+// schedule wins 0.3-1.2 us per search up to 125 000 rows (244 MiB), ties at 150 000 (293 MiB) and loses at 250 000.
+enum PfWaits { PF_WAITS_TILE = 0, PF_WAITS_FRAGMENT = 1 };
+constexpr int64_t PF_FRAG_WAITS_MAX_BYTES = 256ll << 20;
 
 struct PrepParams {
     const float *queries;     // [nq, dim] row-major fp32
@@ -141,8 +146,10 @@ struct XMergeParams {
 // kernel_name (nullable) receives the name of the kernel that was launched (a string literal)
 hipError_t launch_scan(const ScanParams &p, int q_blocks, hipStream_t st, const char **kernel_name);
 hipError_t launch_prep_queries(const PrepParams &p, int nq_pad, hipStream_t st);
-// passes = number of 32*nqb-query passes (grid.y); nqb = 1 or 2
-hipError_t launch_prefilter(const PfParams &p, int nqb, int passes, hipStream_t st, const char **kernel_name);
+// passes = number of 32*nqb-query passes (grid.y); nqb = 1 or 2; frag_waits: the per-fragment wait schedule (mirror
+// with plain loads only, see pf_waits_for)
+hipError_t launch_prefilter(const PfParams &p, int nqb, int passes, int frag_waits, hipStream_t st,
+                            const char **kernel_name);
 hipError_t launch_finalize(const FinParams &p, hipStream_t st);
 hipError_t launch_merge_partials(const MergeParams &p, int nq, hipStream_t st);
 hipError_t launch_merge_results(const XMergeParams &p, hipStream_t st);

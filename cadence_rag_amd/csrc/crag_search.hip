@@ -1735,8 +1735,16 @@ __device__ __forceinline__ int pf_next_pub(int after, int n_tiles, int read_lag)
     return (np < n_tiles) ? np : (1 << 30);
 }
 
-template <int NQB, int SETS, bool MIRROR, bool NT>
+// FRAG: the wait schedule of the mirror's loads (mirror only).  false = the whole tile is waited for in front of its
+// MFMAs and the next tile's loads leave as one burst (the HBM-bound sizes want bursts: see the tile loop).  true =
+// every k-step waits for its own fragment only and re-issues that register at once, so that seven or more loads stay
+// outstanding per wave all the time: for a mirror served from the Infinity Cache, where bytes in flight and not the
+// order of access count (pf_waits_for in crag_search_plan.h chooses).  Same arithmetic, same results.
+// (A template parameter of the one kernel and not a wrapper around a shared body: the wrapper changed the code
+// generated for the existing instantiations.)
+template <int NQB, int SETS, bool MIRROR, bool NT, bool FRAG>
 __global__ __launch_bounds__(SCAN_THREADS) void prefilter_kernel(PfParams p) {
+    static_assert(!FRAG || (MIRROR && !NT), "the per-fragment wait schedule exists for the cached mirror only");
     constexpr int RPO = 2 * NQB;
     // Cache policy of the corpus loads: NT = streaming ("slc" / nt: the lines are not kept) for a mirror far larger
     // than the 256 MB Infinity Cache -- 1M rows x 64: 4-9 % faster (348 -> 335 us on one box, 340 -> 310 on another).
@@ -1789,7 +1797,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void prefilter_kernel(PfParams p) {
         return valid ? (uint32_t)t * TILE_BYTES + lane_off : 0x80000000u;
     };
     u32x4 b[NB];
-    {
+    if constexpr (!FRAG) {
         const uint32_t v0 = voff(0);
 #pragma unroll
         for (int s = 0; s < NB; ++s) b[s] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, v0 + (MIRROR ? (uint32_t)s * 1024u : b_soff<PS>(s)), 0, AUX);
@@ -1805,6 +1813,17 @@ __global__ __launch_bounds__(SCAN_THREADS) void prefilter_kernel(PfParams p) {
         o.okmask = 0u;
     }
     {
+        // the RPO owned queries are consecutive and qg0 is a multiple of RPO: one aligned vector load (qinv is
+        // nq_pad long; padded queries hold 0)
+        typedef float qv_t __attribute__((ext_vector_type(RPO)));
+        qv_t qi;
+        // FRAG: nothing drains the scoreboard in front of the loop and returns are in order, so the loads leave in
+        // the order of their use: the norms (o.okmask below waits for this one load), the query fragments (L2 hits),
+        // the first tile's B fragments LAST -- the state every later tile starts from, which is what the compiler's
+        // counts in the loop assume: the first MFMA waits with seven B loads outstanding.  [B, A, A per k-step
+        // compiles to the same vmcnt(7) in front of the first MFMA, and that then stands for 17 of the prologue's
+        // 25 loads.]
+        if constexpr (FRAG) qi = *reinterpret_cast<const qv_t *>(p.qinv + o.qg0);
 #pragma unroll
         for (int qb = 0; qb < NQB; ++qb) {
             const f16x8 *af = reinterpret_cast<const f16x8 *>(p.a16) +
@@ -1812,10 +1831,15 @@ __global__ __launch_bounds__(SCAN_THREADS) void prefilter_kernel(PfParams p) {
 #pragma unroll
             for (int t8 = 0; t8 < 8; ++t8) a[qb][t8] = af[t8 * 64];
         }
-        // the RPO owned queries are consecutive and qg0 is a multiple of RPO: one aligned vector load (qinv is
-        // nq_pad long; padded queries hold 0)
-        typedef float qv_t __attribute__((ext_vector_type(RPO)));
-        const qv_t qi = *reinterpret_cast<const qv_t *>(p.qinv + o.qg0);
+        if constexpr (FRAG) {
+            __builtin_amdgcn_sched_barrier(0);
+            const uint32_t v0 = voff(0);
+#pragma unroll
+            for (int s = 0; s < NB; ++s) b[s] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, v0 + (uint32_t)s * 1024u, 0, AUX);
+            __builtin_amdgcn_sched_barrier(0);
+        } else {
+            qi = *reinterpret_cast<const qv_t *>(p.qinv + o.qg0);
+        }
 #pragma unroll
         for (int e = 0; e < RPO; ++e)
             if (o.qg0 + e < p.nq && qi[e] > 0.f) o.okmask |= 1u << e;
@@ -1843,8 +1867,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void prefilter_kernel(PfParams p) {
     }
     float inv_cur = 1.f;  // (mirror: rows that may never match are NaN in the mirror itself)
     if (!MIRROR && c.n_tiles > 0) inv_cur = p.inv_norm[(c.t_begin + tile_of(c, 0)) * 32 + j];
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): empty scoreboard at the loop head (see scan_kernel)
-    __syncthreads();
+    if constexpr (!FRAG) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): empty scoreboard at the loop head (see scan_kernel)
+    __syncthreads();   // (publishes the LDS initialisation; plain loads stay in flight across it)
 
     const int k_base = p.k / SETS, k_rem = p.k % SETS;
     const f32x16 zero16 = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1935,6 +1959,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void prefilter_kernel(PfParams p) {
     int next_read = rd_base + PF_READ_LAG;
     const int dq0 = c.g % (32 * NQB);   // (G >= 32 * NQB on a whole MI355X: one delegated query per workgroup)
     int buf = 0;
+    uint32_t tq_end[RPO];   // FRAG: the last bound read, issued behind the last tile's barrier
     for (int ti = 0; ti < c.n_tiles; ++ti) {
         const uint32_t vnext = voff(ti + 1);
         const int64_t tile = c.t_begin + tile_of(c, ti);
@@ -1954,7 +1979,10 @@ __global__ __launch_bounds__(SCAN_THREADS) void prefilter_kernel(PfParams p) {
         // The whole tile before the first MFMA: the 16 loads of the next tile then leave back to back, 16 KiB
         // contiguous per wave.  Waiting fragment by fragment re-issues them in dribs and drabs between 2047 other
         // waves' (measured on one box, 1M rows x 64: 643 us with this wait, 657 without).
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+        // FRAG (a mirror the Infinity Cache serves): no wait here.  Each k-step below waits for its own fragment only
+        // (the compiler counts: seven later loads of the tile outstanding, plus whatever was issued above) and its
+        // register is loaded again at once, so the bytes in flight never fall to zero.
+        if constexpr (!FRAG) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
 
         f32x16 acc[NQB];
         static_for<0, 8>([&](auto T) {
@@ -1999,6 +2027,9 @@ __global__ __launch_bounds__(SCAN_THREADS) void prefilter_kernel(PfParams p) {
         // only be lower than the final one in a wave that is not the last to append; the last one sees them all.
         if (lane == 0) L.want_flush[buf][w] = L.n_stage > (uint32_t)PF_FLUSH_ABOVE ? 1u : 0u;
         __syncthreads();
+        if constexpr (FRAG) {   // the bounds the stashed tiles are judged with: on their way while the last tile ends
+            if (ti == c.n_tiles - 1) load_taus(tq_end);
+        }
         {
             const u32x4 f0 = *reinterpret_cast<const u32x4 *>(&L.want_flush[buf][0]);
             const u32x4 f1 = *reinterpret_cast<const u32x4 *>(&L.want_flush[buf][4]);
@@ -2140,9 +2171,14 @@ __global__ __launch_bounds__(SCAN_THREADS) void prefilter_kernel(PfParams p) {
     }
     if (c.n_tiles > 0) {  // the stashed tiles, against the last bounds published
         {
-            uint32_t tq[RPO];
-            load_taus(tq);
-            take_taus(tq);
+            // (FRAG: read one tile's epilogue earlier.  A stale value is a lower one and only prunes less.)
+            if constexpr (FRAG) {
+                take_taus(tq_end);
+            } else {
+                uint32_t tq[RPO];
+                load_taus(tq);
+                take_taus(tq);
+            }
             if (any_without_bound()) derive_own();
         }
         // One barrier: sift first if the staging buffer is nearly full (decided as in the loop: each wave posts what it
@@ -2670,20 +2706,27 @@ hipError_t launch_prep_queries(const PrepParams &p, int nq_pad, hipStream_t st) 
     return hipGetLastError();
 }
 
-hipError_t launch_prefilter(const PfParams &p, int nqb, int passes, hipStream_t st, const char **kernel_name) {
+hipError_t launch_prefilter(const PfParams &p, int nqb, int passes, int frag_waits, hipStream_t st,
+                            const char **kernel_name) {
     const dim3 grid(p.G, passes), block(SCAN_THREADS);
     const char *name = "";
-#define CRAG_LAUNCH(...)                                             \
-    do {                                                              \
-        name = "crag::" #__VA_ARGS__;                                 \
-        hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, st, p);     \
-    } while (0)
+#define CRAG_LAUNCH(...) hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, st, p)
     const bool mirror = p.corpus16 != nullptr;
-#define CRAG_PICK(NQB_, SETS_)                                                      \
-    do {                                                                             \
-        if (mirror && p.nt) CRAG_LAUNCH(prefilter_kernel<NQB_, SETS_, true, true>);   \
-        else if (mirror) CRAG_LAUNCH(prefilter_kernel<NQB_, SETS_, true, false>);     \
-        else CRAG_LAUNCH(prefilter_kernel<NQB_, SETS_, false, false>);                \
+    // The name reported is the four-argument one for either wait schedule (MIRROR, NT last: callers and tests read
+    // that suffix); the schedule itself is reported beside it (crag_index_scan_waits).
+#define CRAG_PICK(NQB_, SETS_)                                                                     \
+    do {                                                                                            \
+        if (mirror && p.nt) {                                                                       \
+            name = "crag::prefilter_kernel<" #NQB_ ", " #SETS_ ", true, true>";                      \
+            CRAG_LAUNCH(prefilter_kernel<NQB_, SETS_, true, true, false>);                           \
+        } else if (mirror) {                                                                        \
+            name = "crag::prefilter_kernel<" #NQB_ ", " #SETS_ ", true, false>";                     \
+            if (frag_waits) CRAG_LAUNCH(prefilter_kernel<NQB_, SETS_, true, false, true>);           \
+            else CRAG_LAUNCH(prefilter_kernel<NQB_, SETS_, true, false, false>);                     \
+        } else {                                                                                    \
+            name = "crag::prefilter_kernel<" #NQB_ ", " #SETS_ ", false, false>";                    \
+            CRAG_LAUNCH(prefilter_kernel<NQB_, SETS_, false, false, false>);                         \
+        }                                                                                           \
     } while (0)
     if (nqb == 2) {
         if (p.sets == 1) CRAG_PICK(2, 1);

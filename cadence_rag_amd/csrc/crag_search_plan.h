@@ -16,6 +16,7 @@ struct SearchSwitches {
     int pf_derive_lag = 2, pf_read_lag = 4;   // CRAG_PF_LAGS="d,r" (developer tuning; r <= 4 = the stashed tiles)
     int pf_nt = -1;           // CRAG_PF_NT=0/1 forces the cache policy of the prefilter scan
     int64_t nt_above_bytes = 1536ll << 20;    // mirror bytes above which its loads stream (measured: no gain below ~1 GB)
+    int pf_waits = -1;        // CRAG_PF_WAITS=tile|fragment forces the wait schedule of the mirror scan (PfWaits)
 };
 
 struct SearchPlan {   // all int32: crag_search_plan_ hands it to ctypes as it is
@@ -71,4 +72,13 @@ inline SearchPlan plan_search(int64_t size, int n_cu, int nq, int k, bool has_mi
     const int64_t rows_per_g = (size + pl.G - 1) / pl.G + 64;
     pl.window_too_large = rows_per_g * (int64_t)(crag::DIM * 4) >= (int64_t)0x7ff00000 ? 1 : 0;
     return pl;
+}
+
+// Wait schedule of the mirror scan's corpus loads (crag::PfWaits; see prefilter_body).  Kept out of SearchPlan, whose
+// layout host tests pin: search_device asks with the plan's nt.  The per-fragment schedule exists for the mirror with
+// plain loads only; the switch (-1: by size) cannot force it onto another kernel.
+inline int pf_waits_for(int64_t mirror_bytes, bool has_mirror, int nt, int pf_waits_switch) {
+    if (!has_mirror || nt) return crag::PF_WAITS_TILE;
+    if (pf_waits_switch >= 0) return pf_waits_switch ? crag::PF_WAITS_FRAGMENT : crag::PF_WAITS_TILE;
+    return mirror_bytes <= crag::PF_FRAG_WAITS_MAX_BYTES ? crag::PF_WAITS_FRAGMENT : crag::PF_WAITS_TILE;
 }

@@ -497,6 +497,11 @@ class DenseIndex:
         name = self._lib.crag_index_last_scan_kernel(self._h)
         return name.decode() if name else ""
 
+    def scan_waits(self) -> str:
+        """Wait schedule of the most recent scan's corpus loads: "fragment" or "tile" (see crag_index_scan_waits)."""
+        name = self._lib.crag_index_scan_waits(self._h)
+        return name.decode() if name else ""
+
     def scan_geometry(self, nq: int) -> dict:
         wg, th, qb = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
         ab = ctypes.c_int64(0)

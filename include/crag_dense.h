@@ -55,7 +55,9 @@ int crag_device_count(void);
  * then streams the fp32 rows: twice the bytes per search, two thirds of the footprint); CRAG_NO_PREFILTER=1 keeps
  * every search on the exact fp32 MFMA scan.  Results are bit-identical in all three modes.  (Developer switches,
  * same place: CRAG_PF_NT=0/1 and CRAG_PF_NT_ABOVE_MB=<n> override when the mirror scan uses the streaming cache
- * policy -- by default for mirrors above 1.5 GB.) */
+ * policy -- by default for mirrors above 1.5 GB; CRAG_PF_WAITS=tile|fragment forces the wait schedule of the
+ * mirror scan's loads -- by default per-fragment waits for a mirror the Infinity Cache holds, see
+ * crag_index_scan_waits.) */
 int crag_index_create(int device, int dim, int64_t capacity, crag_index **out);
 int crag_index_destroy(crag_index *ix);
 
@@ -516,6 +518,11 @@ int crag_index_phase_trace(crag_index *ix, uint64_t *out128);
 /* Name of the scan kernel the most recent search on this index launched ("crag::scan_pipe_kernel", ...),
  * as rocprofv3 prints it; "" before the first search.  For bench.py's roofline object. */
 const char *crag_index_last_scan_kernel(const crag_index *ix);
+
+/* Wait schedule of the corpus loads of that scan: "fragment" (the fp16-mirror prefilter scan of a cache-sized
+ * mirror: every k-step waits for its own fragment) or "tile"; "" before the first search.  The kernel name above
+ * is the same for both.  Measurement and tests only. */
+const char *crag_index_scan_waits(const crag_index *ix);
 
 /* Bytes of one corpus row the prefilter scan streams: dim*2 when the index keeps the fp16 mirror of the unit rows
  * (default; + dim*2 bytes of HBM per row beside the dim*4 fp32 row, which stays the source of truth: candidates
