@@ -207,11 +207,29 @@ __global__ __launch_bounds__(256) void swiglu_kernel(const u16 *gu, u16 *out, in
                 const int c = c0 + q * 256;
                 if (c < chunks) {
                     Pack8 o;
+                    float lowest = 0.f;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
                         const float x = bf2f(g[q].v[e]);
+                        lowest = fminf(lowest, x);
                         const float act = bf2f(f2bf(x / (1.f + __expf(-x))));  // silu in fp32, rounded to bf16 like the model
                         o.v[e] = f2bf(act * bf2f(u[q].v[e]));
+                    }
+                    // Gates of -89 and below (the bf16 values past -88.5): exp(-x) is +inf in fp32 and the quotient -0,
+                    // while silu(x) is still a normal number down to -92 (-2e-37 at -89).  There 1 + e^-x is e^-x, so
+                    // silu = x e^x, with e^x taken 2^64 too large so that it is no denormal (-inf: -inf * 0 = NaN, as the
+                    // quotient).  One test per chunk, and the chunk read again inside it: nothing of this stays in
+                    // registers on the path of the chunks that hold no such gate.
+                    if (lowest <= -89.f) {
+                        const Pack8 g2 = gp[c], u2 = up[c];
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) {
+                            const float x = bf2f(g2.v[e]);
+                            if (x <= -89.f) {
+                                const float act = bf2f(f2bf(x * __expf(x + 44.3614196f) * 0x1p-64f));  // 64 ln 2
+                                o.v[e] = f2bf(act * bf2f(u2.v[e]));
+                            }
+                        }
                     }
                     op[c] = o;
                 }

@@ -22,7 +22,8 @@ extern "C" {
 
 #define CRAG_HEAD_DIM 128 /* Qwen3 head_dim; the attention / rope kernels are specialised for it */
 
-/* x[t, :] = table[ids[t], :]            (embed_tokens) */
+/* x[t, :] = table[ids[t], :]            (embed_tokens).  hidden % 8 == 0.  An id outside the table is clamped, not
+ * refused: ids[t] < 0 reads row 0, ids[t] >= vocab reads row vocab - 1. */
 int crag_enc_embed_gather(const int32_t *ids, const uint16_t *table, uint16_t *out, int64_t n_tokens,
                           int hidden, int64_t vocab, void *stream);
 
@@ -57,7 +58,10 @@ int crag_enc_attention(const uint16_t *qkv, const uint16_t *vt, uint16_t *out, c
                        const int32_t *cu_pad, const int32_t *blk_seq, const int32_t *blk_q0,
                        int n_blocks, int64_t t_pad, int hq, int hkv, float scale, void *stream);
 
-/* out[t, i] = silu(gu[t, i]) * gu[t, inter + i]   (gate | up fused projection) */
+/* out[t, i] = silu(gu[t, i]) * gu[t, inter + i]   (gate | up fused projection): silu = g / (1 + exp(-g)) in fp32,
+ * rounded to bf16, the product rounded to bf16.  Where exp(-g) overflows fp32 (bf16 gates <= -89) silu is taken as g * exp(g), so
+ * it stays the small negative number it is (-2e-37 at -89) down to the denormals instead of becoming -0.  The fused
+ * epilogues further down keep the quotient alone: they give crag_enc_swiglu's bits for gates above -89. */
 int crag_enc_swiglu(const uint16_t *gate_up, uint16_t *out, int64_t rows, int inter, void *stream);
 
 /* Pooling + post-processing of the gateway: per sequence take the last token (mode 0) or the

@@ -3,7 +3,8 @@ the live rows, the fp32 formula, and one-key probes in the style of attention_pr
 zero except key j, which is the rotated query times 16, so that every other softmax weight underflows to exactly 0 and
 the output must be V[j] bit for bit.
 
-The cache is a one-layer KvCache and is filled and read through its accessors only (append_prefill, keys, values)."""
+The cache is a one-layer KvCache and is filled and read through its accessors only (append_prefill, keys, values).
+(rotated() takes crag_enc_qk_norm_rope as the reference; test_row_probes_gpu.py pins the appended rows without it.)"""
 from __future__ import annotations
 
 import math

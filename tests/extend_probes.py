@@ -4,7 +4,8 @@ the new rows of a sequence hold keys that are all zero except key j, which is 16
 that every other softmax weight underflows to exactly 0 and out[r] must be V[j] bit for bit.
 
 The cache is a one-layer KvCache, filled and read through its accessors (append_prefill, keys, values).  max_len is no
-multiple of the tile, so a read past a slot's end would land in the NaN rows of the next kv head or slot."""
+multiple of the tile, so a read past a slot's end would land in the NaN rows of the next kv head or slot.
+(rotated() takes crag_enc_qk_norm_rope as the reference; test_row_probes_gpu.py pins the appended rows without it.)"""
 from __future__ import annotations
 
 from dataclasses import dataclass
