@@ -107,7 +107,9 @@ int profile_begin(crag_index *ix, hipStream_t st, EvSet **out) {
 
 // K0: 1/||q||, the queries in A-fragment order, reset of the prefilter state
 crag::PrepParams prep_params(const crag_index *ix, const Workspace *ws, const SearchPlan &pl, const SearchArgs &a) {
-    return crag::PrepParams{a.queries, a.nq, ix->dim, ws->at<float>(Workspace::QINV), ws->at<float>(Workspace::A32),
+    // (the fp32 fragments are the fp32 scan's operand; the prefilter path's selection blocks read the raw queries)
+    return crag::PrepParams{a.queries, a.nq, ix->dim, ws->at<float>(Workspace::QINV),
+                            pl.prefilter ? nullptr : ws->at<float>(Workspace::A32),
                             pl.prefilter ? ws->at<_Float16>(Workspace::A16) : nullptr};
 }
 
@@ -191,7 +193,6 @@ crag::FinParams fin_params(const crag_index *ix, const Workspace *ws, const Sear
     crag::FinParams fin;
     fin.corpus = ix->corpus;
     fin.inv_norm = ix->inv_norm;
-    fin.a32 = ws->at<const float>(Workspace::A32);
     fin.qinv = ws->at<const float>(Workspace::QINV);
     fin.cand = ws->at<const uint2>(Workspace::PF_CAND);
     fin.count = ws->at<uint32_t>(Workspace::PF_COUNT);

@@ -66,9 +66,72 @@ __device__ __forceinline__ f32x4 load_query_quad(const float *queries, int dim, 
     return v;
 }
 
+// s + (the s of lane ^ X), the exchange on the VALU: the two halves of the double travel as two 32-bit registers.
+// [__shfl_xor of a double is two ds_bpermute, an LDS round trip per stage of a chain in which every stage waits for the
+// one before.]  X = 32 / 16: v_permlane32_swap / v_permlane16_swap of a register with itself leave {own, partner} in
+// the lanes whose bit X is clear and {partner, own} in the others; the sum of the two is own + partner in either (an fp
+// add is commutative bit for bit; only which NaN payload survives depends on the order, and a NaN total is discarded).
+// X < 16: DPP inside the 16-lane row -- row_ror:8, row_half_mirror then quad_perm [3,2,1,0] (^7 ^3 = ^4), quad_perm
+// [2,3,0,1], quad_perm [1,0,3,2].  All 64 lanes must be active.
+template <int X>
+__device__ __forceinline__ double lane_xor_add_f64(double s) {
+    const uint64_t u = (uint64_t)__double_as_longlong(s);
+    const uint32_t lo = (uint32_t)u, hi = (uint32_t)(u >> 32);
+    if constexpr (X == 32 || X == 16) {
+        uint32_t l0, l1, h0, h1;
+        if constexpr (X == 32) {
+            const auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+            const auto h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+            l0 = l[0], l1 = l[1], h0 = h[0], h1 = h[1];
+        } else {
+            const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+            const auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+            l0 = l[0], l1 = l[1], h0 = h[0], h1 = h[1];
+        }
+        return __longlong_as_double((long long)(((uint64_t)h0 << 32) | l0)) +
+               __longlong_as_double((long long)(((uint64_t)h1 << 32) | l1));
+    } else {
+        static_assert(X == 8 || X == 4 || X == 2 || X == 1, "lane_xor_add_f64: no pattern");
+        uint32_t pl, ph;
+        if constexpr (X == 4) {
+            pl = (uint32_t)__builtin_amdgcn_mov_dpp(__builtin_amdgcn_mov_dpp((int)lo, 0x141, 0xF, 0xF, true), 0x1B, 0xF, 0xF, true);
+            ph = (uint32_t)__builtin_amdgcn_mov_dpp(__builtin_amdgcn_mov_dpp((int)hi, 0x141, 0xF, 0xF, true), 0x1B, 0xF, 0xF, true);
+        } else {
+            constexpr int ctrl = X == 8 ? 0x128 : (X == 2 ? 0x4E : 0xB1);
+            pl = (uint32_t)__builtin_amdgcn_mov_dpp((int)lo, ctrl, 0xF, 0xF, true);
+            ph = (uint32_t)__builtin_amdgcn_mov_dpp((int)hi, ctrl, 0xF, 0xF, true);
+        }
+        return s + __longlong_as_double((long long)(((uint64_t)ph << 32) | pl));
+    }
+}
+
+// The sum of 8 consecutive lanes' values in lane order, d = p0; d += p1; ... d += p7 (the scan kernels' split-K
+// reduction order), valid in the FIRST lane of each aligned group of 8: DPP row shifts (row_shl:n: lane i reads lane
+// i + n of its 16-lane row, which holds two groups) in place of eight ds_bpermute shuffles.  The other lanes of a group
+// end with a sum that runs into the next group or into zeros.  All 64 lanes must be active.
+__device__ __forceinline__ float group8_sum_in_order(float part) {
+    float d = part;
+#define CRAG_SHL_(N_) d += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(part), 0x100 + (N_), 0xF, 0xF, true))
+    CRAG_SHL_(1);
+    CRAG_SHL_(2);
+    CRAG_SHL_(3);
+    CRAG_SHL_(4);
+    CRAG_SHL_(5);
+    CRAG_SHL_(6);
+    CRAG_SHL_(7);
+#undef CRAG_SHL_
+    return d;
+}
+
 __device__ __forceinline__ float canonical_qinv(const f32x4 v, bool real_query, double *sh) {
     double ss = ((double)v[0] * v[0] + (double)v[1] * v[1]) + ((double)v[2] * v[2] + (double)v[3] * v[3]);
-    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+    // butterfly in the order xor 32, 16, 8, 4, 2, 1 (the pairing decides the rounding: it is part of the result)
+    ss = lane_xor_add_f64<32>(ss);
+    ss = lane_xor_add_f64<16>(ss);
+    ss = lane_xor_add_f64<8>(ss);
+    ss = lane_xor_add_f64<4>(ss);
+    ss = lane_xor_add_f64<2>(ss);
+    ss = lane_xor_add_f64<1>(ss);
     const int wv = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0 && wv < 4) sh[wv] = ss;
     __syncthreads();

@@ -70,7 +70,8 @@ struct PrepParams {
     const float *queries;     // [nq, dim] row-major fp32
     int nq, dim;
     float *qinv;              // [nq_pad]
-    float *a32;               // [nq_pad/32][8 waves][16][64] float4: raw queries in fp32 A-fragment order
+    float *a32;               // nullable (a prefilter search: nothing reads them); [nq_pad/32][8 waves][16][64] float4:
+                              // raw queries in fp32 A-fragment order, the fp32 scan kernels' A operand
     _Float16 *a16;            // nullable; [nq_pad/32][8 waves][8][64][8]: unit queries in fp16 A-fragment order
 };
 
@@ -100,8 +101,7 @@ struct PfParams {
 struct FinParams {
     const float *corpus;
     const float *inv_norm;
-    const float *a32;
-    const float *qinv;
+    const float *qinv;          // (the raw queries themselves: scan.queries / scan.dim)
     const uint2 *cand;
     uint32_t *count;            // [nq_pad]; zeroed per query after use
     uint32_t *gbound;           // [nq_pad][PF_BOUND_CELLS]; zeroed per query after use

@@ -1517,7 +1517,8 @@ __global__ __launch_bounds__(256) void prep_queries_kernel(PrepParams p) {
     const float qinv = canonical_qinv(v, q < p.nq, sh);
     if (t == 0) p.qinv[q] = qinv;
     const int qb = q >> 5, i = q & 31, w = t >> 5, d = (4 * t) & 127;
-    {   // fp32 fragments: float4 (s, h) of wave slice w, s = d/8, h = (d/4)&1
+    if (p.a32) {   // fp32 fragments (the fp32 scan kernels' A operand; a prefilter search has no reader for them: its
+                   // selection blocks take the raw query): float4 (s, h) of wave slice w, s = d/8, h = (d/4)&1
         const int sidx = d >> 3, h = (d >> 2) & 1;
         reinterpret_cast<f32x4 *>(p.a32)[((size_t)(qb * SCAN_WAVES + w) * 16 + sidx) * 64 + h * 32 + i] = v;
     }
@@ -2319,10 +2320,12 @@ __global__ __launch_bounds__(SCAN_THREADS) void finalize_fb_kernel(FinParams p) 
     const uint32_t total = p.count[q];
     const uint2 first = gcand[tid];
     const float qinv = p.qinv[q];
-    // thread t < 256 = (slice w, s, h) fetches its float4 of the raw query (prep_queries_kernel's layout)
-    f32x4 qfrag = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (tid < 256)
-        qfrag = reinterpret_cast<const f32x4 *>(p.a32)[((size_t)((q >> 5) * SCAN_WAVES + (tid >> 5)) * 16 + ((tid >> 1) & 15)) * 64 + (tid & 1) * 32 + (q & 31)];
+    // thread t < 256 = (slice w = t >> 5, s = (t >> 1) & 15, h = t & 1) fetches float4 number t of the RAW query, zero
+    // padded.  [It used to read the fp32 fragment prep_queries_kernel stored for it: that kernel's thread t, which holds
+    // dims 4t .. 4t+3, stores them at (w, sidx, h) = (t >> 5, ((4t) & 127) >> 3, ((4t) >> 2) & 1) = (t >> 5,
+    // (t >> 1) & 15, t & 1) -- the very float4 this thread asked for.  On a prefilter search nothing else read those
+    // 256 KiB, so prep no longer writes them.]
+    const f32x4 qfrag = load_query_quad(p.scan.queries, p.scan.dim, q, p.nq, tid);
     // Statistics (bench.py's byte accounting): a record per query that only this workgroup updates -- read here,
     // written back at the end with plain stores.  [They were three atomic adds on one shared record: 192 same-line
     // device-scope atomics per search, whose acknowledgements the kernel's end had to wait for.]  p.stats is the
@@ -2491,10 +2494,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void finalize_fb_kernel(FinParams p) 
                 const f32x4 *ctile = reinterpret_cast<const f32x4 *>(p.corpus + (size_t)(row >> 5) * TILE_FLOATS) + (size_t)sub * 32 * 32;
                 part = exact_slice_dot<PS>(&qs[sub][0][0], ctile, (int)(row & 31u));
             }
-            // the 8 slice sums in wave order 0..7 (the scan kernels' split-K reduction order)
-            float d = __shfl(part, (tid & 63 & ~7) | 0);
-#pragma unroll
-            for (int ww = 1; ww < 8; ++ww) d += __shfl(part, (tid & 63 & ~7) | ww);
+            // the 8 slice sums in wave order 0..7 (the scan kernels' split-K reduction order), in the group's lane 0
+            const float d = group8_sum_in_order(part);
             if (live && sub == 0) {
                 const float scale = inv_row * qinv;
                 float sc = d * scale;

@@ -7,7 +7,7 @@ import bench
 from cadence_rag_amd.dense_index import DenseIndex
 dev = torch.device("cuda", 0)
 names = ["loaded", "kth", "rescored", "own list+ticket", "gathered", "end"]
-for rows in (100_000, 1_000_000):
+for rows in [int(a) for a in sys.argv[1:]] or (100_000, 1_000_000):   # (row counts on the command line, or both)
     big = bench.synth(rows, 1234, dev); idx = DenseIndex(bench.DIM, capacity=rows, device=0); idx.add(big)
     q = bench.synth(64, 4321, dev)
     for k in (10, 50, 100):
