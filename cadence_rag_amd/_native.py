@@ -151,6 +151,9 @@ SIGNATURES = {
     "crag_enc_sample": (_c.c_int, [_P, _c.c_int64, _P, _P, _P, _P, _P, _P, _c.c_uint64, _c.c_uint32, _P, _P, _P, _c.c_int, _P]),
     "crag_enc_grammar_advance": (_c.c_int, [_P, _P, _P, _c.c_int64, _P, _P, _c.c_int, _c.c_int, _P, _P, _c.c_int, _P]),
     "crag_enc_logprobs": (_c.c_int, [_P, _c.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _P]),
+    "crag_enc_adjust_workspace_bytes": (_c.c_int64, [_c.c_int, _c.c_int64]),
+    "crag_enc_adjust_logits": (_c.c_int, [_P, _P, _c.c_int64, _P, _c.c_int64, _c.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                          _P, _P, _P, _P, _c.c_int64, _c.c_int, _P]),
 }
 
 

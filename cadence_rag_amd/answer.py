@@ -38,6 +38,14 @@ equals), ranks the candidate quoted into a repair turn the same way among those 
 notes.samples gains "scores" (one mean per candidate) and "ranked": True.  "logprob" with one sample, or on a backend
 without the capability, behaves as "first" and says notes.samples["ranked"] = False.
 
+Repetition control (cadence_rag_amd.penalties): a request's repetition_penalty / presence_penalty / frequency_penalty /
+no_repeat_ngram / logit_bias / min_new_tokens, over the ANSWER_* defaults, all neutral.  A native model with
+supports_penalties applies them on the GPU before every pick (crag_enc_adjust_logits), with the ids of the citation
+alphabet "[]-0123456789QA" exempt, so that citing [Q-12] a second time is never penalised or banned; an HTTP service is
+sent presence_penalty, frequency_penalty and logit_bias, and notes.penalties_ignored names the others that were set.
+notes.penalties echoes the parameters (with "applied": False for a native model without the capability) only when
+they are not neutral: a request that names none of this gets the response it always got.
+
 ANSWER_CONSTRAINED (native backend, a model with supports_grammar): the reply is decoded under the citation grammar of
 the evidence ids in the prompt (cadence_rag_amd.grammar.citation_grammar), which makes a failing answer unrepresentable
 whenever the model stops by itself.  The gate and the repair loop run unchanged on whatever comes back.
@@ -54,6 +62,7 @@ from .config import settings
 from .grammar import INSUFFICIENT as _INSUFFICIENT_BYTES
 from .grammar import TokenGrammar, citation_grammar
 from .logprobs import mean_logprob, summarise
+from .penalties import CITATION_ALPHABET, PenaltyParams, active as _active_penalties, exempt_ids
 from .sampling import SamplingParams
 
 INSUFFICIENT = _INSUFFICIENT_BYTES.decode("ascii")   # "INSUFFICIENT_EVIDENCE": one definition, the grammar's
@@ -88,7 +97,9 @@ class ChatModel(Protocol):
     max_new_tokens, grammar=None, sampling=None, streams=None) -> List[str]`: n replies to one chat, reply i drawn on
     noise stream streams[i]; the same exceptions as generate_text.
     Optional: a model whose class sets `supports_logprobs = True` also takes `logprobs=int` in both and then leaves
-    `last_logprobs`: per reply a list of cadence_rag_amd.logprobs.TokenLogprob, one per produced token."""
+    `last_logprobs`: per reply a list of cadence_rag_amd.logprobs.TokenLogprob, one per produced token.
+    Optional: a model whose class sets `supports_penalties = True` also takes `penalties=PenaltyParams,
+    penalty_exempt=ids or None` in both: repetition control, the exempt ids untouched by it."""
 
     model_id: str
 
@@ -183,8 +194,8 @@ def _post_json(url: str, headers: Dict[str, str], body: Dict[str, Any], timeout_
     return resp.status_code, resp.text
 
 
-def _chat_http(messages: List[Dict[str, str]], max_new_tokens: int, sampling: Optional[SamplingParams] = None
-               ) -> Tuple[str, str]:
+def _chat_http(messages: List[Dict[str, str]], max_new_tokens: int, sampling: Optional[SamplingParams] = None,
+               penalties: Optional[PenaltyParams] = None) -> Tuple[str, str]:
     import json
 
     url = settings.llm_base_url.rstrip("/") + "/chat/completions"
@@ -192,6 +203,11 @@ def _chat_http(messages: List[Dict[str, str]], max_new_tokens: int, sampling: Op
     body = {"model": settings.llm_model, "messages": messages, "temperature": 0, "max_tokens": int(max_new_tokens)}
     if sampling is not None:   # the three knobs every OpenAI-compatible service knows
         body.update(temperature=float(sampling.temperature), top_p=float(sampling.top_p), seed=int(sampling.seed))
+    if penalties is not None:  # ... and the three of these; the others are no part of the protocol (penalties_ignored)
+        body.update(presence_penalty=float(penalties.presence_penalty),
+                    frequency_penalty=float(penalties.frequency_penalty))
+        if penalties.logit_bias:   # the protocol's range is -100..100: -inf goes as its lower end
+            body["logit_bias"] = {str(t): max(float(b), -100.0) for t, b in penalties.logit_bias.items()}
     status, text = _post_json(url, headers, body, settings.llm_timeout_s)
     if status != 200:
         raise AnswerClientError(f"LLM service returned {status}: {text.strip()[:400]}")
@@ -207,7 +223,7 @@ def _chat_http(messages: List[Dict[str, str]], max_new_tokens: int, sampling: Op
 
 def _chat_native(messages: List[Dict[str, str]], max_new_tokens: int, grammar: Optional[TokenGrammar] = None,
                  sampling: Optional[SamplingParams] = None, stream: int = 0, speculate: int = 0,
-                 logprobs: Optional[int] = None) -> Tuple[str, str]:
+                 logprobs: Optional[int] = None, penalties: Optional[PenaltyParams] = None) -> Tuple[str, str]:
     """ValueError (the prompt does not fit) passes through to the caller, which drops evidence."""
     llm = _llm
     if llm is None:
@@ -221,6 +237,7 @@ def _chat_native(messages: List[Dict[str, str]], max_new_tokens: int, grammar: O
                 extra.update(speculate=int(speculate))
             if logprobs is not None:
                 extra.update(logprobs=int(logprobs))
+            extra.update(_penalty_kwargs(llm, penalties))
             text = llm.generate_text(messages, max_new_tokens, **extra)
     except (AnswerClientError, ValueError):
         raise
@@ -233,8 +250,8 @@ def _chat_native(messages: List[Dict[str, str]], max_new_tokens: int, grammar: O
 
 def chat_samples(messages: List[Dict[str, str]], n: int, max_new_tokens: Optional[int] = None,
                  grammar: Optional[TokenGrammar] = None, sampling: Optional[SamplingParams] = None,
-                 streams: Optional[Sequence[int]] = None, speculate: int = 0, logprobs: Optional[int] = None
-                 ) -> Tuple[List[str], str]:
+                 streams: Optional[Sequence[int]] = None, speculate: int = 0, logprobs: Optional[int] = None,
+                 penalties: Optional[PenaltyParams] = None) -> Tuple[List[str], str]:
     """(n replies, model id) from the registered native model's generate_text_samples (native_samples()).  ValueError
     (the prompt does not fit) passes through, as from chat().  speculate > 0: a model with supports_speculation only; logprobs: one with supports_logprobs only."""
     llm = _llm
@@ -246,7 +263,8 @@ def chat_samples(messages: List[Dict[str, str]], n: int, max_new_tokens: Optiona
                                               grammar=grammar, sampling=sampling,
                                               streams=None if streams is None else [int(x) for x in streams],
                                               **({"speculate": int(speculate)} if speculate else {}),
-                                              **({} if logprobs is None else {"logprobs": int(logprobs)}))
+                                              **({} if logprobs is None else {"logprobs": int(logprobs)}),
+                                              **_penalty_kwargs(llm, penalties))
     except (AnswerClientError, ValueError):
         raise
     except Exception as exc:  # noqa: BLE001 - callers rely on a single error type
@@ -258,19 +276,21 @@ def chat_samples(messages: List[Dict[str, str]], n: int, max_new_tokens: Optiona
 
 def chat(messages: List[Dict[str, str]], max_new_tokens: Optional[int] = None, grammar: Optional[TokenGrammar] = None,
          sampling: Optional[SamplingParams] = None, stream: int = 0, speculate: int = 0,
-         logprobs: Optional[int] = None) -> Tuple[str, str]:
+         logprobs: Optional[int] = None, penalties: Optional[PenaltyParams] = None) -> Tuple[str, str]:
     """(reply, model id) from the configured LLM.  grammar: native backend only (an HTTP service cannot take one).
     speculate > 0: native backend only, a model with supports_speculation (native_speculation()).
     sampling: None is greedy; a native model must have supports_sampling (native_sampling()), and draws on noise stream
     `stream`; an HTTP service gets temperature, top_p and seed.
     logprobs: native backend only, a model with supports_logprobs (native_logprobs()); its records are in the model's
-    last_logprobs."""
+    last_logprobs.
+    penalties: a native model must have supports_penalties (native_penalties()) and takes all of it, with the citation
+    alphabet exempt; an HTTP service gets presence_penalty, frequency_penalty and logit_bias."""
     if not llm_enabled():
         raise AnswerClientError("LLM_BASE_URL is not configured")
     budget = int(max_new_tokens or settings.llm_max_new_tokens)
     if _is_native(settings.llm_base_url):
-        return _chat_native(messages, budget, grammar, sampling, stream, speculate, logprobs)
-    return _chat_http(messages, budget, sampling)
+        return _chat_native(messages, budget, grammar, sampling, stream, speculate, logprobs, penalties)
+    return _chat_http(messages, budget, sampling, penalties)
 
 
 def constrained_decoding() -> bool:
@@ -297,6 +317,43 @@ def native_speculation() -> bool:
 def native_logprobs() -> bool:
     """The backend is native and the registered model takes logprobs=n."""
     return _is_native(settings.llm_base_url) and bool(getattr(_llm, "supports_logprobs", False))
+
+
+def native_penalties() -> bool:
+    """The backend is native and the registered model takes penalties=PenaltyParams."""
+    return _is_native(settings.llm_base_url) and bool(getattr(_llm, "supports_penalties", False))
+
+
+_PENALTY_FIELDS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "no_repeat_ngram", "logit_bias",
+                   "min_new_tokens")
+_HTTP_PENALTY_FIELDS = ("presence_penalty", "frequency_penalty", "logit_bias")
+
+
+def penalties_for(request: Any) -> Optional[PenaltyParams]:
+    """The request's repetition-control fields over the ANSWER_* defaults; None when the result is neutral -- decoding
+    is then exactly what it is without them.  AnswerRequestError: a value out of range."""
+    import json
+
+    merged = {}
+    for name in _PENALTY_FIELDS:
+        given = getattr(request, name, None)
+        merged[name] = getattr(settings, "answer_" + name) if given is None else given
+    try:
+        if isinstance(merged["logit_bias"], str):   # the setting: a JSON object as text
+            merged["logit_bias"] = json.loads(merged["logit_bias"]) if merged["logit_bias"].strip() else {}
+        return _active_penalties(PenaltyParams(**merged))
+    except (TypeError, ValueError) as exc:
+        raise AnswerRequestError(str(exc)) from exc
+
+
+def _penalty_kwargs(llm: Any, penalties: Optional[PenaltyParams]) -> Dict[str, Any]:
+    """What a native model with supports_penalties is passed: the parameters, and the ids of the citation alphabet as
+    exempt -- citing [Q-12] a second time is never penalised or banned -- when the model has a token table."""
+    if penalties is None:
+        return {}
+    table = getattr(llm, "token_table", None)
+    return {"penalties": penalties,
+            "penalty_exempt": exempt_ids(table(), CITATION_ALPHABET) if callable(table) else None}
 
 
 def logprobs_for(request: Any) -> bool:
@@ -380,6 +437,12 @@ class AnswerRequest(_retrieve.RetrieveRequest):
     speculate: Optional[int] = None
     logprobs: Optional[bool] = None
     sample_rank: Optional[str] = None
+    repetition_penalty: Optional[float] = None
+    presence_penalty: Optional[float] = None
+    frequency_penalty: Optional[float] = None
+    no_repeat_ngram: Optional[int] = None
+    logit_bias: Optional[Dict[Any, float]] = None
+    min_new_tokens: Optional[int] = None
 
 
 def _evidence_items(pack: Dict[str, Any]) -> List[Dict[str, Any]]:
@@ -420,6 +483,7 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
     speculate = speculate_for(request)
     want_logprobs = logprobs_for(request)
     rank_mode = sample_rank_for(request)
+    penalties = penalties_for(request)
     pack_request = _retrieve.RetrieveRequest(query=request.query, intent=request.intent, filters=request.filters,
                                              budget=request.budget, return_style="evidence_pack_json", debug=request.debug,
                                              facets=request.facets, facet_top=request.facet_top)
@@ -433,6 +497,17 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
         if _is_native(settings.llm_base_url) and not native_sampling():
             notes["sampling"]["applied"] = False   # the registered model cannot sample: it decodes greedily
             sampling = None
+    if penalties is not None:           # neutral by default: no such note
+        notes["penalties"] = penalties.echo()
+        if _is_native(settings.llm_base_url):
+            if not native_penalties():      # the registered model takes none: it decodes as without them
+                notes["penalties"]["applied"] = False
+                penalties = None
+        else:   # an HTTP service is sent the three knobs of its protocol; the others that are set are named here
+            ignored = [name for name in _PENALTY_FIELDS if name not in _HTTP_PENALTY_FIELDS
+                       and getattr(penalties, name) != getattr(PenaltyParams(), name)]
+            if ignored:
+                notes["penalties_ignored"] = ignored
     # several candidates come from one call of a native model that can fork a prefill; anything else draws one as ever
     multi = n_samples > 1 and sampling is not None and native_samples()
     if n_samples > 1 and not multi:
@@ -470,13 +545,15 @@ def answer_question(request: AnswerRequest, backend: Optional[_retrieve.Retrieve
                     texts, model = chat_samples(build_messages(query, items, turns), n_samples, grammar=grammar,
                                                 sampling=sampling,
                                                 streams=[attempt * n_samples + i for i in range(n_samples)],
-                                                speculate=speculate, logprobs=scoring)
+                                                speculate=speculate, logprobs=scoring, penalties=penalties)
                 else:
                     extra = {} if sampling is None else {"sampling": sampling, "stream": attempt}
                     if speculate:
                         extra["speculate"] = speculate
                     if scoring is not None:
                         extra["logprobs"] = scoring
+                    if penalties is not None:
+                        extra["penalties"] = penalties
                     text, model = chat(build_messages(query, items, turns), grammar=grammar, **extra)
                     texts = [text]
             except ValueError as exc:   # the prompt does not fit the model's context: the lowest-ranked item goes

@@ -90,6 +90,16 @@ class Settings:
     # how the answer is chosen among several valid candidates (a request's `sample_rank` overrides it): "first" -- the
     # lowest index -- or "logprob" -- the highest mean token log-probability, which needs samples > 1 and such a model
     answer_sample_rank: str = "first"
+    # repetition control of /answer (cadence_rag_amd.penalties); a request's own field of the same name overrides each.
+    # All neutral by default: nothing is launched and the response is what it was.  ANSWER_LOGIT_BIAS is a JSON object
+    # as text, token id -> value ('{"1234": -100}'; "" is none).  A native model with supports_penalties applies all of
+    # them on the GPU (crag_enc_adjust_logits); an HTTP service gets presence_penalty, frequency_penalty and logit_bias
+    answer_repetition_penalty: float = 1.0
+    answer_presence_penalty: float = 0.0
+    answer_frequency_penalty: float = 0.0
+    answer_no_repeat_ngram: int = 0
+    answer_logit_bias: str = ""
+    answer_min_new_tokens: int = 0
 
     def __post_init__(self) -> None:
         if self.rerank_device < 0:

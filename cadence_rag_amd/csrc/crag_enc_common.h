@@ -1,6 +1,6 @@
 // crag_enc_common.h — the small helpers shared by the encoder-lane translation units (crag_encoder.hip,
 // crag_attention.hip, crag_encoder_small.hip, crag_encoder_wide.hip, crag_rerank.hip, crag_decode.hip, crag_extend.hip,
-// crag_grammar.hip, crag_sample.hip, crag_logprobs.hip): vector types, error reporting, bf16 conversion, fragment load,
+// crag_grammar.hip, crag_sample.hip, crag_logprobs.hip, crag_penalty.hip): vector types, error reporting, bf16 conversion, fragment load,
 // block and half-wave reductions, the per-head RMSNorm + RoPE of one head vector, the append of a row to the KV cache, the
 // order-preserving key of a float, the (value, id) order of every greedy selection and its workgroup merge.  Internal linkage: nothing here is exported.
 #pragma once

@@ -29,6 +29,10 @@ kernels) with a full-vocabulary head -- the in-process LLM behind /answer (caden
   logprobs=n            generate / generate_samples score every produced token with crag_enc_logprobs on the logits it
                         was picked from (last_logprobs: token, logprob, rank, the mass a grammar left allowed, the n most
                         likely ids); score(prompts, continuations) gives the same records for text it is handed.
+  penalties=...         generate / generate_samples first run crag_enc_adjust_logits on every row a token is picked from
+                        (cadence_rag_amd.penalties: repetition, presence and frequency penalties, the n-gram ban, a bias
+                        list, min_new_tokens) over a token log the picker keeps on the device, and pick on the adjusted
+                        rows in every mode; logprobs keeps scoring the raw logits.  Off by default: nothing is launched.
 
 The cache layout ([layer][slot][kv head][max_len][128] bf16, keys and values apart) sits behind KvCache.keys / .values.
 At most MAX_SEQS = 8 sequences decode at a time.
@@ -44,6 +48,8 @@ import torch.nn.functional as F
 
 from ..grammar import KIND_STOP, TokenGrammar, TokenTable
 from ..logprobs import TokenLogprob
+from ..penalties import PenaltyParams, bias_list, exempt_words
+from ..penalties import active as active_penalties
 from ..sampling import SamplingParams
 from ..speculate import MAX_SPECULATE, propose_drafts
 from . import ops
@@ -164,9 +170,31 @@ class _Picker:
     streams per prompt, and under a grammar the tables and every prompt's automaton state on the device."""
 
     def __init__(self, gen: "Qwen3Generator", n: int, grammar: Optional[TokenGrammar], sampling, streams,
-                 logprobs: Optional[int] = None) -> None:
+                 logprobs: Optional[int] = None, penalties=None, prompts: Sequence[Sequence[int]] = (),
+                 max_new_tokens: int = 0, stop: Sequence[int] = (), exempt: Optional[Sequence[int]] = None) -> None:
         self.device = gen.device
         self.table = self.draws = None
+        # penalties: every pick first runs ops.adjust_logits on the rows' logits and picks on the adjusted rows; the
+        # picker then owns a token log on the device (the prompts, uploaded once, and every token it picks, appended
+        # from the device tensor it was picked into) and the host lengths of its rows.  None or neutral: none of this.
+        rules = [penalties] * n if penalties is None or isinstance(penalties, PenaltyParams) else list(penalties)
+        if len(rules) != n or any(p is not None and not isinstance(p, PenaltyParams) for p in rules):
+            raise ValueError("penalties takes one PenaltyParams, or one per prompt")
+        self.rules: Optional[List[PenaltyParams]] = None
+        if any(active_penalties(p) is not None for p in rules):
+            if n > gen.max_seqs:
+                raise ValueError(f"penalties take 1..{gen.max_seqs} prompts")
+            self.rules = [p if p is not None else PenaltyParams() for p in rules]
+            self.stop_ids = sorted({int(s) for s in stop})
+            self.prompt_len = [len(p) for p in prompts]
+            self.log_len = list(self.prompt_len)
+            log = np.zeros((n, max(self.prompt_len) + int(max_new_tokens)), dtype=np.int32)
+            for b, p in enumerate(prompts):
+                log[b, :len(p)] = np.asarray(p, dtype=np.int32)
+            self.log = torch.from_numpy(log).to(self.device)
+            self.adjusted, self.adjust_ws = gen._adjust_buffers()
+            self.exempt_bits = None if exempt is None else gen._exempt_bits(exempt)
+            self.bias_key, self.bias_dev = None, (None, None)
         # logprobs = n_top: every pick is scored by ops.logprobs on the logits it was picked from; `scores` then holds the
         # TokenLogprob of every row of the last pick, and the token loops file those of the tokens they emit in `records`
         self.n_top = None if logprobs is None else _check_logprobs(logprobs, gen.cfg.vocab_size)
@@ -196,12 +224,52 @@ class _Picker:
         return ops.sample(logits, [self.draws[b] for b in rows], step, [self.lanes[b] for b in rows], token,
                           allowed_bits=bits)
 
+    def _adjust(self, rows: List[int], logits: torch.Tensor, step: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The rows' logits under their penalties (into the picker's scratch) and the greedy tokens on them.  step: how
+        many ids every row has produced -- below min_new_tokens the stop ids are biased to -inf."""
+        n, vocab = logits.shape
+        lists = [bias_list(self.rules[b], step, self.stop_ids, vocab) for b in rows]
+        bias = {}
+        if any(lists):
+            key = tuple(tuple(x) for x in lists)
+            if key != self.bias_key:   # the lists change when a row passes min_new_tokens or the rows do: rarely
+                flat = [e for x in lists for e in x]
+                self.bias_key = key
+                self.bias_dev = (torch.tensor([t for t, _ in flat], dtype=torch.int32).to(self.device),
+                                 torch.tensor([v for _, v in flat], dtype=torch.float32).to(self.device))
+            bias = dict(bias_ids=self.bias_dev[0], bias_values=self.bias_dev[1],
+                        bias_offsets=np.concatenate([[0], np.cumsum([len(x) for x in lists])]).tolist())
+        out = self.adjusted[:n]
+        token = torch.empty(n, dtype=torch.int32, device=self.device)
+        ops.adjust_logits(logits.contiguous(), out, self.log, rows, [self.prompt_len[b] for b in rows],
+                          [self.log_len[b] for b in rows], [self.rules[b] for b in rows], token, self.adjust_ws,
+                          exempt_bits=self.exempt_bits, **bias)
+        return out, token
+
+    def _append(self, rows: List[int], token: torch.Tensor) -> None:
+        """The picked tokens go behind the rows' logs, device to device.  (A -1 or a stop id ends its sequence: whatever
+        is appended for it is never read.)"""
+        at = torch.tensor([rows, [self.log_len[b] for b in rows]], dtype=torch.int64).to(self.device)
+        self.log.index_put_((at[0], at[1]), token)
+        for b in rows:
+            self.log_len[b] += 1
+
     def __call__(self, rows: List[int], logits: torch.Tensor, greedy_tokens: torch.Tensor, step: int) -> List[int]:
+        raw = logits    # what logprobs scores: the model's own distribution, whatever picked the id
+        if self.rules is not None:   # lm_head's greedy token is not valid under penalties: the kernel's is
+            logits, greedy_tokens = self._adjust(rows, logits, step)
+        token = self._pick(rows, logits, raw, greedy_tokens, step)
+        if self.rules is not None:
+            self._append(rows, token)
+        return token.tolist()
+
+    def _pick(self, rows: List[int], logits: torch.Tensor, raw: torch.Tensor, greedy_tokens: torch.Tensor, step: int
+              ) -> torch.Tensor:
         if self.table is None:
             token = greedy_tokens if self.draws is None else self._draw(rows, logits, step)
             if self.n_top is not None:
-                self.scores = score_rows(logits, token, self.n_top)
-            return token.tolist()
+                self.scores = score_rows(raw, token, self.n_top)
+            return token
         idx = torch.tensor(rows, dtype=torch.int64).to(self.device)
         cur = self.state.index_select(0, idx)      # the states of `rows`: they move on behind the chosen tokens
         token = torch.empty(len(rows), dtype=torch.int32, device=self.device)
@@ -216,8 +284,8 @@ class _Picker:
             ops.grammar_advance(*self.tables[:5], cur, token)
         self.state.index_copy_(0, idx, cur)
         if self.n_top is not None:   # the bits grammar_argmax handed out: the mass the automaton left allowed
-            self.scores = score_rows(logits, token, self.n_top, bits)
-        return token.tolist()
+            self.scores = score_rows(raw, token, self.n_top, bits)
+        return token
 
     def file(self, b: int, k: int) -> None:
         """The token loop emitted row k of the last pick as a token of prompt b: its record is kept."""
@@ -260,6 +328,7 @@ class Qwen3Generator:
     supports_samples = True   # generate_text_samples: n replies from one prefill
     supports_speculation = True   # ... and speculate=k: up to k prompt-lookup drafts verified per forward
     supports_logprobs = True      # ... and logprobs=n: last_logprobs holds a TokenLogprob per produced token
+    supports_penalties = True     # ... and penalties=PenaltyParams, penalty_exempt=ids: repetition control
 
     def __init__(self, encoder: Qwen3Encoder, lm_head: torch.Tensor, tokenizer=None, *, max_context: Optional[int] = None,
                  max_seqs: int = MAX_SEQS, model_id: Optional[str] = None, prefix_cache: bool = False) -> None:
@@ -366,6 +435,25 @@ class Qwen3Generator:
         if self._token_table is None:
             self._token_table = TokenTable.from_tokenizer(self._tokenizer(), self.stop_ids(), self.cfg.vocab_size)
         return self._token_table
+
+    # -- repetition control: what a _Picker with penalties borrows --------------------------------------------------
+    def _adjust_buffers(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(the adjusted rows [MAX_ROWS, vocab] fp32, ops.adjust_logits' workspace): made on the first call with
+        penalties, kept for the later ones."""
+        bufs = self.__dict__.get("_adjust_bufs")
+        if bufs is None:
+            bufs = self._adjust_bufs = (torch.empty(MAX_ROWS, self.cfg.vocab_size, dtype=torch.float32, device=self.device),
+                                        ops.adjust_workspace(MAX_ROWS, self.cfg.vocab_size, self.device))
+        return bufs
+
+    def _exempt_bits(self, ids: Sequence[int]) -> torch.Tensor:
+        """The exempt ids as the kernel's bit mask on the device; the last list's mask is kept (/answer passes one)."""
+        key = np.unique(np.asarray(ids, dtype=np.int64)).tobytes()
+        held = self.__dict__.get("_exempt_held")
+        if held is None or held[0] != key:
+            words = exempt_words(np.frombuffer(key, dtype=np.int64), self.cfg.vocab_size)
+            held = self._exempt_held = (key, torch.from_numpy(words.view(np.int32)).to(self.device))
+        return held[1]
 
     def _tokenizer(self):
         if self.tokenizer is None:
@@ -686,7 +774,8 @@ class Qwen3Generator:
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_ids: Sequence[int] = (),
                  reuse_prefix: bool = False, grammar: Optional[TokenGrammar] = None,
                  sampling=None, streams: Optional[Sequence[int]] = None, speculate: int = 0,
-                 drafter=None, logprobs: Optional[int] = None) -> List[List[int]]:
+                 drafter=None, logprobs: Optional[int] = None, penalties=None,
+                 penalty_exempt: Optional[Sequence[int]] = None) -> List[List[int]]:
         """Greedy continuation of every prompt (token ids): at most max_new_tokens ids each, ending before the first
         stop id.  A prompt longer than max_context - max_new_tokens raises PromptTooLong (a ValueError): the caller
         shortens its prompt, nothing is truncated here.
@@ -712,7 +801,14 @@ class Qwen3Generator:
         picked from, the picked id still on the device -- in every picking mode and in both loops; under speculation a
         token is scored on the row that verified it, and a rejected draft leaves nothing.  last_logprobs[b] then holds one
         TokenLogprob (token, logprob, rank, allowed_logmass under a grammar, the n most likely (id, logprob)) per id
-        returned for prompt b; a stop token leaves none.  The ids returned do not depend on it."""
+        returned for prompt b; a stop token leaves none.  The ids returned do not depend on it.
+        penalties: a penalties.PenaltyParams for every prompt, or one per prompt (1..max_seqs prompts).  Every pick then
+        first runs ops.adjust_logits -- the rule is penalties.adjust_host -- over the sequence's prompt and the ids
+        picked so far, which the picker logs on the device, and picks on the adjusted rows: greedy takes the kernel's
+        token, sampling and the grammar read the adjusted rows; while fewer than min_new_tokens ids are out, stop_ids are
+        biased to -inf.  penalty_exempt: ids no penalty touches (penalties.exempt_ids).  logprobs keeps scoring the raw
+        logits, and speculate=k returns the ids of speculate=0.  None or a neutral value: nothing is allocated or
+        launched, the code path without penalties."""
         max_new_tokens, speculate = int(max_new_tokens), self._check_speculate(speculate)
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be positive")
@@ -722,7 +818,8 @@ class Qwen3Generator:
             raise PromptTooLong(f"a prompt of {longest} tokens does not fit: max_context {self.max_context} - "
                                 f"max_new_tokens {max_new_tokens} leaves {room}")
         stop = {int(s) for s in stop_ids}
-        pick = _Picker(self, len(prompts), grammar, sampling, streams, logprobs)
+        pick = _Picker(self, len(prompts), grammar, sampling, streams, logprobs, penalties, prompts, max_new_tokens, stop,
+                       penalty_exempt)
         keeps = [0] * len(prompts)
         if reuse_prefix and len(prompts) <= self.max_seqs:
             keeps = [plan_reuse(self.resident(b), p, PREFIX_MIN_REUSE) for b, p in enumerate(prompts)]
@@ -914,7 +1011,8 @@ class Qwen3Generator:
     def generate_samples(self, prompt: Sequence[int], n: int, max_new_tokens: int, stop_ids: Sequence[int] = (),
                          reuse_prefix: bool = False, grammar: Optional[TokenGrammar] = None,
                          sampling=None, streams: Optional[Sequence[int]] = None, speculate: int = 0,
-                         drafter=None, logprobs: Optional[int] = None) -> List[List[int]]:
+                         drafter=None, logprobs: Optional[int] = None, penalties: Optional[PenaltyParams] = None,
+                         penalty_exempt: Optional[Sequence[int]] = None) -> List[List[int]]:
         """n (1..max_seqs) continuations of ONE prompt from one prefill: the prompt goes into slot 0 (prefill, or extend
         behind what plan_reuse keeps under reuse_prefix, as in generate), slots 1..n-1 are forked from it, the one row
         of logits serves every sequence's first pick, and generate's token loop runs over the n slots: a child reads
@@ -923,7 +1021,8 @@ class Qwen3Generator:
         Afterwards the children are empty and slot 0 holds the prompt and continuation 0 with their ids, for a later
         reuse_prefix.  last_reuse / last_grammar hold one entry per sample (the prompt's rows were reused / computed
         once, for all of them).  n = 1 is generate([prompt], ...).  speculate / drafter: as in generate; every sample
-        drafts from the prompt and its own output.  logprobs: as in generate, last_logprobs[i] for sample i."""
+        drafts from the prompt and its own output.  logprobs: as in generate, last_logprobs[i] for sample i.  penalties /
+        penalty_exempt: as in generate, one value for every sample; each sample is penalised for its own output."""
         n, max_new_tokens, speculate = int(n), int(max_new_tokens), self._check_speculate(speculate)
         if not 1 <= n <= self.max_seqs:
             raise ValueError(f"generate_samples takes n in 1..{self.max_seqs}")
@@ -933,7 +1032,10 @@ class Qwen3Generator:
         if len(prompt) > room:
             raise PromptTooLong(f"a prompt of {len(prompt)} tokens does not fit: max_context {self.max_context} - "
                                 f"max_new_tokens {max_new_tokens} leaves {room}")
-        pick = _Picker(self, n, grammar, sampling, streams, logprobs)
+        if penalties is not None and not isinstance(penalties, PenaltyParams):
+            raise ValueError("generate_samples takes one PenaltyParams for all samples")
+        pick = _Picker(self, n, grammar, sampling, streams, logprobs, penalties, [prompt] * n, max_new_tokens,
+                       {int(s) for s in stop_ids}, penalty_exempt)
         keep = plan_reuse(self.resident(0), prompt, PREFIX_MIN_REUSE) if reuse_prefix else 0
         if keep:
             self.truncate(0, keep)
@@ -959,22 +1061,26 @@ class Qwen3Generator:
     def generate_text_samples(self, messages: Sequence[Dict[str, str]], n: int, max_new_tokens: int,
                               grammar: Optional[TokenGrammar] = None, sampling: Optional[SamplingParams] = None,
                               streams: Optional[Sequence[int]] = None, speculate: int = 0, drafter=None,
-                              logprobs: Optional[int] = None) -> List[str]:
+                              logprobs: Optional[int] = None, penalties: Optional[PenaltyParams] = None,
+                              penalty_exempt: Optional[Sequence[int]] = None) -> List[str]:
         """One chat -> n replies as text from one prefill (generate_samples), reply i drawn on noise stream streams[i];
-        logprobs: last_logprobs[i] holds reply i's records."""
+        logprobs: last_logprobs[i] holds reply i's records; penalties / penalty_exempt: as in generate."""
         ids = self.generate_samples(self.chat_ids(messages), n, max_new_tokens, self.stop_ids(),
                                     reuse_prefix=self.prefix_cache, grammar=grammar, sampling=sampling, streams=streams,
-                                    speculate=speculate, drafter=drafter, logprobs=logprobs)
+                                    speculate=speculate, drafter=drafter, logprobs=logprobs, penalties=penalties,
+                                    penalty_exempt=penalty_exempt)
         tok = self._tokenizer()
         return [tok.decode(x, skip_special_tokens=True) for x in ids]
 
     def generate_text(self, messages: Sequence[Dict[str, str]], max_new_tokens: int,
                       grammar: Optional[TokenGrammar] = None, sampling: Optional[SamplingParams] = None,
-                      stream: int = 0, speculate: int = 0, drafter=None, logprobs: Optional[int] = None) -> str:
+                      stream: int = 0, speculate: int = 0, drafter=None, logprobs: Optional[int] = None,
+                      penalties: Optional[PenaltyParams] = None, penalty_exempt: Optional[Sequence[int]] = None) -> str:
         """One chat -> the assistant's reply as text; under `grammar` when one is given, drawn with `sampling` on noise
-        stream `stream` when that is given (generate); logprobs: last_logprobs[0] holds the reply's records."""
+        stream `stream` when that is given (generate); logprobs: last_logprobs[0] holds the reply's records; penalties /
+        penalty_exempt: as in generate."""
         ids = self.generate([self.chat_ids(messages)], max_new_tokens, self.stop_ids(),
                             reuse_prefix=self.prefix_cache, grammar=grammar, sampling=sampling,
                             streams=None if sampling is None else [int(stream)], speculate=speculate,
-                            drafter=drafter, logprobs=logprobs)[0]
+                            drafter=drafter, logprobs=logprobs, penalties=penalties, penalty_exempt=penalty_exempt)[0]
         return self._tokenizer().decode(ids, skip_special_tokens=True)

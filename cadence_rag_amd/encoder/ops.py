@@ -557,6 +557,63 @@ def logprobs(logits, token, logprob, *, allowed_bits=None, lse_all=None, lse_all
     return logprob
 
 
+# -- repetition control (csrc/crag_penalty.hip) -------------------------------------------------------------------------
+def adjust_workspace(n_rows: int, vocab: int, device) -> torch.Tensor:
+    """Device scratch of adjust_logits for up to n_rows rows of vocab ids (uint8): a [vocab] int32 slice per row."""
+    need = int(_native.load().crag_enc_adjust_workspace_bytes(int(n_rows), int(vocab)))
+    if need <= 0:
+        raise ValueError(f"no adjust workspace for n_rows={n_rows}, vocab={vocab}")
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def adjust_logits(logits, out, history, history_rows, prompt_lens, total_lens, params, token, workspace, *,
+                  exempt_bits=None, bias_ids=None, bias_values=None, bias_offsets=None):
+    """Per row of logits [n <= 8, vocab] fp32: out[r] (fp32, may be logits itself) = the row under params[r]
+    (cadence_rag_amd.penalties PenaltyParams; one for all rows, or one per row) and token[r] (int32) = the lowest id among
+    its maxima (crag_enc_adjust_logits; the rule: penalties.adjust_host).  history [rows, stride] int32 is a token log on
+    the device: row r reads the first total_lens[r] ids of log row history_rows[r], the first prompt_lens[r] of them its
+    prompt (HOST ints).  exempt_bits (optional) [ceil(vocab / 32)] int32, shared by the rows: ids no penalty touches.
+    bias_ids int32 / bias_values float32 (device) with bias_offsets (HOST ints, n + 1, rising from 0), given together: the
+    rows' bias lists back to back, a row's ids strictly ascending -- params[r].logit_bias is NOT read here.  workspace:
+    adjust_workspace(n, vocab)."""
+    from ..penalties import PenaltyParams
+    _req(logits, torch.float32, "logits"); _req(out, torch.float32, "out"); _req(history, torch.int32, "history")
+    _req(token, torch.int32, "token"); _req(workspace, torch.uint8, "workspace")
+    if logits.dim() != 2 or history.dim() != 2 or out.shape != logits.shape:
+        raise ValueError("logits and out must be [n, vocab] and history [rows, stride]")
+    n, vocab = logits.shape
+    rows = [params] * n if isinstance(params, PenaltyParams) else list(params)
+    lists = [[int(x) for x in xs] for xs in (history_rows, prompt_lens, total_lens)]
+    if len(rows) != n or any(len(xs) != n for xs in lists) or token.numel() != n:
+        raise ValueError("params, history_rows, prompt_lens, total_lens and token need one entry per row")
+    if exempt_bits is not None:
+        _req(exempt_bits, torch.int32, "exempt_bits")
+        if exempt_bits.numel() != (vocab + 31) // 32:
+            raise ValueError("exempt_bits must be [ceil(vocab / 32)]")
+    given = [x is not None for x in (bias_ids, bias_values, bias_offsets)]
+    if any(given) != all(given):
+        raise ValueError("bias_ids, bias_values and bias_offsets are given together")
+    h_off = None
+    if all(given):
+        _req(bias_ids, torch.int32, "bias_ids"); _req(bias_values, torch.float32, "bias_values")
+        offsets = [int(x) for x in bias_offsets]
+        if len(offsets) != n + 1 or bias_ids.numel() != bias_values.numel() or \
+                (n <= _native.CRAG_DECODE_MAX_SEQS and max(offsets) > bias_ids.numel()):
+            raise ValueError("bias_offsets needs n + 1 entries inside bias_ids, and bias_values one value per id")
+        h_off = (ctypes.c_int32 * (n + 1))(*offsets)
+    m = max(n, 1)
+    h_row, h_prompt, h_total = ((ctypes.c_int32 * m)(*xs) for xs in lists)
+    h_rp = (ctypes.c_float * m)(*[float(p.repetition_penalty) for p in rows])
+    h_fr = (ctypes.c_float * m)(*[float(p.frequency_penalty) for p in rows])
+    h_pr = (ctypes.c_float * m)(*[float(p.presence_penalty) for p in rows])
+    h_ng = (ctypes.c_int32 * m)(*[int(p.no_repeat_ngram) for p in rows])
+    _native.check(_native.load().crag_enc_adjust_logits(
+        _p(logits), _p(out), int(vocab), _p(history), int(history.shape[1]), int(history.shape[0]), h_row, h_prompt,
+        h_total, h_rp, h_fr, h_pr, h_ng, _p(exempt_bits), _p(bias_ids), _p(bias_values), h_off, _p(token), _p(workspace),
+        int(workspace.numel()), int(n), _stream()), "crag_enc_adjust_logits")
+    return out, token
+
+
 # -- continuing cached sequences (csrc/crag_extend.hip) ---------------------------------------------------------------
 def extend_workspace_bytes(n_seqs: int, hq: int, max_new_rows: int, max_len: int) -> int:
     """Bytes of scratch extend_attention needs at most for up to n_seqs sequences with up to max_new_rows new rows in

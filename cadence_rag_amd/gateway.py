@@ -159,6 +159,13 @@ class AnswerRequestModel(RetrieveRequestModel):
     speculate: Optional[int] = Field(default=None, ge=0, le=7)   # drafts per forward (ANSWER_SPECULATE when absent)
     logprobs: Optional[bool] = None      # score the answer's tokens (ANSWER_LOGPROBS when absent)
     sample_rank: Optional[str] = None    # "first" or "logprob" (ANSWER_SAMPLE_RANK when absent); anything else is a 422
+    # repetition control (cadence_rag_amd.penalties): absent fields take the ANSWER_* defaults; out of range is a 422
+    repetition_penalty: Optional[float] = Field(default=None, ge=0.1, le=10.0)
+    presence_penalty: Optional[float] = Field(default=None, ge=-2.0, le=2.0)
+    frequency_penalty: Optional[float] = Field(default=None, ge=-2.0, le=2.0)
+    no_repeat_ngram: Optional[int] = Field(default=None, ge=0, le=8)
+    logit_bias: Optional[Dict[str, float]] = None    # token id -> value in -100..100, or -inf (checked by PenaltyParams)
+    min_new_tokens: Optional[int] = Field(default=None, ge=0)
 
 
 @app.post("/answer")
@@ -167,7 +174,10 @@ def answer_endpoint(payload: AnswerRequestModel) -> dict:
                                     temperature=payload.temperature, top_p=payload.top_p, top_k=payload.top_k,
                                     min_p=payload.min_p, seed=payload.seed, samples=payload.samples,
                                     speculate=payload.speculate, logprobs=payload.logprobs,
-                                    sample_rank=payload.sample_rank)
+                                    sample_rank=payload.sample_rank, repetition_penalty=payload.repetition_penalty,
+                                    presence_penalty=payload.presence_penalty,
+                                    frequency_penalty=payload.frequency_penalty, no_repeat_ngram=payload.no_repeat_ngram,
+                                    logit_bias=payload.logit_bias, min_new_tokens=payload.min_new_tokens)
     try:
         return _answer.answer_question(request)
     except _answer.AnswerRequestError as exc:

@@ -414,6 +414,58 @@ int crag_enc_logprobs(const float *logits, int64_t vocab, const uint32_t *allowe
                       float *logprob, float *lse_all, float *lse_allowed, int32_t *rank, int32_t *top_id,
                       float *top_logprob, int n_top, int n_rows, void *stream);
 
+/* ---- repetition control: csrc/crag_penalty.hip ----
+ *
+ * crag_enc_adjust_logits: per row r < n_rows (1..CRAG_DECODE_MAX_SEQS) of logits [n_rows, vocab] fp32, the logits a
+ *   caller that wants the model to move away from what it has said picks its next token from, and the greedy token on
+ *   them.  out [n_rows, vocab] fp32 may be logits itself.  The rule, operation by operation, is
+ *   cadence_rag_amd/penalties.py (adjust_host); the kernel gives its bits.
+ *   history [n_history_rows, history_stride] int32 (device) is a token log: row r reads the first h_total_len[r] ids of
+ *   log row h_history_row[r] -- H, of which the first h_prompt_len[r] are the prompt P and the rest the output O.  Two
+ *   rows may name one log row with different lengths (a sequence's rows under speculation).  An id of the log outside
+ *   0..vocab - 1 is ignored.  seen(t): t occurs in H; c(t): how often t occurs in O.  The h_* arrays are HOST arrays of
+ *   n_rows entries, h_bias_offsets of n_rows + 1.  Per id t, from l = logits[r][t]:
+ *     1. unless bit t % 32 of exempt_bits[t / 32] is set (device, [ceil(vocab / 32)], shared by the rows; NULL: no id):
+ *        a. seen(t) and h_repetition[r] != 1:  l = l / rp when l > 0, else l * rp -- one correctly rounded operation; a
+ *           NaN takes the else arm
+ *        b. c(t) > 0:  l = (l - fp32(h_frequency[r] * fp32(c))) - h_presence[r] -- three roundings, never a fused
+ *           multiply-add
+ *        c. n = h_ngram[r] > 0 and some j with j + n - 1 < |O| has O[j .. j+n-2] equal to the last n - 1 ids of O and
+ *           O[j+n-1] == t:  l = -inf
+ *     2. t == bias_ids[k] for a k in h_bias_offsets[r] .. h_bias_offsets[r + 1] - 1:  l = l + bias_values[k].  bias_ids /
+ *        bias_values are device arrays, the ids of a row's slice strictly ascending inside 0..vocab - 1; the three are
+ *        NULL together: no bias.
+ *   token[r] (device int32) = the lowest id among the maxima of out[r], NaNs left out, -1 when nothing is left:
+ *   crag_enc_lm_head's rule.
+ *   One workgroup per row, which zeroes a [vocab] int32 slice of the workspace, scatters the history, the n-gram
+ *   continuations and the bias flags into it and walks the vocabulary once; the history has no cap.  Integer atomics on
+ *   the row's own slice are the only atomics, every store is a plain vector store.  The same inputs give the same bits
+ *   on every run, and a row's out bits and token depend on its own logits, history and parameters alone -- not on
+ *   n_rows or its position.
+ *   workspace: crag_enc_adjust_workspace_bytes(n_rows, vocab) bytes of device scratch, 16-byte aligned (0: n_rows or
+ *   vocab out of range).  A row is read 16 bytes at a time from its first 16-byte aligned id on; out is stored that way
+ *   when its rows have the misalignment of the logits rows (out == logits, or two tensors of one shape).
+ *   CRAG_EINVAL, nothing launched: a NULL pointer (exempt_bits and the three bias arrays excepted, those three only
+ *   together), n_rows outside 1..8, vocab outside 1..2^31 - 1, a repetition penalty outside CRAG_ADJUST_MIN_REPETITION..
+ *   CRAG_ADJUST_MAX_REPETITION, a frequency or presence penalty outside -CRAG_ADJUST_MAX_ADDITIVE..
+ *   CRAG_ADJUST_MAX_ADDITIVE (a NaN is outside), an n-gram size that is neither 0 nor in 2..CRAG_ADJUST_MAX_NGRAM,
+ *   prompt_len > total_len, total_len > history_stride, a negative length, a history row outside the log, a bias slice
+ *   longer than CRAG_ADJUST_MAX_BIAS, offsets that do not rise from 0, bias ids not strictly ascending or outside the
+ *   vocabulary (a call with bias entries reads the ids back with one small synchronous copy to see them; one without
+ *   makes no copy), a device pointer not aligned to 4 bytes, a workspace not aligned to 16.  CRAG_E2BIG: the workspace is too small. */
+#define CRAG_ADJUST_MIN_REPETITION 0.1f
+#define CRAG_ADJUST_MAX_REPETITION 10.0f
+#define CRAG_ADJUST_MAX_ADDITIVE 2.0f
+#define CRAG_ADJUST_MAX_NGRAM 8
+#define CRAG_ADJUST_MAX_BIAS 256
+int64_t crag_enc_adjust_workspace_bytes(int n_rows, int64_t vocab);
+int crag_enc_adjust_logits(const float *logits, float *out, int64_t vocab, const int32_t *history, int64_t history_stride,
+                           int n_history_rows, const int32_t *h_history_row, const int32_t *h_prompt_len,
+                           const int32_t *h_total_len, const float *h_repetition, const float *h_frequency,
+                           const float *h_presence, const int32_t *h_ngram, const uint32_t *exempt_bits,
+                           const int32_t *bias_ids, const float *bias_values, const int32_t *h_bias_offsets,
+                           int32_t *token, void *workspace, int64_t workspace_bytes, int n_rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
