@@ -20,6 +20,7 @@ CRAG_DIM = 1024
 CRAG_DEDUPE_MAX_WIDTH = 256
 CRAG_SUBSET_MAX_WIDTH = 4096
 CRAG_GROUP_MAX_PER = 8
+CRAG_MMR_MAX_WIDTH = 256
 CRAG_FILTER_MAX_QUERIES = 64
 CRAG_ATTR_MAX_QUERIES = 64
 CRAG_ATTR_MAX_CLAUSES = 8
@@ -98,6 +99,9 @@ SIGNATURES = {
     "crag_index_search_grouped_scratch_bytes": (_c.c_int64, [_c.c_int, _c.c_int64, _c.c_int]),
     "crag_index_search_grouped_async": (_c.c_int, [_P, _P, _c.c_int, _c.c_int, _P, _c.c_int64, _c.c_int, _P, _c.c_int64,
                                                    _P, _P, _P, _P, _P, _c.c_int64, _P]),
+    "crag_index_mmr_scratch_bytes": (_c.c_int64, [_c.c_int, _c.c_int]),
+    "crag_index_mmr_async": (_c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_float, _c.c_int, _P, _P, _P, _P, _P, _P,
+                                        _P, _c.c_int64, _P]),
     "crag_index_phase_trace": (_c.c_int, [_P, _c.POINTER(_c.c_uint64)]),
     "crag_index_prefilter_stats": (_c.c_int, [_P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64),
                                               _c.POINTER(_c.c_int64)]),

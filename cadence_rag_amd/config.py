@@ -55,6 +55,12 @@ class Settings:
     # at most this many chunks of one call among the lane's rows, applied over the whole table (the grouped search), so
     # that one long call cannot fill the lane while _pack keeps DEFAULT_MAX_QUOTES_PER_CALL of it.  0 = off
     dense_per_call_cap: int = 0
+    # maximal marginal relevance on the dense lanes (the graded form of the reference's planned redundancy control,
+    # PHASED_PLAN.md:286-303): the lane fetches dense_mmr_fetch rows (0: min(4 x its limit, 256); a search returns at most
+    # CRAG_MAX_K) and picks its limit among them by lambda * cosine to the query - (1 - lambda) * the largest cosine to a
+    # row picked before (crag_index_mmr_async).  1.0 = the plain ranking = off: nothing is launched
+    dense_mmr_lambda: float = 1.0
+    dense_mmr_fetch: int = 0
     # /answer (PHASED_PLAN.md:318-326): "" = off, "native" = the in-process Qwen3Generator, http(s) = an OpenAI-compatible
     # chat-completions service
     llm_base_url: str = ""

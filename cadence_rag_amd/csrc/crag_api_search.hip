@@ -475,6 +475,51 @@ int crag_index_search_ids_async(crag_index *ix, const float *d_queries, int nq, 
     return CRAG_OK;
 }
 
+int64_t crag_index_mmr_scratch_bytes(int nq, int width) { return crag::mmr_scratch_bytes(nq, width); }
+
+int crag_index_mmr_async(crag_index *ix, const int64_t *d_ids, const float *d_rel, const int32_t *d_counts, int nq,
+                         int width, float lambda, int k, int64_t *d_out_ids, float *d_out_rel, float *d_out_value,
+                         int32_t *d_out_slots, float *d_out_sim_rows, int32_t *d_out_counts, void *d_scratch,
+                         int64_t scratch_bytes, void *stream) {
+    if (!ix) return fail(CRAG_EINVAL, "mmr: index is NULL");
+    if (nq < 0 || nq > 65535) return fail(CRAG_EINVAL, "mmr: nq must be in [0, 65535] (got %d)", nq);
+    if (width < 1 || width > CRAG_MMR_MAX_WIDTH)
+        return fail(CRAG_EINVAL, "mmr: width must be in [1, %d] (got %d)", CRAG_MMR_MAX_WIDTH, width);
+    if (k < 1 || k > CRAG_MMR_MAX_WIDTH) return fail(CRAG_EINVAL, "mmr: k must be in [1, %d] (got %d)", CRAG_MMR_MAX_WIDTH, k);
+    if (!(lambda >= 0.f && lambda <= 1.f))   // (NaN fails both)
+        return fail(CRAG_EINVAL, "mmr: lambda must be finite, in [0, 1] (got %g)", (double)lambda);
+    if (!d_ids || !d_rel || !d_counts || !d_out_ids || !d_out_rel || !d_out_counts || !d_scratch)
+        return fail(CRAG_EINVAL, "mmr: ids / rel / counts / out_ids / out_rel / out_counts / scratch must not be NULL");
+    if (scratch_bytes < crag::mmr_scratch_bytes(nq, width) || ((uintptr_t)d_scratch & 7))
+        return fail(CRAG_EINVAL, "mmr: scratch too small or not 8-byte aligned (crag_index_mmr_scratch_bytes)");
+    if (nq == 0) return CRAG_OK;
+    std::lock_guard<std::mutex> lk(ix->mu);
+    DeviceGuard guard(ix->device);
+    crag::MmrParams p;
+    p.corpus = ix->corpus;
+    p.inv_norm = ix->inv_norm;
+    p.stored = ix->ids;
+    p.size = ix->size;
+    p.piece_shift = crag::crag_piece_shift(ix->corpus16 != nullptr);
+    p.ids = d_ids;
+    p.rel = d_rel;
+    p.counts = d_counts;
+    p.nq = nq;
+    p.width = width;
+    p.k = k;
+    p.lambda = lambda;
+    p.mu = 1.0f - lambda;
+    p.gram = (float *)d_scratch;
+    p.out_ids = d_out_ids;
+    p.out_rel = d_out_rel;
+    p.out_value = d_out_value;
+    p.out_slots = d_out_slots;
+    p.out_sim_rows = d_out_sim_rows;
+    p.out_counts = d_out_counts;
+    HIP_TRY(crag::launch_mmr(p, (hipStream_t)stream));
+    return CRAG_OK;
+}
+
 int64_t crag_index_search_grouped_scratch_bytes(int nq, int64_t n_groups, int per_group) {
     return crag::group_scratch_bytes(nq, n_groups, per_group);
 }

@@ -286,4 +286,28 @@ struct GroupParams {
 int64_t group_scratch_bytes(int nq, int64_t n_groups, int per_group);
 hipError_t launch_grouped(const GroupParams &p, hipStream_t st);
 
+// ---- MMR diversification of ranked lists (crag_mmr.hip) ----
+struct MmrParams {
+    const float *corpus;        // tile32 layout
+    const float *inv_norm;
+    const int64_t *stored;      // [size] ids, ascending with the position
+    int64_t size;
+    int piece_shift;
+    const int64_t *ids;         // [nq, width]
+    const float *rel;           // [nq, width] relevance of each slot
+    const int32_t *counts;      // [nq], clamped to [0, width]
+    int nq, width, k;           // width, k <= CRAG_MMR_MAX_WIDTH
+    float lambda, mu;           // mu = 1.0f - lambda, rounded once on the host
+    float *gram;                // scratch [nq][width_pad][width_pad] pair cosines, NaN: not comparable
+    int64_t *out_ids;           // [nq, k] picks in pick order, -1 padded
+    float *out_rel;             // [nq, k], NaN padded
+    float *out_value;           // nullable [nq, k] the winning value, NaN padded
+    int32_t *out_slots;         // nullable [nq, k] the input slot of each pick, -1 padded
+    float *out_sim_rows;        // nullable [nq, k, width] cos(pick, slot), NaN: not comparable / ignored / no pick
+    int32_t *out_counts;        // [nq]
+};
+// the queries' Gram matrices: width rounded up to whole blocks of 32, squared, fp32
+int64_t mmr_scratch_bytes(int nq, int width);
+hipError_t launch_mmr(const MmrParams &p, hipStream_t st);
+
 }  // namespace crag

@@ -51,6 +51,7 @@ class DenseIndex:
         self._h = ctypes.c_void_p()
         self.dim = int(dim)
         self.device = int(device)
+        self._mmr_scratch: dict = {}   # per (stream, nq, width): the scratch of mmr_async
         _native.check(self._lib.crag_index_create(self.device, self.dim, int(capacity),
                                                   ctypes.byref(self._h)), "crag_index_create")
 
@@ -59,6 +60,7 @@ class DenseIndex:
         if getattr(self, "_h", None) is not None and self._h:
             self._lib.crag_index_destroy(self._h)
             self._h = ctypes.c_void_p()
+            self._mmr_scratch = {}
 
     def __del__(self) -> None:  # pragma: no cover
         try:
@@ -366,6 +368,80 @@ class DenseIndex:
                                   stream=torch.cuda.current_stream(dev).cuda_stream)
         res = (out_ids.cpu().numpy(), out_sc.cpu().numpy(), out_ct.cpu().numpy())
         return res + (slot.cpu().numpy(),) if slot_scores else res
+
+    # -- maximal marginal relevance over ranked lists (crag_index_mmr_async) ------------------------
+    @staticmethod
+    def mmr_scratch_bytes(nq: int, width: int) -> int:
+        return int(_native.load().crag_index_mmr_scratch_bytes(int(nq), int(width)))
+
+    def mmr_async(self, d_ids, d_rel, d_counts, lam: float, k: int, d_out_ids, d_out_rel, d_out_counts,
+                  d_out_value=None, d_out_slots=None, d_out_sim_rows=None, scratch=None, stream: int = 0) -> None:
+        """MMR over ranked lists, enqueued on `stream`: d_ids int64 / d_rel fp32 [nq, width <= 256], d_counts int32 [nq]
+        (what search_async emits).  k times per list the candidate with the largest lam * rel - (1 - lam) * pen is
+        picked (ties: the lower id), pen being the largest cosine to a row picked before; slots beyond the count, -1, a
+        non-finite rel and a repeated id are ignored, an id without a stored vector is picked by rel alone.  d_out_ids
+        int64 / d_out_rel fp32 [nq, k] in pick order (-1 / NaN pad), d_out_counts int32 [nq]; optional d_out_value fp32
+        and d_out_slots int32 [nq, k], d_out_sim_rows fp32 [nq, k, width] (cos(pick, slot), NaN: no pair).  scratch: a
+        uint8 CUDA tensor of mmr_scratch_bytes(nq, width) bytes, one per stream in use (default: kept here per (stream,
+        nq, width)).  Arguments are torch CUDA tensors."""
+        if d_ids.dim() != 2:
+            raise ValueError("d_ids must have shape [nq, width]")
+        nq, width = int(d_ids.shape[0]), int(d_ids.shape[1])
+        if scratch is None:
+            scratch = self._mmr_scratch.get((stream, nq, width))
+            if scratch is None:
+                scratch = self._mmr_scratch[(stream, nq, width)] = torch.empty(
+                    self.mmr_scratch_bytes(nq, width), dtype=torch.uint8, device=d_ids.device)
+        opt = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        _native.check(self._lib.crag_index_mmr_async(
+            self._h, d_ids.data_ptr(), d_rel.data_ptr(), d_counts.data_ptr(), nq, width, float(lam), int(k),
+            d_out_ids.data_ptr(), d_out_rel.data_ptr(), opt(d_out_value), opt(d_out_slots), opt(d_out_sim_rows),
+            d_out_counts.data_ptr(), scratch.data_ptr(), int(scratch.numel()) * scratch.element_size(),
+            ctypes.c_void_p(stream)), "crag_index_mmr_async")
+
+    def mmr(self, ids, rel, lam: float, k: int):
+        """Host convenience over mmr_async for one list (flat sequences of ids and relevances) or several (sequences of
+        sequences, lengths may differ; at most 256 slots each).  Returns (ids, rel, value, slots) of the picks in pick
+        order -- arrays for one list, lists of arrays for several.  Synchronises."""
+        if torch is None:  # pragma: no cover
+            raise _native.NativeLibraryError("DenseIndex.mmr stages its buffers with torch")
+        single = len(ids) == 0 or np.ndim(ids[0]) == 0
+        lists = [np.asarray(ids, dtype=np.int64).reshape(-1)] if single else \
+            [np.asarray(l, dtype=np.int64).reshape(-1) for l in ids]
+        rels = [np.asarray(rel, dtype=np.float32).reshape(-1)] if single else \
+            [np.asarray(r, dtype=np.float32).reshape(-1) for r in rel]
+        if len(rels) != len(lists) or any(r.size != l.size for r, l in zip(rels, lists)):
+            raise ValueError("ids and rel must have the same shape")
+        width = max([int(l.size) for l in lists] + [1])
+        if width > _native.CRAG_MMR_MAX_WIDTH:
+            raise ValueError(f"a list holds at most {_native.CRAG_MMR_MAX_WIDTH} ids (got {width})")
+        if not 1 <= int(k) <= _native.CRAG_MMR_MAX_WIDTH:
+            raise ValueError(f"k must be in [1, {_native.CRAG_MMR_MAX_WIDTH}] (got {k})")
+        if not 0.0 <= float(lam) <= 1.0:
+            raise ValueError(f"lam must be finite, in [0, 1] (got {lam})")
+        nq, k = len(lists), int(k)
+        h_ids = np.full((nq, width), -1, dtype=np.int64)
+        h_rel = np.full((nq, width), np.nan, dtype=np.float32)
+        for q, (l, r) in enumerate(zip(lists, rels)):
+            h_ids[q, :l.size] = l
+            h_rel[q, :r.size] = r
+        dev = torch.device("cuda", self.device)
+        d_ids, d_rel = torch.from_numpy(h_ids).to(dev), torch.from_numpy(h_rel).to(dev)
+        d_ct = torch.tensor([int(l.size) for l in lists], dtype=torch.int32, device=dev)
+        o_ids = torch.empty(nq, k, dtype=torch.int64, device=dev)
+        o_rel = torch.empty(nq, k, dtype=torch.float32, device=dev)
+        o_val = torch.empty(nq, k, dtype=torch.float32, device=dev)
+        o_slot = torch.empty(nq, k, dtype=torch.int32, device=dev)
+        o_ct = torch.empty(nq, dtype=torch.int32, device=dev)
+        if nq:
+            self.mmr_async(d_ids, d_rel, d_ct, lam, k, o_ids, o_rel, o_ct, o_val, o_slot,
+                           stream=torch.cuda.current_stream(dev).cuda_stream)
+        ct = o_ct.cpu().numpy()
+        outs = [t.cpu().numpy() for t in (o_ids, o_rel, o_val, o_slot)]
+        res = [tuple(a[q, :ct[q]].copy() for a in outs) for q in range(nq)]
+        if single:
+            return res[0]
+        return tuple([r[i] for r in res] for i in range(4))
 
     # -- exact top-k under a cap per group (crag_index_search_grouped_async) ------------------------
     GROUPED_SCRATCH_LIMIT = 256 << 20   # search_grouped splits its queries so that the scratch stays at or below this

@@ -601,14 +601,19 @@ class DenseTable:
 
     def fetch_dense(self, query_embedding, filters: Optional[RetrieveFilters],
                     call_ids: Optional[Sequence[UUID]], mode: str, limit: int,
-                    select: Sequence[str], per_call: Optional[int] = None) -> List[Dict[str, Any]]:
+                    select: Sequence[str], per_call: Optional[int] = None, mmr=None) -> List[Dict[str, Any]]:
         """ORDER BY embedding <=> q LIMIT :limit, rows as mappings with `select` columns + score.  per_call: at most
         that many rows of one call among them -- the best rows under the cap over the WHOLE table (the grouped search,
-        crag_index_search_grouped_async, over the filter columns' call numbers), not a cut of the plain top-`limit`."""
+        crag_index_search_grouped_async, over the filter columns' call numbers), not a cut of the plain top-`limit`.
+        mmr (cadence_rag_amd.mmr.MmrParams): the lane fetches mmr.fetch rows by the same route, picks `limit` of them by
+        maximal marginal relevance on the GPU (DenseIndex.mmr: relevance = the row's cosine to the query, redundancy =
+        its largest cosine to a row picked before) and returns them in pick order, `score` still the cosine."""
         del mode  # the HBM scan is always exact; `mode` only labels what pgvector would have done
         if len(self) == 0 or limit <= 0:
             return []
         q = _parse_vector(query_embedding)
+        if mmr is not None:
+            return self._fetch_dense_mmr(q, filters, call_ids, int(limit), select, per_call, mmr)
         if per_call:
             # (the listed-rows route below has no cap: every capped request takes the grouped search)
             ids, scores, _, counts = self._search_per_call(q, filters, call_ids, int(limit), int(per_call))
@@ -635,6 +640,49 @@ class DenseTable:
             row["score"] = float(sc)
             rows.append(row)
         return rows
+
+    def _fetch_dense_mmr(self, q: np.ndarray, filters, call_ids, limit: int, select: Sequence[str],
+                         per_call: Optional[int], mmr) -> List[Dict[str, Any]]:
+        """fetch_dense with MMR: mmr.fetch_for(limit) rows (a search returns at most CRAG_MAX_K) by the route the request
+        takes without it -- the grouped search under a cap, the listed rows of a small call scope, else the masked
+        search --, then `limit` picks among them.  The search's ids, scores and count stay on the device: the MMR call
+        follows the search on the same stream and only the picks come back."""
+        import torch
+
+        from ._native import CRAG_MMR_MAX_WIDTH, CRAG_SUBSET_MAX_WIDTH
+        ix = self.index
+        limit = min(limit, CRAG_MMR_MAX_WIDTH)
+        fetch = min(mmr.fetch_for(limit), _native_max_k())
+        dev = torch.device("cuda", ix.device)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        d_q = torch.from_numpy(np.ascontiguousarray(q[None, :], dtype=np.float32)).to(dev)
+        d_ids = torch.empty(1, fetch, dtype=torch.int64, device=dev)
+        d_rel = torch.empty(1, fetch, dtype=torch.float32, device=dev)
+        d_ct = torch.empty(1, dtype=torch.int32, device=dev)
+        listed = None
+        if not per_call:
+            cap = min(max(settings.embeddings_exact_scan_threshold, 0), CRAG_SUBSET_MAX_WIDTH)
+            listed = self.scoped_positions(filters, call_ids, cap) if cap > 0 else None
+        if listed is not None:
+            if listed.size == 0:
+                return []
+            id_col = self.columns[self.id_field]
+            d_list = torch.tensor([[int(id_col[i]) for i in listed]], dtype=torch.int64, device=dev)
+            d_n = torch.tensor([int(listed.size)], dtype=torch.int32, device=dev)
+            ix.search_ids_async(d_q, d_list, d_n, fetch, d_ids, d_rel, d_ct, stream=stream)
+        else:
+            mask = self.filter_mask_device(filters, call_ids)   # (complete in memory on return; shared: stride 0)
+            if per_call:
+                cols = self.filter_columns()
+                ix.search_grouped_async(d_q, fetch, cols.d_call_slot, cols.n_calls, int(per_call), d_ids, d_rel, d_ct,
+                                        d_row_mask=mask, stream=stream)
+            else:
+                ix.search_async(d_q, fetch, d_ids, d_rel, d_ct, d_row_mask=mask, stream=stream)
+        o_ids = torch.empty(1, limit, dtype=torch.int64, device=dev)
+        o_rel = torch.empty(1, limit, dtype=torch.float32, device=dev)
+        o_ct = torch.empty(1, dtype=torch.int32, device=dev)
+        ix.mmr_async(d_ids, d_rel, d_ct, float(mmr.lam), limit, o_ids, o_rel, o_ct, stream=stream)
+        return self._dense_rows(o_ids.cpu().numpy(), o_rel.cpu().numpy(), o_ct.cpu().numpy(), select)
 
     def _search_per_call(self, q: np.ndarray, filters, call_ids, limit: int, per_call: int):
         """The grouped search of one query under the request's filters: group = the row's call number."""
@@ -799,6 +847,16 @@ def _dense_per_call_cap() -> int:
     """Settings.dense_per_call_cap as the grouped search takes it: 0 (off) .. CRAG_GROUP_MAX_PER."""
     from ._native import CRAG_GROUP_MAX_PER
     return min(max(int(settings.dense_per_call_cap or 0), 0), CRAG_GROUP_MAX_PER)
+
+
+def _dense_mmr():
+    """Settings.dense_mmr_lambda / dense_mmr_fetch as the dense lanes take them: None when the knob is off (1.0 or more:
+    the plain ranking, nothing is launched), else the MmrParams with lambda clamped to [0, 1]."""
+    from .mmr import MmrParams
+    lam = float(settings.dense_mmr_lambda)
+    if not lam < 1.0:   # (NaN: off)
+        return None
+    return MmrParams(lam=max(lam, 0.0), fetch=max(int(settings.dense_mmr_fetch or 0), 0))
 
 
 def _estimate_dense_candidates(table: DenseTable, table_name: str, filters: Optional[RetrieveFilters],
@@ -993,12 +1051,20 @@ class GpuRetrieveBackend(RetrieveBackend):
 
     def fetch_chunks_dense(self, query_embedding, filters, call_ids, mode, limit):
         cap = _dense_per_call_cap()   # (the artifact side has no per-call quota in _pack: it stays uncapped)
+        mmr = _dense_mmr()
+        if mmr is not None:
+            return self.tables["chunks"].fetch_dense(query_embedding, filters, call_ids, mode, limit, CHUNK_SELECT,
+                                                     per_call=cap or None, mmr=mmr)
         if cap:
             return self.tables["chunks"].fetch_dense(query_embedding, filters, call_ids, mode, limit, CHUNK_SELECT,
                                                      per_call=cap)
         return _fetch_chunks_dense(self.tables["chunks"], query_embedding, filters, call_ids, mode, limit)
 
     def fetch_artifacts_dense(self, query_embedding, filters, call_ids, mode, limit):
+        mmr = _dense_mmr()
+        if mmr is not None:
+            return self.tables["artifact_chunks"].fetch_dense(query_embedding, filters, call_ids, mode, limit,
+                                                              ARTIFACT_SELECT, mmr=mmr)
         return _fetch_artifacts_dense(self.tables["artifact_chunks"], query_embedding, filters, call_ids, mode, limit)
 
     def facets(self, table_name, filters, call_ids, namespaces, top):
@@ -1259,6 +1325,8 @@ def _retrieval_notes(tokens: List[str], dense: _DenseState, rerank: Optional[_Re
         notes["dedupe_dropped"] = dict(dedupe.dropped)
     if _dense_per_call_cap():   # likewise
         notes["dense_per_call_cap"] = _dense_per_call_cap()
+    if _dense_mmr() is not None:   # likewise
+        notes["dense_mmr_lambda"] = _dense_mmr().lam
     return notes
 
 

@@ -274,6 +274,52 @@ int crag_index_search_grouped_async(crag_index *ix, const float *d_queries, int 
                                     int64_t *d_out_ids, float *d_out_scores, int32_t *d_out_groups, int32_t *d_out_counts,
                                     void *d_scratch, int64_t scratch_bytes, void *stream);
 
+/* Maximal marginal relevance (MMR) over ranked lists: the graded redundancy control of the dense lane, next to the two
+ * hard gates (the per-call cap of crag_index_search_grouped_async, the cosine threshold of crag_index_dedupe_async).
+ * Stands in for: the redundancy control the reference plans but has NO code for -- PHASED_PLAN.md:286-303 "improve
+ * top-of-pack precision and reduce redundancy" and IMPLEMENTATION_PLAN.md:150-158.  Meant for lists whose relevance is
+ * on the cosine scale (a search's scores, crag_index_search_ids_async's slot scores): relevance and pair similarity
+ * are then one scale.
+ *   d_ids [nq, width] int64, d_rel [nq, width] fp32 the relevance of each slot (any finite value is legal), d_counts
+ *   [nq] clamped to [0, width] -- the shape crag_index_search_async and crag_rrf_fuse emit
+ *   lambda  finite, in [0, 1];  mu = 1.0f - lambda, computed once in fp32;  k in [1, CRAG_MMR_MAX_WIDTH]
+ * A slot is a CANDIDATE when it lies below the count, its id is not -1, its rel is finite and no earlier slot below the
+ * count holds the same id; every other slot is ignored.  A candidate is COMPARABLE when its id is stored with
+ * inv_norm > 0 (dedupe's eligibility); one that is not can be picked, is never penalised and never penalises anyone.
+ * The walk, t = 0, 1, ... while t < k and candidates remain:
+ *   value[i] = lambda * rel[i] - mu * pen[i]      three fp32 operations (mul, mul, sub), each rounded once, no contraction
+ *   the candidate with the largest value is picked; equal values go to the lower id
+ *   pen[i] = 0 until a picked comparable item p is compared with a comparable i: the first comparison sets
+ *   pen[i] = sim(p, i), later ones pen[i] = max(pen[i], sim(p, i))
+ * lambda = 1 therefore yields the candidates in (rel descending, id ascending) order: crag_index_search_ids_async's
+ * order when rel holds its slot scores.
+ *   sim(i, j) = the bits crag_index_dedupe_async reports for the pair: clamp(dot(i, j) * (inv_norm[i] * inv_norm[j]),
+ *   -1, 1), the same fixed-order fp32 accumulation.  Symmetric; it depends on the two rows alone (not on the slot, width,
+ *   nq, k, lambda or the row layout, with or without the fp16 mirror).
+ * Outputs, per query, count = min(k, candidates):
+ *   d_out_ids [nq, k]          the picks in pick order, -1 padded
+ *   d_out_rel [nq, k]          their rel, NaN padded
+ *   d_out_value [nq, k]        nullable: the winning value bits, NaN padded
+ *   d_out_slots [nq, k]        nullable: the input slot of each pick, -1 padded
+ *   d_out_sim_rows [nq, k, width]  nullable: for pick t, sim(pick, slot) for every slot; NaN where the pair is not
+ *                              comparable or the slot is ignored; every cell of the rows t >= count is NaN
+ *   d_out_counts [nq]
+ *   d_scratch  crag_index_mmr_scratch_bytes(nq, width) bytes (the queries' pair-cosine matrices), 8-byte aligned, owned
+ *              by the caller, one per stream in use.  The call overwrites whatever it reads of it.
+ * All pointers DEVICE; two launches on `stream`, no host synchronisation, no allocation, no workspace of the index.  The
+ * outputs are a function of the inputs alone, bit for bit, from run to run.  Ordering against edits as for
+ * crag_index_dedupe_async.  An empty index is valid: nothing is comparable, the picks go by rel alone.
+ * CRAG_EINVAL with a message that contains "mmr", checked before any HIP call, nothing enqueued: NULL index or required
+ * pointer, nq < 0 (or > 65535), width < 1 or > CRAG_MMR_MAX_WIDTH, k outside [1, CRAG_MMR_MAX_WIDTH], a non-finite
+ * lambda or one outside [0, 1], scratch too small or not 8-byte aligned.  nq == 0 is CRAG_OK and excuses nothing else. */
+#define CRAG_MMR_MAX_WIDTH 256
+int64_t crag_index_mmr_scratch_bytes(int nq, int width);
+int crag_index_mmr_async(crag_index *ix, const int64_t *d_ids, const float *d_rel, const int32_t *d_counts,
+                         int nq, int width, float lambda, int k,
+                         int64_t *d_out_ids, float *d_out_rel, float *d_out_value, int32_t *d_out_slots,
+                         float *d_out_sim_rows, int32_t *d_out_counts,
+                         void *d_scratch, int64_t scratch_bytes, void *stream);
+
 /* Merge per-shard results (the multi-GPU exchange step: each rank's [nq, k] top-k after an
  * RCCL all-gather) into the global top-k.  All pointers DEVICE.
  *   d_ids/d_scores/d_counts  [n_lists, nq, k] / [n_lists, nq, k] / [n_lists, nq]
