@@ -1506,12 +1506,53 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
+// ---- developer probes of what a launch costs outside its blocks' own work (profiles/launch_weight_probe.json,
+// DESIGN 4.1).  Build-time only (make PROBE="-DCRAG_PROBE_...=N"), all off in the library that ships; none of them
+// changes a result.  A pad is N KiB of s_nop (4 bytes each).
+//   CRAG_PROBE_FIN_PAD_EXEC_KIB    straight-line pad run once at the start of every selection block: fetched + issued
+//   CRAG_PROBE_FIN_PAD_LOOP_KIB    the same number of s_nop issued from a 64-byte loop: issued, nothing more to fetch
+//   CRAG_PROBE_FIN_PAD_SKIP_KIB    the pad in the middle of the common path behind a branch no search takes (k < 0):
+//                                  code-object size and jump distance, nothing fetched for execution
+//   CRAG_PROBE_FIN_NO_FALLBACK     the selection role without the fallback role in its kernel (footprint; a search whose
+//                                  candidate list overflows gets no answer from such a build)
+//   CRAG_PROBE_FIN_TRACE           the FIN_T phase stamps (scripts/probes/fin_phase_trace.py needs this build)
+//   CRAG_PROBE_PREP_PAD_EXEC_KIB   straight-line pad at the start of prep_queries_kernel
+#ifndef CRAG_PROBE_FIN_PAD_EXEC_KIB
+#define CRAG_PROBE_FIN_PAD_EXEC_KIB 0
+#endif
+#ifndef CRAG_PROBE_FIN_PAD_LOOP_KIB
+#define CRAG_PROBE_FIN_PAD_LOOP_KIB 0
+#endif
+#ifndef CRAG_PROBE_FIN_PAD_SKIP_KIB
+#define CRAG_PROBE_FIN_PAD_SKIP_KIB 0
+#endif
+#ifndef CRAG_PROBE_PREP_PAD_EXEC_KIB
+#define CRAG_PROBE_PREP_PAD_EXEC_KIB 0
+#endif
+template <int KIB>
+__device__ __forceinline__ void probe_pad_exec() {
+    if constexpr (KIB > 0) asm volatile(".rept 256 * %0\n\ts_nop 0\n\t.endr" ::"n"(KIB));
+}
+template <int KIB>
+__device__ __forceinline__ void probe_pad_loop() {   // 16 trips per KiB, 16 s_nop a trip beside the loop's own instructions
+    if constexpr (KIB > 0) {
+#pragma unroll 1
+        for (int i = 0; i < KIB * 16; ++i) asm volatile(".rept 16\n\ts_nop 0\n\t.endr" ::: "memory");
+    }
+}
+template <int KIB>
+__device__ __forceinline__ void probe_pad_skip(int k) {   // (k >= 0 in every search: the pad is jumped over)
+    if constexpr (KIB > 0)
+        asm volatile("s_cmp_lt_i32 %0, 0\n\ts_cbranch_scc0 1f\n\t.rept 256 * %1\n\ts_nop 0\n\t.endr\n1:" ::"s"(k), "n"(KIB) : "scc");
+}
+
 // ---- K0: per query 1/||q||, the query in fp32 A-fragment order (raw) and fp16 A-fragment order (unit) --------
 // One 256-thread workgroup per padded query; thread t owns dims 4t .. 4t+3.  (The per-query prefilter state --
 // class maxima, candidate count -- is left zeroed by the selection kernel of the previous search; the overflow
 // word holds the sequence number of the search that overflowed and needs no reset.)
 __global__ __launch_bounds__(256) void prep_queries_kernel(PrepParams p) {
     __shared__ double sh[4];
+    probe_pad_exec<CRAG_PROBE_PREP_PAD_EXEC_KIB>();
     const int q = blockIdx.x, t = threadIdx.x;
     const f32x4 v = load_query_quad(p.queries, p.dim, q, p.nq, t);
     const float qinv = canonical_qinv(v, q < p.nq, sh);
@@ -2269,8 +2310,15 @@ __global__ __launch_bounds__(SCAN_THREADS) void finalize_fb_kernel(FinParams p) 
     __shared__ int s_last;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int R = p.rsplit;  // selection blocks per query (1, or 4 / 8 for large k: the exact rescoring is shared)
+    // (The kernel's text is laid out for the search that is asked for all day -- k <= 24, one block per query, a few
+    // dozen candidates: what such a block executes is one contiguous run of code, and everything else -- the fallback
+    // role, the radix select, the trim between rounds, the hand-off and gather of R > 1 -- is marked unlikely, so the
+    // compiler places it behind that run.  profiles/launch_weight_probe.json: what executed bytes cost a launch.)
     if ((int)blockIdx.x >= p.nq * R) {
-        if (__hip_atomic_load(p.flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != p.seq) return;
+#ifdef CRAG_PROBE_FIN_NO_FALLBACK
+        return;
+#else
+        if (__builtin_expect(__hip_atomic_load(p.flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != p.seq, 1)) return;
         const int b = (int)blockIdx.x - p.nq * R;
         scan_body<S, PS>(p.scan, b % p.scan.G, b / p.scan.G, U.slab);
         // every wave drains its own list stores, then the barrier; one lane releases them and draws a ticket
@@ -2294,12 +2342,20 @@ __global__ __launch_bounds__(SCAN_THREADS) void finalize_fb_kernel(FinParams p) 
         }
         if (threadIdx.x == 0) __hip_atomic_store(p.fb_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
+#endif
     }
-    // developer probe: timestamps (100 MHz) of the phases of query 0's selection blocks
+    probe_pad_exec<CRAG_PROBE_FIN_PAD_EXEC_KIB>();
+    probe_pad_loop<CRAG_PROBE_FIN_PAD_LOOP_KIB>();
+    // developer probe: timestamps (100 MHz) of the phases of query 0's selection blocks.  Compiled in only with
+    // -DCRAG_PROBE_FIN_TRACE: seven tests of p.trace and their stores are code every block would step over.
+#ifdef CRAG_PROBE_FIN_TRACE
 #define FIN_T(PH_)                                                                                               \
     do {                                                                                                         \
         if (p.trace && (int)blockIdx.x < R && threadIdx.x == 0) p.trace[((int)blockIdx.x % R) * 16 + (PH_)] = wall_clock64(); \
     } while (0)
+#else
+#define FIN_T(PH_) do { } while (0)
+#endif
     FIN_T(0);
     constexpr int NT = FIN_THREADS;
     auto &best = U.f.best;
@@ -2310,7 +2366,10 @@ __global__ __launch_bounds__(SCAN_THREADS) void finalize_fb_kernel(FinParams p) 
     auto &hist = U.f.hist;
     int &s_nbest = U.f.s_nbest, &s_nsurv = U.f.s_nsurv, &s_rescored = U.f.s_rescored;
     uint32_t &s_kth = U.f.s_kth;
-    const int q = (int)blockIdx.x / R, rpart = (int)blockIdx.x % R, tid = threadIdx.x;
+    // (R is 1, 4 or 8 -- crag_search_plan.h; the survivors' share below takes it for a power of two as well -- and a
+    // shift is three scalar instructions where the division by a run-time R is thirty, ahead of the first loads)
+    const int rshift = __builtin_ctz((unsigned)R);
+    const int q = (int)blockIdx.x >> rshift, rpart = (int)blockIdx.x & (R - 1), tid = threadIdx.x;
     // Everything the kernel needs first, in flight together (one memory round trip instead of a chain of four:
     // flag -> count -> candidates -> ...): the overflow flag, the candidate count, the first NT candidates (read
     // before the count is known -- the list has `cap` >= NT slots; the usual few hundred candidates are all among
@@ -2358,6 +2417,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void finalize_fb_kernel(FinParams p) 
         s_nbest = 0;
         s_rescored = 0;
         s_kth = 0u;
+        s_nsurv = 0;
     }
     __syncthreads();
     if (tid == 0 && R == 1) p.count[q] = 0u;
@@ -2366,7 +2426,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void finalize_fb_kernel(FinParams p) 
     // 1. (a lower bound on) the k-th largest approximate score among the candidates
     uint32_t thr_ord = 0u;
     if (C > k) {
-        if (C <= 64) {  // a few dozen candidates (k <= 24): rank by counting in one wave, one barrier
+        if (__builtin_expect(C <= 64, 1)) {  // a few dozen candidates (k <= 24): rank by counting in one wave, one barrier
             if (tid < C) {
                 const uint32_t mine = lcand[tid].x;
                 int rank = 0;
@@ -2466,13 +2526,16 @@ __global__ __launch_bounds__(SCAN_THREADS) void finalize_fb_kernel(FinParams p) 
         thr_ord = f2ord(ord2f(s_kth) - 2.f * PF_DELTA);
     }
     FIN_T(2);   // k-th approximate score known
+    probe_pad_skip<CRAG_PROBE_FIN_PAD_SKIP_KIB>(k);
 
     // 2. survivors -> exact scores, 8 lanes per row (64 rows per sweep), in rounds of FIN_ROUND candidates
     const int grp = tid >> 3, sub = tid & 7;  // lane `sub` = K slice (the scan's wave w)
     for (int r0 = 0; r0 < C; r0 += FIN_ROUND) {
         const int rn = (C - r0) < FIN_ROUND ? (C - r0) : FIN_ROUND;
-        if (tid == 0) s_nsurv = 0;
-        __syncthreads();
+        if (r0 > 0) {   // (the first round's zero was written ahead of the barriers above)
+            if (tid == 0) s_nsurv = 0;
+            __syncthreads();
+        }
         for (int e = tid; e < rn; e += NT) {
             const uint2 ce = in_lds ? lcand[e] : gcand[r0 + e];
             // (several blocks per query: block r rescores the candidates whose list position is r mod R)
@@ -2511,7 +2574,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void finalize_fb_kernel(FinParams p) 
         }
         __syncthreads();
         if (tid == 0) s_rescored += ns;
-        if (r0 + FIN_ROUND < C && s_nbest > k) {  // more rounds follow: keep only the running top-k
+        if (__builtin_expect(r0 + FIN_ROUND < C && s_nbest > k, 0)) {  // more rounds follow: keep only the running top-k
             const int B = s_nbest;
             uint64_t mine[(FIN_BEST + NT - 1) / NT];
             int64_t mine_id[(FIN_BEST + NT - 1) / NT];
@@ -2540,7 +2603,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void finalize_fb_kernel(FinParams p) 
     // 3. rank by counting among the exact keys
     int B = s_nbest;
     unsigned long long rescored_all = (unsigned long long)s_rescored;
-    if (R > 1) {
+    if (__builtin_expect(R > 1, 0)) {
         // this block's own best keys (at most k of them can be in the query's top-k; its share is rarely larger) ->
         // global scratch; the block of the query that finishes LAST gathers the R lists and ranks them.  Nobody waits
         // for anybody.
@@ -2642,10 +2705,12 @@ __global__ __launch_bounds__(SCAN_THREADS) void finalize_fb_kernel(FinParams p) 
         }
     }
     FIN_T(6);
+#ifdef CRAG_PROBE_FIN_TRACE
     if (p.trace && (int)blockIdx.x < R && threadIdx.x == 0) {
         p.trace[rpart * 16 + 8] = (unsigned long long)C;
         p.trace[rpart * 16 + 9] = (unsigned long long)s_rescored;
     }
+#endif
 #undef FIN_T
 }
 

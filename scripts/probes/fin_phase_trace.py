@@ -1,5 +1,9 @@
 """Developer probe: where a selection block of finalize_fb_kernel spends its time (CRAG_PHASE_TRACE=1: device timestamps
-of query 0's selection blocks at the phase boundaries, 100 MHz)."""
+of query 0's selection blocks at the phase boundaries, 100 MHz).
+
+Needs a library built with the stamps compiled in -- the default build leaves them out (crag_search.hip, FIN_T):
+   make -C cadence_rag_amd/csrc clean all PROBE=-DCRAG_PROBE_FIN_TRACE
+With the default library every line reads as empty (no block ever writes a stamp)."""
 import os, sys, torch
 os.environ["CRAG_PHASE_TRACE"] = "1"
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
