@@ -1,6 +1,7 @@
 """BM25 lane on the GPU (crag_bm25_lane_host / Bm25Index) against tests/bm25_oracle.py.
 
-Tolerance (derived, not measured): |dscore| <= 2 * (T + 9) * 2^-24 * score, T = distinct known terms of the query; ids
+Every result is also compared exactly (ids, counts, score bits) with tests/bm25_replay.py, the fp32 restatement of the
+header's formula.  Tolerance against the fp64 oracle (derived, not measured): |dscore| <= 2 * (T + 9) * 2^-24 * score, T = distinct known terms of the query; ids
 equal the oracle's except for permutations inside a window of that same relative width; exact ties (identical tf..., dl)
 come out in ascending id order with identical bits.  See bm25_oracle.tolerance / assert_matches."""
 import ctypes
@@ -10,6 +11,7 @@ import pytest
 import torch
 
 from bm25_oracle import Bm25Oracle, assert_matches
+from bm25_replay import assert_equals_replay, replay_index
 from cadence_rag_amd import _native
 from cadence_rag_amd import retrieve as rt
 from cadence_rag_amd.bm25 import RANGE_ROWS, Bm25Index
@@ -24,7 +26,9 @@ def host(t):
 
 
 def check(index, oracle, queries, k, eligible=None, **kw):
-    """eligible: None, bool [N] (shared) or bool [nq, N]."""
+    """eligible: None, bool [N] (shared) or bool [nq, N].  Two legs: the fp64 oracle inside its tolerance window (the
+    check of the formula), then ids, counts and score bits equal to the fp32 replay (the check of the header's contract:
+    one rounding per operation, terms in ascending id) -- every query, no window."""
     mask = stride = None
     if eligible is not None:
         packed = DenseIndex.pack_mask(eligible)
@@ -36,6 +40,7 @@ def check(index, oracle, queries, k, eligible=None, **kw):
     for q, text in enumerate(queries):
         el = None if eligible is None else (eligible[q] if np.ndim(eligible) == 2 else eligible)
         worst = max(worst, assert_matches(oracle, text, k, ids[q], sc[q], ct[q], el))
+    assert_equals_replay(replay_index(index, *index.query_terms(queries), k, eligible), ids, sc, ct, f"k={k}")
     return ids, sc, ct, worst
 
 
