@@ -29,6 +29,8 @@ CRAG_FACET_MAX_QUERIES = 64
 CRAG_FACET_MAX_NAMESPACES = 16
 CRAG_FACET_MAX_TOP = 64
 CRAG_E2BIG = -5
+CRAG_EINVAL = -1
+CRAG_NGRAM_TILE = 4096
 CRAG_DECODE_MAX_SEQS = 8
 CRAG_DECODE_MAX_ROWS = 8
 CRAG_DECODE_SPLIT = 128
@@ -76,6 +78,10 @@ SIGNATURES = {
     "crag_bm25_scratch_bytes": (_c.c_int64, [_c.c_int64, _c.c_int, _c.c_int]),
     "crag_bm25_lane_host": (_c.c_int, [_P, _P, _P, _P, _P, _c.c_int64, _c.c_int64, _c.c_float, _P, _P, _P, _c.c_int, _c.c_int,
                                        _P, _c.c_int64, _P, _P, _c.c_int64, _P, _P, _P, _P]),
+    "crag_ngram_scratch_bytes": (_c.c_int64, [_c.c_int64, _c.c_int64]),
+    "crag_ngram_extract": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _P, _c.c_int64, _P]),
+    "crag_ngram_heads": (_c.c_int, [_P, _P, _c.c_int64, _P, _P]),
+    "crag_ngram_emit": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _P, _P, _P, _c.c_int64, _P]),
     "crag_filter_masks_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P, _P, _c.c_int, _P, _P, _c.c_int64, _P]),
     "crag_attr_masks_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int64, _P, _P,
                                         _c.c_int64, _P]),

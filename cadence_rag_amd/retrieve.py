@@ -811,6 +811,35 @@ class DenseTable:
             return lane
         return self.build_bm25_lane(lane.text_column)
 
+    def build_ngram_lane(self, text_column: str):
+        """GPU character-trigram lane (cadence_rag_amd.ngram.NgramIndex: the reference's `pdb.ngram(3,3)` alias of the
+        column, a self-defined rule) over this table's `text_column`, its postings built on the device.  Row i <->
+        position i; the lane remembers the column and the table generation, as the BM25 lane does."""
+        import torch
+
+        from .ngram import NgramIndex
+        if text_column not in self.columns and len(self):
+            raise ValueError(f"{self.name} has no column {text_column!r}")
+        lane = NgramIndex(self.columns.get(text_column, []), np.asarray(self.columns.get(self.id_field, []), dtype=np.int64),
+                          torch.device("cuda", self.index.device))
+        lane.text_column = text_column
+        lane.table_generation = self.generation
+        return lane
+
+    def sync_ngram_lane(self, lane):
+        """`sync_bm25_lane` for the trigram lane: unchanged when current, grown with `extend` when rows were appended
+        behind the ones it holds, rebuilt when rows moved or left."""
+        if getattr(lane, "table_generation", None) == self.generation and len(lane) == len(self):
+            return lane
+        ids = np.asarray(self.columns.get(self.id_field, []), dtype=np.int64)
+        held = len(lane)
+        if held <= ids.size and np.array_equal(ids[:held], lane.ids):
+            if held < ids.size:
+                lane.extend(self.columns[lane.text_column][held:], ids[held:])
+            lane.table_generation = self.generation
+            return lane
+        return self.build_ngram_lane(lane.text_column)
+
     def dedupe(self, ids, threshold: float) -> List[Tuple[Optional[int], Optional[float]]]:
         """Greedy near-duplicate suppression of one ranked list of row ids (best first, at most 256) over the stored
         vectors (DenseIndex.dedupe): per input id (slot of the kept, higher-ranked id that is at least `threshold`
@@ -946,6 +975,10 @@ class RetrieveBackend:
     def resolve_call_ids(self, filters): return None
     def fetch_chunks_bm25(self, query, filters, call_ids, limit): return []
     def fetch_artifacts_bm25(self, query, filters, call_ids, limit): return []
+    # the character-trigram field of the lexical lanes: None = this backend has no such lane (it then does not appear
+    # anywhere in the response), a list = the lane ran
+    def fetch_chunks_ngram(self, query, filters, call_ids, limit): return None
+    def fetch_artifacts_ngram(self, query, filters, call_ids, limit): return None
     def fetch_chunks_tech(self, tokens, filters, call_ids, limit): return []
     def fetch_artifacts_tech(self, tokens, filters, call_ids, limit): return []
     def estimate_dense_candidates(self, table_name, filters, call_ids): return 0
@@ -968,13 +1001,17 @@ class GpuRetrieveBackend(RetrieveBackend):
     (cadence_rag_amd.fusion) when attached.  BM25 lanes: `bm25_chunks` / `bm25_artifacts` are either callables
     (query, filters, call_ids, limit) -> rows -- pg_search's own rows as an input, as they are to _rrf_merge -- or
     native lanes (cadence_rag_amd.bm25.Bm25Index from DenseTable.build_bm25_lane: a self-defined BM25, not parity
-    with pg_search, whose arithmetic is not in the reference repository)."""
+    with pg_search, whose arithmetic is not in the reference repository).  Trigram lanes, off unless given:
+    `ngram_chunks` / `ngram_artifacts` are callables of the same shape or native lanes (cadence_rag_amd.ngram.NgramIndex
+    from DenseTable.build_ngram_lane); a side with one adds the lane `bm25_ngram` behind `bm25`."""
 
     def __init__(self, chunks: DenseTable, artifact_chunks: DenseTable, *, calls: Sequence[Dict[str, Any]] = (),
-                 bm25_chunks=None, bm25_artifacts=None, tech_chunks=None, tech_artifacts=None) -> None:
+                 bm25_chunks=None, bm25_artifacts=None, tech_chunks=None, tech_artifacts=None,
+                 ngram_chunks=None, ngram_artifacts=None) -> None:
         self.tables = {"chunks": chunks, "artifact_chunks": artifact_chunks}
         self.calls = list(calls)
         self._bm25 = {"chunks": bm25_chunks, "artifact_chunks": bm25_artifacts}
+        self._ngram = {"chunks": ngram_chunks, "artifact_chunks": ngram_artifacts}
         self._tech = {"chunks": tech_chunks, "artifact_chunks": tech_artifacts}
 
     def resolve_call_ids(self, filters):
@@ -992,16 +1029,18 @@ class GpuRetrieveBackend(RetrieveBackend):
         mask = table.filter_mask(filters, call_ids)
         return None if mask is None else torch.from_numpy(DenseIndex.pack_mask(mask)).to(lane.device)
 
-    def _bm25_rows(self, name, select, query, filters, call_ids, limit):
-        """retrieve.py:123-180: the SELECTed columns + `score`, best first."""
-        fn, table = self._bm25[name], self.tables[name]
+    def _bm25_rows(self, name, select, query, filters, call_ids, limit, field="bm25"):
+        """retrieve.py:123-180: the SELECTed columns + `score`, best first.  field: "bm25", the word lane, or "ngram",
+        the trigram lane (same rows, same limit, same mask; None when the side has no such lane)."""
+        lanes, sync = (self._bm25, "sync_bm25_lane") if field == "bm25" else (self._ngram, "sync_ngram_lane")
+        fn, table = lanes[name], self.tables[name]
         if fn is None:
-            return []
+            return [] if field == "bm25" else None
         if callable(fn):
             return list(fn(query, filters, call_ids, limit))
         if len(table) == 0 or int(limit) <= 0:
             return []
-        lane = self._bm25[name] = table.sync_bm25_lane(fn)
+        lane = lanes[name] = getattr(table, sync)(fn)
         d_mask = self._lane_mask(table, lane, filters, call_ids)
         ids, scores, counts = lane.search([query], min(int(limit), _native_max_k()), row_mask=d_mask, mask_stride=0)
         n = int(counts[0])
@@ -1019,6 +1058,12 @@ class GpuRetrieveBackend(RetrieveBackend):
 
     def fetch_artifacts_bm25(self, query, filters, call_ids, limit):
         return self._bm25_rows("artifact_chunks", ARTIFACT_SELECT, query, filters, call_ids, limit)
+
+    def fetch_chunks_ngram(self, query, filters, call_ids, limit):
+        return self._bm25_rows("chunks", CHUNK_SELECT, query, filters, call_ids, limit, field="ngram")
+
+    def fetch_artifacts_ngram(self, query, filters, call_ids, limit):
+        return self._bm25_rows("artifact_chunks", ARTIFACT_SELECT, query, filters, call_ids, limit, field="ngram")
 
     def _tech_rows(self, name, select, tokens, filters, call_ids, limit):
         lane, table = self._tech[name], self.tables[name]
@@ -1262,13 +1307,18 @@ class _DedupeState:
 
 def _gather_lanes(be: "RetrieveBackend", query: str, tokens: List[str], filters, dense: _DenseState
                   ) -> Dict[str, Dict[str, Sequence[Dict[str, Any]]]]:
-    """table -> {lane name -> rows}, lanes in fusion order (bm25, tech_tokens, dense)."""
+    """table -> {lane name -> rows}, lanes in fusion order (bm25, [bm25_ngram,] tech_tokens, dense): the trigram lane
+    exists only where the backend returns a list for it."""
     call_ids = be.resolve_call_ids(filters)
+    ngram = {"chunks": getattr(be, "fetch_chunks_ngram", None), "artifact_chunks": getattr(be, "fetch_artifacts_ngram", None)}
     fetch = {"chunks": (be.fetch_chunks_bm25, be.fetch_chunks_tech, be.fetch_chunks_dense),
              "artifact_chunks": (be.fetch_artifacts_bm25, be.fetch_artifacts_tech, be.fetch_artifacts_dense)}
     lanes: Dict[str, Dict[str, Sequence[Dict[str, Any]]]] = {s.table: {} for s in _QUERY_ORDER}
     for s in _QUERY_ORDER:
         lanes[s.table]["bm25"] = fetch[s.table][0](query, filters, call_ids, s.bm25_topk)
+        rows = ngram[s.table](query, filters, call_ids, s.bm25_topk) if ngram[s.table] is not None else None
+        if rows is not None:
+            lanes[s.table]["bm25_ngram"] = rows
     for s in _QUERY_ORDER:
         lanes[s.table]["tech_tokens"] = fetch[s.table][1](tokens, filters, call_ids, DEFAULT_TECH_TOPK)
     if dense.on and dense.literal is not None:
@@ -1297,7 +1347,7 @@ def _debug_section(lanes, dense: _DenseState) -> Dict[str, Any]:
 
 
 def _retrieval_notes(tokens: List[str], dense: _DenseState, rerank: Optional[_RerankState] = None,
-                     dedupe: Optional[_DedupeState] = None) -> Dict[str, Any]:
+                     dedupe: Optional[_DedupeState] = None, lanes=None) -> Dict[str, Any]:
     chunks, artifacts = _BY_TABLE["chunks"], _BY_TABLE["artifact_chunks"]
     notes = {
         "planner": dense.planner,
@@ -1323,6 +1373,8 @@ def _retrieval_notes(tokens: List[str], dense: _DenseState, rerank: Optional[_Re
     if dedupe is not None and dedupe.on:   # likewise
         notes["dedupe_cosine"] = dedupe.cosine
         notes["dedupe_dropped"] = dict(dedupe.dropped)
+    if lanes is not None and any("bm25_ngram" in by_name for by_name in lanes.values()):   # likewise: the lane ran
+        notes["lanes"] = {"bm25": True, "bm25_ngram": True, "tech_tokens": True, "dense": dense.on}
     if _dense_per_call_cap():   # likewise
         notes["dense_per_call_cap"] = _dense_per_call_cap()
     if _dense_mmr() is not None:   # likewise
@@ -1379,7 +1431,7 @@ def retrieve_evidence(payload: RetrieveRequest, backend: Optional[RetrieveBacken
             cap = None if s.list_cap is None else min(s.list_cap, budget.max_evidence_items)
             packed[s.out] = _pack(fused[s.table], s, purse, cap)
         response = {**head, "intent": payload.intent, "budget": budget.model_dump(), **packed,
-                    "notes": {"retrieval": _retrieval_notes(tokens, dense, rerank, dedupe)}}
+                    "notes": {"retrieval": _retrieval_notes(tokens, dense, rerank, dedupe, lanes)}}
     response.update(facets)
     if payload.debug:
         response["debug"] = _debug_section(lanes, dense)

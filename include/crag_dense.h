@@ -410,6 +410,57 @@ int crag_bm25_lane_host(const int64_t *d_post_ptr, const int32_t *d_post_pos, co
                         int64_t scratch_bytes, int64_t *d_out_ids, float *d_out_scores, int32_t *d_out_counts,
                         void *stream);
 
+/* Character-trigram field of the BM25 lane: the inverted CSR crag_bm25_lane_host scores, built on the device from the
+ * rows' bytes (cadence_rag_amd.ngram.NgramIndex drives it).  Stands in for the reference's second index over every
+ * lexical column, the `pdb.ngram(3,3)` aliases of alembic/versions/0005_add_bm25_ngram.py and 0006_add_artifact_chunks.py
+ * ("BM25 ngram robustness (ASR noise)", PHASED_PLAN.md:113,379).  NOT parity with Tantivy's ngram tokenizer: the rule is
+ * this tree's own (DESIGN.md 4.7b lists the departures).  It works on the BYTES of one row:
+ *   Decode.  A lead byte 0xxxxxxx / 110xxxxx / 1110xxxx / 11110xxx starts a sequence of 1 / 2 / 3 / 4 bytes; the following
+ *     bytes must be 10xxxxxx and lie inside the row; the value is what the payload bits give (overlong forms and the
+ *     surrogate range are NOT checked); a 4-byte value above 0x10FFFF is malformed.  A malformed or cut-off lead, any
+ *     other byte (0xF8-0xFF) and a continuation byte no valid lead consumed are each one separator of one byte, and
+ *     decoding resumes at the next byte.
+ *   Fold and classify.  'A'-'Z' become 'a'-'z' (no other case mapping).  A code point is a gram character if it is an
+ *     ASCII letter or digit or if it is >= 0x80; every other ASCII code point is a separator.
+ *   Grams.  Every three consecutive gram characters form one gram, one per start position, overlapping; runs of one or two
+ *     characters yield nothing.   key = cp0 << 42 | cp1 << 21 | cp2: exact, below 2^63 - 1, no hashing.
+ *   Row statistics.  dl = the row's number of grams; tf = occurrences of a gram in the row, stored saturating at 65 535.
+ *   Term ids.  The term id of a key is its rank among the distinct keys of the index, ascending.
+ * The build is three calls around a sort and a prefix sum that the CALLER runs with any correct routine (the result is
+ * integers, fully determined by the rule):
+ *   1. crag_ngram_extract: one slot per byte position p of the text, d_slot_keys[p] = the key of the gram that starts at p
+ *      or CRAG_NGRAM_NO_KEY (above every key), d_slot_rows[p] = the row of p; d_doc_len [n_rows] is zeroed and counted.
+ *      The number of grams is the sum of d_doc_len.
+ *   -- the caller sorts the n_bytes slots by key, STABLE (or by (key, row)): the first n_grams sorted slots are the grams,
+ *      rows ascending inside a key --
+ *   2. crag_ngram_heads: d_flags[i] = (sorted gram i opens a (key, row) run) + 2^32 * (it opens a key run).
+ *   -- the caller takes the inclusive prefix sum d_scan of d_flags; its last element is nnz + 2^32 * n_terms --
+ *   3. crag_ngram_emit: d_keys [n_terms] ascending, d_post_ptr [n_terms + 1], d_post_pos [nnz] row positions ascending
+ *      inside a term, d_post_tf [nnz] -- with d_doc_len the arrays of crag_bm25_lane_host.  n_grams = 0 writes
+ *      d_post_ptr[0] = 0 alone.
+ *   d_text      [n_bytes] the rows' bytes concatenated, 16-byte aligned;  d_text_ptr [n_rows + 1] int64, row r is
+ *               [d_text_ptr[r], d_text_ptr[r + 1]), rows may be empty
+ *   d_scratch   crag_ngram_scratch_bytes(n_bytes, n_rows) bytes, 8-byte aligned, owned by the caller; calls 1 and 3 use it
+ * Memory the caller sizes: 12 bytes of slots per byte of text, 8 + 4 per gram sorted, 8 per gram of flags (the scan may
+ * overwrite them), 4 per byte of scratch.  The kernels read the text in tiles of CRAG_NGRAM_TILE bytes; the result does
+ * not depend on where the tiles' edges fall.  Nothing is allocated by any of the calls.  Everything is enqueued on
+ * `stream`; crag_ngram_extract alone waits for the stream once, for the check of d_text_ptr, before it touches the text.
+ * CRAG_E2BIG: n_bytes > 2^31 - 1 (checked first, from the argument alone) -- a larger corpus is split by rows into
+ * several indexes by the caller.  CRAG_EINVAL: d_text_ptr not ascending from 0 to n_bytes, NULL / misaligned pointer,
+ * n_rows >= 2^31, scratch too small, counts that cannot be (n_terms <= nnz <= n_grams).  On an error nothing was written
+ * but the scratch.  crag_ngram_scratch_bytes returns the same negative codes for sizes it does not take. */
+#define CRAG_NGRAM_TILE 4096
+#define CRAG_NGRAM_NO_KEY INT64_MAX
+int64_t crag_ngram_scratch_bytes(int64_t n_bytes, int64_t n_rows);
+int crag_ngram_extract(const uint8_t *d_text, int64_t n_bytes, const int64_t *d_text_ptr, int64_t n_rows,
+                       int64_t *d_slot_keys, int32_t *d_slot_rows, int32_t *d_doc_len, void *d_scratch,
+                       int64_t scratch_bytes, void *stream);
+int crag_ngram_heads(const int64_t *d_sorted_keys, const int32_t *d_sorted_rows, int64_t n_grams, int64_t *d_flags,
+                     void *stream);
+int crag_ngram_emit(const int64_t *d_sorted_keys, const int32_t *d_sorted_rows, const int64_t *d_scan, int64_t n_grams,
+                    int64_t n_terms, int64_t nnz, int64_t *d_keys, int64_t *d_post_ptr, int32_t *d_post_pos,
+                    uint16_t *d_post_tf, void *d_scratch, int64_t scratch_bytes, void *stream);
+
 /* Filter row masks for up to 64 queries, built on the device from device-resident columns: the producer of the
  * `row_mask` every lane above takes (crag_index_search*, crag_index_count_eligible, crag_tech_lane*, crag_bm25_lane_host).
  * Replaces: _build_filter_clause (retrieve.py:93-120) -- call_started_at >= :date_from, <= :date_to, call_id = ANY(:ids),
