@@ -78,6 +78,8 @@ SIGNATURES = {
     "crag_bm25_scratch_bytes": (_c.c_int64, [_c.c_int64, _c.c_int, _c.c_int]),
     "crag_bm25_lane_host": (_c.c_int, [_P, _P, _P, _P, _P, _c.c_int64, _c.c_int64, _c.c_float, _P, _P, _P, _c.c_int, _c.c_int,
                                        _P, _c.c_int64, _P, _P, _c.c_int64, _P, _P, _P, _P]),
+    "crag_bm25_clause_masks_host": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _P, _P, _c.c_int, _P,
+                                               _c.c_int64, _P, _P, _c.c_int64, _P]),
     "crag_ngram_scratch_bytes": (_c.c_int64, [_c.c_int64, _c.c_int64]),
     "crag_ngram_extract": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _P, _c.c_int64, _P]),
     "crag_ngram_heads": (_c.c_int, [_P, _P, _c.c_int64, _P, _P]),

@@ -13,7 +13,8 @@ from __future__ import annotations
 
 import ctypes
 import re
-from typing import Dict, List, Optional, Sequence
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -25,6 +26,10 @@ RANGE_ROWS = 16384        # row positions per workgroup of the scoring kernel (c
 MAX_QUERIES = 64
 MAX_TOKEN_BYTES = 255
 TF_MAX = 65535            # tf is stored in 16 bits, saturating
+WHERE_MAX = 65535         # token positions at or above this are not indexed (post_where is 16 bits wide)
+MAX_CLAUSES = 16          # constraint clauses per query (include/crag_dense.h CRAG_BM25_MAX_CLAUSES)
+MAX_PHRASE_TERMS = 8      # terms per phrase (CRAG_BM25_MAX_PHRASE)
+REQ_TERM, EXC_TERM, REQ_PHRASE, EXC_PHRASE, MATCH_NOTHING = 0, 1, 2, 3, 4   # clause kinds of the C ABI
 
 # [^\W_] is exactly str.isalnum() per character (the re module's \w is "isalnum() or '_'")
 _RUN = re.compile(r"[^\W_]+")
@@ -41,6 +46,66 @@ def tokenize(text: str) -> List[str]:
     return out
 
 
+class QuerySyntaxError(ValueError):
+    """A query over the limits of the clause syntax (16 constraint clauses, 8 terms per phrase)."""
+
+
+@dataclass(frozen=True)
+class ParsedQuery:
+    """A query string read by the rule of DESIGN.md 4.7c (include/crag_dense.h states it).
+      clauses  the constraint clauses in item order: (kind, tokens), kind one of REQ_TERM, EXC_TERM (one token each),
+               REQ_PHRASE, EXC_PHRASE (two to eight tokens, in phrase order)
+      bag      the scored tokens in item order: those of every non-excluded item (optional and required terms, the
+               members of required phrases)
+      text     the non-excluded items' text joined by single spaces, operators and quotes removed: what a lane that
+               applies no clauses (the trigram field) is given"""
+    clauses: Tuple[Tuple[int, Tuple[str, ...]], ...]
+    bag: Tuple[str, ...]
+    text: str
+
+    @property
+    def has_constraints(self) -> bool:
+        return bool(self.clauses)
+
+
+# one item: an optional prefix where no text stands in front of it, then a quoted run (the closing quote may be missing)
+# or a run without whitespace and quotes.  A lone prefix fails the first reading and is read as (tokenless) text
+_ITEM = re.compile(r'(?:(?<!\S)([+-]))?(?:"([^"]*)"?|([^\s"]+))')
+
+
+def parse_query(text: str) -> ParsedQuery:
+    """Items are separated by whitespace outside double quotes; `"` opens a quoted item (it also ends an unquoted one),
+    an unclosed quote runs to the end.  An item may carry one prefix, `+` or `-`, directly in front of it, at the start
+    of the string or after whitespace; anywhere else the character is text.  Every item's text goes through `tokenize`;
+    an item without tokens is dropped.  Unquoted: every token is a term of the item's kind (`+` required, `-` excluded,
+    none optional).  Quoted: one token is a term, more are a phrase, required unless prefixed `-`.  Nothing else is
+    syntax.  Raises QuerySyntaxError over 16 constraint clauses or 8 terms in a phrase."""
+    clauses: List[Tuple[int, Tuple[str, ...]]] = []
+    bag: List[str] = []
+    kept: List[str] = []
+    for prefix, inside, bare in _ITEM.findall(text or ""):
+        quoted = not bare           # (a bare item is never empty; a quoted one may be)
+        raw = inside if quoted else bare
+        toks = tokenize(raw)
+        if not toks:
+            continue
+        excluded = prefix == "-"
+        if quoted and len(toks) > 1:
+            if len(toks) > MAX_PHRASE_TERMS:
+                raise QuerySyntaxError(f"a phrase holds at most {MAX_PHRASE_TERMS} terms ({len(toks)} given)")
+            clauses.append((EXC_PHRASE if excluded else REQ_PHRASE, tuple(toks)))
+        elif excluded:
+            clauses.extend((EXC_TERM, (tok,)) for tok in toks)
+        elif quoted or prefix == "+":
+            clauses.extend((REQ_TERM, (tok,)) for tok in toks)
+        if not excluded:
+            bag.extend(toks)
+            kept.append(raw.strip())
+        if len(clauses) > MAX_CLAUSES:
+            raise QuerySyntaxError(f"a query holds at most {MAX_CLAUSES} constraint clauses")
+    return ParsedQuery(tuple(clauses), tuple(bag), " ".join(kept))
+
+
 class Bm25Index:
     """Vocabulary and per-row (term id, tf) pairs on the host, the inverted CSR on the device.
 
@@ -48,11 +113,19 @@ class Bm25Index:
       vocab {token: term id}, ids handed out in order of first appearance
       row_ptr [N + 1] int64, row_terms [nnz] int32 (ascending inside a row), row_tf [nnz] int64, doc_len [N] int32
     Device: post_ptr [V + 1] int64, post_pos [nnz] int32 (row positions, ascending inside a term), post_tf [nnz] uint16,
-      doc_len [N] int32, ids [N] int64."""
+      doc_len [N] int32, ids [N] int64.
+    With positions=True (what phrase clauses need) the host also keeps every (row, term) pair's token
+    positions, ascending -- pair_off [nnz + 1] int64 into pair_where uint16, in row order; positions at or above 65 535
+    are not indexed -- and the device their permutation into posting order: post_off [nnz + 1] int64, post_where uint16:
+    2 bytes per token and 8 per posting beside the 6 per posting of the lane."""
 
-    def __init__(self, texts: Sequence[str], ids: Sequence[int], device) -> None:
+    def __init__(self, texts: Sequence[str], ids: Sequence[int], device, positions: bool = False) -> None:
         import torch
         self.device = torch.device(device) if not isinstance(device, torch.device) else device
+        self.positions = bool(positions)
+        self.pair_off = np.zeros(1, dtype=np.int64)
+        self.pair_where = np.empty(0, dtype=np.uint16)
+        self._clause_masks: dict = {}   # per stream: the clause masks of a full batch
         self.vocab: Dict[str, int] = {}
         self.row_ptr = np.zeros(1, dtype=np.int64)
         self.row_terms = np.empty(0, dtype=np.int32)
@@ -80,19 +153,33 @@ class Bm25Index:
         tfs: List[int] = []
         lens = np.empty(len(texts), dtype=np.int64)
         dls = np.empty(len(texts), dtype=np.int32)
+        where: List[int] = []
+        where_lens: List[int] = []
         for i, text in enumerate(texts):
             counts: Dict[int, int] = {}
+            at: Dict[int, List[int]] = {}
             toks = tokenize(text)
-            for tok in toks:
+            for p, tok in enumerate(toks):
                 t = vocab.get(tok)
                 if t is None:
                     t = vocab[tok] = len(vocab)
                 counts[t] = counts.get(t, 0) + 1
+                if self.positions and p < WHERE_MAX:
+                    at.setdefault(t, []).append(p)
             row = sorted(counts.items())
             terms.extend(t for t, _ in row)
             tfs.extend(c for _, c in row)
             lens[i] = len(row)
             dls[i] = len(toks)
+            if self.positions:
+                for t, _ in row:
+                    ps = at.get(t, ())
+                    where.extend(ps)
+                    where_lens.append(len(ps))
+        if self.positions:
+            self.pair_off = np.concatenate([self.pair_off, self.pair_off[-1] +
+                                            np.cumsum(np.asarray(where_lens, dtype=np.int64))])
+            self.pair_where = np.concatenate([self.pair_where, np.asarray(where, dtype=np.uint16)])
         self.row_ptr = np.concatenate([self.row_ptr, self.row_ptr[-1] + np.cumsum(lens)])
         self.row_terms = np.concatenate([self.row_terms, np.asarray(terms, dtype=np.int32)])
         self.row_tf = np.concatenate([self.row_tf, np.asarray(tfs, dtype=np.int64)])
@@ -100,12 +187,22 @@ class Bm25Index:
         self.ids = np.concatenate([self.ids, new_ids])
 
     @classmethod
-    def from_arrays(cls, row_ptr, row_terms, row_tf, n_terms: int, ids, device, vocab: Optional[Dict[str, int]] = None
-                    ) -> "Bm25Index":
+    def from_arrays(cls, row_ptr, row_terms, row_tf, n_terms: int, ids, device, vocab: Optional[Dict[str, int]] = None,
+                    pair_off=None, pair_where=None) -> "Bm25Index":
         """An index over rows that are (term id, tf) pairs already (a synthetic corpus, or rows tokenised elsewhere):
         row_ptr [N + 1], row_terms ascending inside a row.  `vocab` maps tokens to term ids; without one the tokens of
-        a query are the decimal term ids."""
+        a query are the decimal term ids.  pair_off [nnz + 1] / pair_where: the token positions of every (row, term)
+        pair, flat, in row order, ascending inside a pair (both or neither; with them the index has positions)."""
         self = cls([], [], device)
+        if (pair_off is None) != (pair_where is None):
+            raise ValueError("pair_off and pair_where come together")
+        if pair_off is not None:
+            self.positions = True
+            self.pair_off = np.asarray(pair_off, dtype=np.int64).reshape(-1)
+            self.pair_where = np.asarray(pair_where, dtype=np.uint16).reshape(-1)
+            if self.pair_off.size != np.asarray(row_terms).size + 1 or self.pair_off[0] != 0 or \
+                    np.any(np.diff(self.pair_off) < 0) or self.pair_off[-1] != self.pair_where.size:
+                raise ValueError("pair_off must ascend from 0 to len(pair_where) with one entry per (row, term) pair + 1")
         self.row_ptr = np.asarray(row_ptr, dtype=np.int64)
         self.row_terms = np.asarray(row_terms, dtype=np.int32)
         self.row_tf = np.asarray(row_tf, dtype=np.int64)
@@ -129,6 +226,18 @@ class Bm25Index:
         np.cumsum(np.bincount(self.row_terms, minlength=v), out=post_ptr[1:])
         return post_ptr, rows[order], np.minimum(self.row_tf[order], TF_MAX).astype(np.uint16)
 
+    def host_positions(self):
+        """The token positions in posting order (the stable permutation of `host_csr`): post_off [nnz + 1] int64,
+        post_where uint16 -- posting j holds its term at post_where[post_off[j] : post_off[j + 1]], ascending."""
+        if not self.positions:
+            raise ValueError("this index was built without positions")
+        order = np.argsort(self.row_terms, kind="stable")
+        lens = np.diff(self.pair_off)[order]
+        post_off = np.zeros(order.size + 1, dtype=np.int64)
+        np.cumsum(lens, out=post_off[1:])
+        src = np.repeat(self.pair_off[:-1][order] - post_off[:-1], lens) + np.arange(post_off[-1], dtype=np.int64)
+        return post_off, self.pair_where[src]
+
     def _upload(self) -> None:
         import torch
         post_ptr, post_pos, post_tf = self.host_csr()
@@ -146,7 +255,12 @@ class Bm25Index:
         self.d_post_ptr, self.d_post_pos = dev(post_ptr), dev(post_pos)
         self.d_post_tf = dev(post_tf, np.int16)                  # (bits of the uint16 values)
         self.d_doc_len, self.d_ids = dev(self.doc_len), dev(self.ids)
+        self.d_post_off = self.d_post_where = None
+        if self.positions:
+            post_off, post_where = self.host_positions()
+            self.d_post_off, self.d_post_where = dev(post_off), dev(post_where, np.int16)   # (bits of the uint16 values)
         self._scratch = {}
+        self._clause_masks = {}
 
     def extend(self, texts: Sequence[str], ids: Sequence[int]) -> None:
         """Rows appended at the end (what the backfill does): only the new rows are tokenised; the device CSR is rebuilt
@@ -225,6 +339,65 @@ class Bm25Index:
             raise ValueError("the BM25 lane takes at most 64 queries per call")
         return self.search_terms(*self.query_terms(query_texts), k, row_mask=row_mask, mask_stride=mask_stride,
                                  stream=stream)
+
+    def clause_arrays(self, parsed_list: Sequence[ParsedQuery]):
+        """The batch's constraint clauses as the host arrays of crag_bm25_clause_masks_host: c_ptr [nq + 1], c_kind,
+        ct_ptr [n_clauses + 1], ct_terms (all int32).  An unknown token turns a required clause into kind 4 ("matches
+        nothing") and drops an excluded one.  A phrase clause on an index without positions raises ValueError."""
+        c_ptr = np.zeros(len(parsed_list) + 1, dtype=np.int32)
+        kinds: List[int] = []
+        ct_ptr: List[int] = [0]
+        ct_terms: List[int] = []
+        get = self.vocab.get
+        for q, parsed in enumerate(parsed_list):
+            for kind, toks in parsed.clauses:
+                if kind in (REQ_PHRASE, EXC_PHRASE) and not self.positions:
+                    raise ValueError("a phrase clause needs an index built with positions=True")
+                ids = [get(tok) for tok in toks]
+                if any(t is None for t in ids):
+                    if kind in (EXC_TERM, EXC_PHRASE):
+                        continue
+                    kind, ids = MATCH_NOTHING, []
+                kinds.append(kind)
+                ct_terms.extend(ids)
+                ct_ptr.append(len(ct_terms))
+            c_ptr[q + 1] = len(kinds)
+        return (c_ptr, np.asarray(kinds, dtype=np.int32), np.asarray(ct_ptr, dtype=np.int32),
+                np.asarray(ct_terms, dtype=np.int32))
+
+    def search_query(self, query_texts: Sequence[str], k: int, row_mask=None, mask_stride: int = 0, stream: int = 0):
+        """`search` for queries in the clause syntax of `parse_query` (+required, -excluded, "quoted phrase"): the rows
+        that pass every clause and the mask, ranked by the BM25 score of the query's non-excluded tokens.  A batch
+        without any constraint IS `search` (same calls, same bits).  Otherwise one launch turns the clauses into a row
+        mask per query (crag_bm25_clause_masks_host, into a buffer this stream keeps) and `search_terms` scores under it.
+        Raises QuerySyntaxError for a query over the limits, ValueError for a phrase on an index without positions."""
+        import torch
+
+        from .fusion import _on_stream
+        if len(query_texts) > MAX_QUERIES:
+            raise ValueError("the BM25 lane takes at most 64 queries per call")
+        parsed = [parse_query(text) for text in query_texts]
+        if not any(p.has_constraints for p in parsed):
+            return self.search(query_texts, k, row_mask=row_mask, mask_stride=mask_stride, stream=stream)
+        c_ptr, c_kind, ct_ptr, ct_terms = self.clause_arrays(parsed)
+        bags = self.query_terms([" ".join(p.bag) for p in parsed])   # (tokens are alphanumeric runs: they re-tokenise as
+        if self.n == 0:                                              #  themselves)
+            return self.search_terms(*bags, k, stream=stream)
+        stride = (self.n + 31) // 32 * 4
+        with _on_stream(stream, self.device):
+            buf = self._clause_masks.get(stream)
+            if buf is None:
+                buf = self._clause_masks[stream] = torch.empty(MAX_QUERIES * stride, dtype=torch.uint8, device=self.device)
+        rc = _native.load().crag_bm25_clause_masks_host(
+            self.d_post_ptr.data_ptr(), self.d_post_pos.data_ptr(),
+            None if self.d_post_off is None else self.d_post_off.data_ptr(),
+            None if self.d_post_where is None else self.d_post_where.data_ptr(), self.n, self.n_terms,
+            c_ptr.ctypes.data, c_kind.ctypes.data if c_kind.size else None, ct_ptr.ctypes.data,
+            ct_terms.ctypes.data if ct_terms.size else None, len(parsed),
+            None if row_mask is None else row_mask.data_ptr(), int(mask_stride), self._slot(stream), buf.data_ptr(), stride,
+            ctypes.c_void_p(stream))
+        _native.check(rc, "crag_bm25_clause_masks_host")
+        return self.search_terms(*bags, k, row_mask=buf, mask_stride=stride, stream=stream)
 
     def search_terms(self, q_ptr, terms, weights, k: int, row_mask=None, mask_stride: int = 0, stream: int = 0):
         """`search` for queries that are term ids and weights already (the arrays of `query_terms`)."""

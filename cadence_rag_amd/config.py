@@ -61,6 +61,10 @@ class Settings:
     # row picked before (crag_index_mmr_async).  1.0 = the plain ranking = off: nothing is launched
     dense_mmr_lambda: float = 1.0
     dense_mmr_fetch: int = 0
+    # clause syntax of the BM25 word lane (cadence_rag_amd.bm25.parse_query: +required, -excluded, "quoted phrase"; a
+    # self-defined rule, not Tantivy's parser).  Phrases need lanes built with positions (build_bm25_lane(...,
+    # positions=True)).  Off: the query string is a bag of tokens and nothing is launched
+    bm25_query_syntax: bool = False
     # /answer (PHASED_PLAN.md:318-326): "" = off, "native" = the in-process Qwen3Generator, http(s) = an OpenAI-compatible
     # chat-completions service
     llm_base_url: str = ""

@@ -220,6 +220,32 @@ struct Bm25Params {
 int64_t bm25_scratch_bytes(int64_t n_rows, int nq, int k);
 hipError_t launch_bm25(const Bm25Params &p, hipStream_t st);
 
+// ---- BM25 query clauses as row masks (crag_bm25_clause.hip) ----
+constexpr int BM25_RANGE_WORDS = BM25_RANGE / 32;   // mask words one workgroup owns
+constexpr int BM25_CLAUSE_MAX = 16;                 // constraint clauses per query
+constexpr int BM25_PHRASE_MAX = 8;                  // terms per phrase
+constexpr int BM25_KIND_REQ_TERM = 0, BM25_KIND_EXC_TERM = 1, BM25_KIND_REQ_PHRASE = 2, BM25_KIND_EXC_PHRASE = 3,
+              BM25_KIND_NOTHING = 4;
+
+struct Bm25ClauseParams {
+    const int64_t *post_ptr;     // [V + 1]
+    const int32_t *post_pos;     // [nnz] row positions, ascending inside a term
+    const int64_t *post_off;     // [nnz + 1] token positions of posting j: post_where[post_off[j] .. post_off[j + 1])
+    const uint16_t *post_where;  // token positions, ascending inside a posting (NULL with post_off: no phrase clause)
+    const int32_t *c_ptr;        // [nq + 1] clauses of query q: [c_ptr[q], c_ptr[q + 1]), at most BM25_CLAUSE_MAX
+    const int32_t *c_kind;       // [n_clauses] BM25_KIND_*
+    const int32_t *ct_ptr;       // [n_clauses + 1] terms of clause c: ct_terms[ct_ptr[c] .. ct_ptr[c + 1])
+    const int32_t *ct_terms;     // term ids, in phrase order
+    const uint32_t *in;          // nullable: every row below n is admitted
+    int64_t in_stride_w;         // mask words per input run, 0: one run shared by all queries
+    uint32_t *out;               // [nq][stride_w]
+    int64_t stride_w;            // mask words per output run
+    int64_t n, n_words;          // rows; ceil(n / 32): the words an input run is sure to hold
+    int nq;
+    int has_phrase;              // some clause is a phrase: the kernel variant with the phrase's LDS
+};
+hipError_t launch_bm25_clause(const Bm25ClauseParams &p, hipStream_t st);
+
 
 // ---- near-duplicate suppression of ranked lists (crag_dedupe.hip) ----
 struct DedupeParams {

@@ -10,6 +10,7 @@ stay in the reference app; INTEGRATION.md shows the three call sites that switch
 """
 from __future__ import annotations
 
+import logging
 from dataclasses import dataclass
 from datetime import datetime
 from typing import Any, Dict, List, Optional, Sequence, Set, Tuple, Union
@@ -19,6 +20,8 @@ import numpy as np
 
 from .config import settings
 from .dense_index import DenseIndex
+
+_log = logging.getLogger(__name__)
 
 DEFAULT_RRF_K = 60
 DEFAULT_DENSE_CHUNK_TOPK = 50
@@ -779,18 +782,19 @@ class DenseTable:
         lane.table_generation = self.generation
         return lane
 
-    def build_bm25_lane(self, text_column: str):
+    def build_bm25_lane(self, text_column: str, positions: bool = False):
         """GPU BM25 lane (cadence_rag_amd.bm25.Bm25Index, non-parity with pg_search) over this table's
         `text_column` -- "text" for chunks, "content" for artifact_chunks (retrieve.py:141,173).  Row i <-> position i,
         so `filter_mask` serves this lane as it serves the other two.  The lane remembers the column and the table
-        generation it was built for: `sync_bm25_lane` brings a stale one up to date."""
+        generation it was built for: `sync_bm25_lane` brings a stale one up to date.  positions: also index the token
+        positions, which the phrase clauses of the query syntax need (settings.bm25_query_syntax)."""
         import torch
 
         from .bm25 import Bm25Index
         if text_column not in self.columns and len(self):
             raise ValueError(f"{self.name} has no column {text_column!r}")
         lane = Bm25Index(self.columns.get(text_column, []), np.asarray(self.columns.get(self.id_field, []), dtype=np.int64),
-                         torch.device("cuda", self.index.device))
+                         torch.device("cuda", self.index.device), positions=positions)
         lane.text_column = text_column
         lane.table_generation = self.generation
         return lane
@@ -809,7 +813,7 @@ class DenseTable:
                 lane.extend(self.columns[lane.text_column][held:], ids[held:])
             lane.table_generation = self.generation
             return lane
-        return self.build_bm25_lane(lane.text_column)
+        return self.build_bm25_lane(lane.text_column, positions=bool(getattr(lane, "positions", False)))
 
     def build_ngram_lane(self, text_column: str):
         """GPU character-trigram lane (cadence_rag_amd.ngram.NgramIndex: the reference's `pdb.ngram(3,3)` alias of the
@@ -1029,6 +1033,18 @@ class GpuRetrieveBackend(RetrieveBackend):
         mask = table.filter_mask(filters, call_ids)
         return None if mask is None else torch.from_numpy(DenseIndex.pack_mask(mask)).to(lane.device)
 
+    def _parsed_query(self, query):
+        """The query in the clause syntax, or None when it is over the syntax's limits: the lanes then read the raw
+        string as a bag of tokens.  Logged once per request: the lanes of one request ask with the same string."""
+        from .bm25 import QuerySyntaxError, parse_query
+        try:
+            return parse_query(query)
+        except QuerySyntaxError as exc:
+            if getattr(self, "_syntax_logged", None) != query:
+                self._syntax_logged = query
+                _log.warning("BM25 query syntax: %s; the query is read as a bag of tokens", exc)
+            return None
+
     def _bm25_rows(self, name, select, query, filters, call_ids, limit, field="bm25"):
         """retrieve.py:123-180: the SELECTed columns + `score`, best first.  field: "bm25", the word lane, or "ngram",
         the trigram lane (same rows, same limit, same mask; None when the side has no such lane)."""
@@ -1036,13 +1052,19 @@ class GpuRetrieveBackend(RetrieveBackend):
         fn, table = lanes[name], self.tables[name]
         if fn is None:
             return [] if field == "bm25" else None
+        # the clause syntax (settings.bm25_query_syntax): the word lane applies the clauses, the trigram
+        # lane is given the non-excluded items' text.  A query over the syntax's limits is read as a bag, as without it
+        parsed = self._parsed_query(query) if settings.bm25_query_syntax else None
+        if parsed is not None and field == "ngram":
+            query = parsed.text
         if callable(fn):
             return list(fn(query, filters, call_ids, limit))
         if len(table) == 0 or int(limit) <= 0:
             return []
         lane = lanes[name] = getattr(table, sync)(fn)
         d_mask = self._lane_mask(table, lane, filters, call_ids)
-        ids, scores, counts = lane.search([query], min(int(limit), _native_max_k()), row_mask=d_mask, mask_stride=0)
+        search = lane.search_query if parsed is not None and field == "bm25" else lane.search
+        ids, scores, counts = search([query], min(int(limit), _native_max_k()), row_mask=d_mask, mask_stride=0)
         n = int(counts[0])
         pos_of = table._positions()
         out = []

@@ -410,6 +410,64 @@ int crag_bm25_lane_host(const int64_t *d_post_ptr, const int32_t *d_post_pos, co
                         int64_t scratch_bytes, int64_t *d_out_ids, float *d_out_scores, int32_t *d_out_counts,
                         void *stream);
 
+/* Query clauses of the BM25 lane as row masks for up to 64 queries: required (+), excluded (-) and
+ * quoted-phrase clauses become one row mask per query, which crag_bm25_lane_host then scores under -- its arithmetic is
+ * untouched.  The reference hands the user's string to `text @@@ :query` (retrieve.py:141,173), where pg_search runs
+ * Tantivy's query parser.  NOT parity with it: the rule is this tree's own.
+ * Parsing (host, cadence_rag_amd.bm25.parse_query):
+ *   Items are separated by whitespace outside double quotes.  `"` opens a quoted item (and ends an unquoted one); an
+ *   unclosed quote runs to the end of the string.  An item may carry ONE prefix, `+` or `-`, directly in front of it, at the start of the string or
+ *   after whitespace (anywhere else, and inside quotes, the character is text).  Every item's text goes through the
+ *   lane's tokenizer; an item with no tokens is dropped.
+ *   An unquoted item: each of its tokens is a term clause of the item's kind -- `+` required, `-` excluded, no prefix
+ *   optional (`+foo-bar` is two required terms).
+ *   A quoted item: one token makes a term clause, two or more make a phrase clause; either is required unless the item
+ *   is prefixed `-` (then excluded).  An unprefixed quoted phrase is a REQUIREMENT (in Tantivy it is a SHOULD clause with
+ *   a phrase score).  Nothing else is syntax: `field:`, `*`, `~` and parentheses separate tokens as before.
+ * Matching.  A row passes a query iff its input mask bit is set, it holds every required term, no excluded term, every
+ *   required phrase and no excluded phrase.  A row holds the phrase t0 .. t(m-1) iff some token position p exists with
+ *   token t_i at position p + i for every i.  Positions index the tokens the tokenizer keeps for that row (they count as
+ *   doc_len does); a phrase never spans two rows; a term may repeat inside a phrase.  Positions at or above 65 535 are
+ *   NOT indexed (16-bit positions; the reference's chunks hold at most 600 tokens).
+ * Unknown tokens: in a required term or phrase the query matches nothing (kind 4); in an excluded clause the clause is
+ *   dropped; in an optional clause the token is dropped.
+ * Scoring.  The scored bag is the tokens of every non-excluded item (optional terms, required terms, members of required
+ *   phrases) with the qtf counting of the lane; excluded tokens score nothing.  A row is returned only if it passes AND
+ *   scores > 0, so a query of excluded clauses alone returns nothing, and a query without prefix or quote gives the
+ *   lane's result bit for bit.
+ * Limits (design decisions): at most CRAG_BM25_MAX_CLAUSES constraint clauses per query (required terms, excluded terms
+ *   and phrases count one each; optional terms are no clauses), at most CRAG_BM25_MAX_PHRASE terms per phrase.
+ *
+ *   d_post_ptr [n_terms + 1], d_post_pos [nnz]  the postings of crag_bm25_lane_host
+ *   d_post_off [nnz + 1] int64, d_post_where [d_post_off[nnz]] uint16: posting j (the order of d_post_pos) holds its
+ *               term at the token positions d_post_where[d_post_off[j] .. d_post_off[j + 1]), ascending.  Both may be
+ *               NULL when no clause is a phrase.
+ *   Clauses from the HOST in CSR form: h_c_ptr [nq + 1] int32 (h_c_ptr[0] = 0), h_c_kind [n_clauses] -- 0 required
+ *               term, 1 excluded term, 2 required phrase, 3 excluded phrase, 4 "matches nothing" (no terms) --,
+ *               h_ct_ptr [n_clauses + 1] int32 (h_ct_ptr[0] = 0), h_ct_terms: term ids in phrase order.
+ *   d_in_mask / in_stride  as in crag_attr_masks_host (nullable: every row is admitted; in_stride 0: one shared run; bits
+ *               at positions >= n_rows are ignored).  The in and out masks must NOT overlap; this is not checked.
+ *   d_out_mask  nq runs of mask_stride bytes in the row_mask encoding of crag_index_search (4-byte aligned); mask_stride a
+ *               multiple of 4 >= ceil(n_rows/32)*4.  EVERY byte of every run is written -- bits at positions >= n_rows
+ *               and the bytes up to mask_stride are 0 --, nothing outside nq * mask_stride bytes is; plain stores, never
+ *               OR: the buffer may be uninitialised and reused.  The output depends on the input alone, whatever the
+ *               launch geometry.  A query without clauses copies its input mask (all ones below n_rows without one).
+ *   slot        an upload slot as for crag_tech_lane_host: ONE host-to-device copy per call (the clause arrays)
+ * Everything is enqueued on `stream`, no host synchronisation.
+ * CRAG_EINVAL with a message that contains "bm25_clause_masks_host", checked before any HIP call, nothing enqueued: a
+ * NULL required pointer, nq outside 1..64, n_rows outside [0, 2^31), n_terms outside [0, 2^31), bad mask_stride or
+ * in_stride, a misaligned mask, h_c_ptr / h_ct_ptr not ascending from 0, an unknown kind, a term id outside
+ * [0, n_terms), a term clause without exactly one term, a kind-4 clause with terms, a phrase with fewer than 2 or more
+ * than 8 terms, more than 16 clauses in a query, a phrase clause with NULL position arrays.
+ * n_rows == 0 is CRAG_OK (the runs are zeroed when mask_stride > 0). */
+#define CRAG_BM25_MAX_CLAUSES 16
+#define CRAG_BM25_MAX_PHRASE  8
+int crag_bm25_clause_masks_host(const int64_t *d_post_ptr, const int32_t *d_post_pos, const int64_t *d_post_off,
+                                const uint16_t *d_post_where, int64_t n_rows, int64_t n_terms,
+                                const int32_t *h_c_ptr, const int32_t *h_c_kind, const int32_t *h_ct_ptr,
+                                const int32_t *h_ct_terms, int nq, const uint8_t *d_in_mask, int64_t in_stride,
+                                crag_upload_slot *slot, uint8_t *d_out_mask, int64_t mask_stride, void *stream);
+
 /* Character-trigram field of the BM25 lane: the inverted CSR crag_bm25_lane_host scores, built on the device from the
  * rows' bytes (cadence_rag_amd.ngram.NgramIndex drives it).  Stands in for the reference's second index over every
  * lexical column, the `pdb.ngram(3,3)` aliases of alembic/versions/0005_add_bm25_ngram.py and 0006_add_artifact_chunks.py
