@@ -412,11 +412,7 @@ int crag_index_dedupe_async(crag_index *ix, const int64_t *d_ids, const int32_t 
     std::lock_guard<std::mutex> lk(ix->mu);
     DeviceGuard guard(ix->device);
     crag::DedupeParams p;
-    p.corpus = ix->corpus;
-    p.inv_norm = ix->inv_norm;
-    p.stored = ix->ids;
-    p.size = ix->size;
-    p.piece_shift = crag::crag_piece_shift(ix->corpus16 != nullptr);
+    p.rows = row_view(ix);
     p.ids = d_ids;
     p.counts = d_counts;
     p.width = width;
@@ -436,7 +432,7 @@ int crag_index_search_ids_async(crag_index *ix, const float *d_queries, int nq, 
                                 float *d_out_scores, int32_t *d_out_counts, float *d_out_slot_scores, void *d_scratch,
                                 int64_t scratch_bytes, void *stream) {
     if (!ix) return fail(CRAG_EINVAL, "search_ids: index is NULL");
-    if (nq < 0 || nq > 65535) return fail(CRAG_EINVAL, "search_ids: nq must be in [0, 65535] (got %d)", nq);
+    if (int rc = check_nq("search_ids", nq)) return rc;
     if (width < 1) return fail(CRAG_EINVAL, "search_ids: width must be >= 1 (got %d)", width);
     if (k < 1 || k > CRAG_MAX_K) return fail(CRAG_EINVAL, "search_ids: k must be in [1, %d] (got %d)", CRAG_MAX_K, k);
     if (list_stride != 0 && list_stride != width)
@@ -447,17 +443,14 @@ int crag_index_search_ids_async(crag_index *ix, const float *d_queries, int nq, 
     if (width > CRAG_SUBSET_MAX_WIDTH)
         return fail(CRAG_E2BIG, "search_ids: width %d exceeds CRAG_SUBSET_MAX_WIDTH (%d): use the row_mask route", width,
                     CRAG_SUBSET_MAX_WIDTH);
-    if (scratch_bytes < crag::subset_scratch_bytes(nq, width) || ((uintptr_t)d_scratch & 7))
-        return fail(CRAG_EINVAL, "search_ids: scratch too small or not 8-byte aligned (crag_index_search_ids_scratch_bytes)");
+    if (int rc = check_scratch("search_ids", d_scratch, scratch_bytes, crag::subset_scratch_bytes(nq, width),
+                               "crag_index_search_ids_scratch_bytes"))
+        return rc;
     if (nq == 0) return CRAG_OK;
     std::lock_guard<std::mutex> lk(ix->mu);
     DeviceGuard guard(ix->device);
     crag::SubsetParams p;
-    p.corpus = ix->corpus;
-    p.inv_norm = ix->inv_norm;
-    p.stored = ix->ids;
-    p.size = ix->size;
-    p.piece_shift = crag::crag_piece_shift(ix->corpus16 != nullptr);
+    p.rows = row_view(ix);
     p.queries = d_queries;
     p.nq = nq;
     p.dim = ix->dim;
@@ -482,7 +475,7 @@ int crag_index_mmr_async(crag_index *ix, const int64_t *d_ids, const float *d_re
                          int32_t *d_out_slots, float *d_out_sim_rows, int32_t *d_out_counts, void *d_scratch,
                          int64_t scratch_bytes, void *stream) {
     if (!ix) return fail(CRAG_EINVAL, "mmr: index is NULL");
-    if (nq < 0 || nq > 65535) return fail(CRAG_EINVAL, "mmr: nq must be in [0, 65535] (got %d)", nq);
+    if (int rc = check_nq("mmr", nq)) return rc;
     if (width < 1 || width > CRAG_MMR_MAX_WIDTH)
         return fail(CRAG_EINVAL, "mmr: width must be in [1, %d] (got %d)", CRAG_MMR_MAX_WIDTH, width);
     if (k < 1 || k > CRAG_MMR_MAX_WIDTH) return fail(CRAG_EINVAL, "mmr: k must be in [1, %d] (got %d)", CRAG_MMR_MAX_WIDTH, k);
@@ -490,17 +483,14 @@ int crag_index_mmr_async(crag_index *ix, const int64_t *d_ids, const float *d_re
         return fail(CRAG_EINVAL, "mmr: lambda must be finite, in [0, 1] (got %g)", (double)lambda);
     if (!d_ids || !d_rel || !d_counts || !d_out_ids || !d_out_rel || !d_out_counts || !d_scratch)
         return fail(CRAG_EINVAL, "mmr: ids / rel / counts / out_ids / out_rel / out_counts / scratch must not be NULL");
-    if (scratch_bytes < crag::mmr_scratch_bytes(nq, width) || ((uintptr_t)d_scratch & 7))
-        return fail(CRAG_EINVAL, "mmr: scratch too small or not 8-byte aligned (crag_index_mmr_scratch_bytes)");
+    if (int rc = check_scratch("mmr", d_scratch, scratch_bytes, crag::mmr_scratch_bytes(nq, width),
+                               "crag_index_mmr_scratch_bytes"))
+        return rc;
     if (nq == 0) return CRAG_OK;
     std::lock_guard<std::mutex> lk(ix->mu);
     DeviceGuard guard(ix->device);
     crag::MmrParams p;
-    p.corpus = ix->corpus;
-    p.inv_norm = ix->inv_norm;
-    p.stored = ix->ids;
-    p.size = ix->size;
-    p.piece_shift = crag::crag_piece_shift(ix->corpus16 != nullptr);
+    p.rows = row_view(ix);
     p.ids = d_ids;
     p.rel = d_rel;
     p.counts = d_counts;
@@ -529,7 +519,7 @@ int crag_index_search_grouped_async(crag_index *ix, const float *d_queries, int 
                                     int64_t *d_out_ids, float *d_out_scores, int32_t *d_out_groups, int32_t *d_out_counts,
                                     void *d_scratch, int64_t scratch_bytes, void *stream) {
     if (!ix) return fail(CRAG_EINVAL, "search_grouped: index is NULL");
-    if (nq < 0 || nq > 65535) return fail(CRAG_EINVAL, "search_grouped: nq must be in [0, 65535] (got %d)", nq);
+    if (int rc = check_nq("search_grouped", nq)) return rc;
     if (k < 1 || k > CRAG_MAX_K) return fail(CRAG_EINVAL, "search_grouped: k must be in [1, %d] (got %d)", CRAG_MAX_K, k);
     if (per_group < 1 || per_group > CRAG_GROUP_MAX_PER)
         return fail(CRAG_EINVAL, "search_grouped: per_group must be in [1, %d] (got %d)", CRAG_GROUP_MAX_PER, per_group);
@@ -544,18 +534,14 @@ int crag_index_search_grouped_async(crag_index *ix, const float *d_queries, int 
                         (long long)need, (long long)mask_stride);
         if (((uintptr_t)d_row_mask) & 3) return fail(CRAG_EINVAL, "search_grouped: row_mask must be 4-byte aligned");
     }
-    if (scratch_bytes < crag::group_scratch_bytes(nq, n_groups, per_group) || ((uintptr_t)d_scratch & 7))
-        return fail(CRAG_EINVAL,
-                    "search_grouped: scratch too small or not 8-byte aligned (crag_index_search_grouped_scratch_bytes)");
+    if (int rc = check_scratch("search_grouped", d_scratch, scratch_bytes, crag::group_scratch_bytes(nq, n_groups, per_group),
+                               "crag_index_search_grouped_scratch_bytes"))
+        return rc;
     if (nq == 0) return CRAG_OK;
     std::lock_guard<std::mutex> lk(ix->mu);
     DeviceGuard guard(ix->device);
     crag::GroupParams p;
-    p.corpus = ix->corpus;
-    p.inv_norm = ix->inv_norm;
-    p.stored = ix->ids;
-    p.size = ix->size;
-    p.piece_shift = crag::crag_piece_shift(ix->corpus16 != nullptr);
+    p.rows = row_view(ix);
     p.queries = d_queries;
     p.nq = nq;
     p.dim = ix->dim;

@@ -36,16 +36,6 @@ static_assert(BM25_RANGE == 1 << 14, "the range-local key packs the position int
 static_assert(BM25_PER == 16, "one half mask word per thread");
 static_assert(BM25_MERGE_PER * BM25_THREADS >= 2 * CRAG_MAX_K, "a merge round takes the running best plus one list");
 
-// first index in [lo, hi) whose position is >= x
-__device__ __forceinline__ int64_t lower_bound_pos(const int32_t *pos, int64_t lo, int64_t hi, int64_t x) {
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if ((int64_t)pos[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // Number of keys >= thr in the workgroup.  s_part: 16 ints; consecutive calls alternate between two such buffers, so one
 // barrier per call is enough (a wave can be at most one call ahead of the slowest reader).
 template <int NPER>
@@ -100,8 +90,8 @@ __global__ __launch_bounds__(BM25_THREADS) void bm25_score_kernel(Bm25Params p) 
         if (tid < nt) {   // lanes search different terms: the workgroup pays one latency chain per round
             const int term = p.q_term[c0 + tid];
             const int64_t a = p.post_ptr[term], b = p.post_ptr[term + 1];
-            lo = lower_bound_pos(p.post_pos, a, b, base);
-            hi = lower_bound_pos(p.post_pos, lo, b, end);
+            lo = lower_bound_asc(p.post_pos, a, b, base);
+            hi = lower_bound_asc(p.post_pos, lo, b, end);
         }
         // (the barrier of this vote also keeps the previous round's readers of s_lo / s_len ahead of the writes below)
         if (!__syncthreads_or(hi > lo)) continue;   // no term of this round has a posting in the range

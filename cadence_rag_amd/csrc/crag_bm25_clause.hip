@@ -43,16 +43,6 @@ static_assert(CL_THREADS == 512 && CL_TERMS <= CL_THREADS, "one lane per clause 
 static_assert(BM25_RANGE <= 65536, "the candidate list holds local positions in 16 bits");
 static_assert(BM25_CLAUSE_MAX == CRAG_BM25_MAX_CLAUSES && BM25_PHRASE_MAX == CRAG_BM25_MAX_PHRASE, "one set of limits");
 
-// first index in [lo, hi) whose position is >= x
-__device__ __forceinline__ int64_t cl_lower_bound(const int32_t *pos, int64_t lo, int64_t hi, int64_t x) {
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if ((int64_t)pos[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // is token position x in where[a .. a + len) (ascending)?
 __device__ __forceinline__ bool cl_has_where(const uint16_t *where, int64_t a, int len, int x) {
     int lo = 0, hi = len;
@@ -125,8 +115,8 @@ __global__ __launch_bounds__(CL_THREADS) void bm25_clause_mask_kernel(Bm25Clause
         if (tid < ntm) {   // lanes search different terms: the workgroup pays one latency chain
             const int term = p.ct_terms[tt0 + tid];
             const int64_t a = p.post_ptr[term], b = p.post_ptr[term + 1];
-            const int64_t lo = cl_lower_bound(p.post_pos, a, b, base);
-            const int64_t hi = cl_lower_bound(p.post_pos, lo, b, end);
+            const int64_t lo = lower_bound_asc(p.post_pos, a, b, base);
+            const int64_t hi = lower_bound_asc(p.post_pos, lo, b, end);
             s_lo[tid] = lo;
             s_len[tid] = (int)(hi - lo);
         }

@@ -32,12 +32,7 @@ __global__ __launch_bounds__(256) void lookup_ids_kernel(const int64_t *stored, 
     unsigned long long c = 0;
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
         const int64_t id = ids[j];
-        int64_t lo = 0, hi = size;   // first position whose id is >= id
-        while (lo < hi) {
-            const int64_t mid = lo + ((hi - lo) >> 1);
-            if (stored[mid] < id) lo = mid + 1;
-            else hi = mid;
-        }
+        const int64_t lo = lower_bound_asc(stored, 0, size, id);
         const bool hit = lo < size && stored[lo] == id;
         if (pos) pos[j] = lo + (add_index ? j : 0);
         if (hit) {

@@ -1,7 +1,8 @@
 // crag_exact.h -- the exact-score arithmetic of the dense lane, in one place: the 64-bit candidate key, the canonical
 // 1/||q||, one 128-dim slice of the exact fp32 dot product and the score -> key expression.  crag_search.hip (the scans
 // and the selection kernel), crag_subset.hip (the search over id lists) and crag_group.hip (the search with a cap per
-// group) include it, so a (query, row) pair has the same score bits on every path.  Device code only.
+// group) include it, so a (query, row) pair has the same score bits on every path; crag_mmr.hip includes it for the key
+// helpers of its walk (its cosines are crag_gram.h's, not these scores).  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

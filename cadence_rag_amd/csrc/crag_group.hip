@@ -107,7 +107,7 @@ __global__ __launch_bounds__(SCAN_THREADS) __attribute__((amdgpu_waves_per_eu(2,
     __shared__ float qinv_sh[GQ_BLOCK];
     const int tid = threadIdx.x, lane = tid & 63, grp = tid >> 3, sub = tid & 7;
     const int64_t pos = (int64_t)blockIdx.x * GS_ROWS + grp;
-    const bool stored = pos < p.size;
+    const bool stored = pos < p.rows.size;
 
     f32x4 c0[16], c1[16];
 #pragma unroll
@@ -116,10 +116,10 @@ __global__ __launch_bounds__(SCAN_THREADS) __attribute__((amdgpu_waves_per_eu(2,
     int32_t g = -1;
     if (stored) {
         if (sub == 0) {
-            inv_row = p.inv_norm[pos];
+            inv_row = p.rows.inv_norm[pos];
             g = p.row_group[pos];
         }
-        const f32x4 *ctile = reinterpret_cast<const f32x4 *>(p.corpus + (size_t)(pos >> 5) * TILE_FLOATS) + (size_t)sub * 32 * 32;
+        const f32x4 *ctile = reinterpret_cast<const f32x4 *>(p.rows.corpus + (size_t)(pos >> 5) * TILE_FLOATS) + (size_t)sub * 32 * 32;
         exact_slice_fetch<PS>(ctile, (int)(pos & 31), c0, c1);
     }
     // lane 0 of a row owns its pairs; a group number outside [0, n_groups) is never used as an index
@@ -219,7 +219,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void group_select_kernel(GroupParams 
             const uint64_t key = keys[r];
             const uint32_t pos = ~(uint32_t)key;
             p.out_scores[o] = ord2f((uint32_t)(key >> 32));
-            p.out_ids[o] = p.stored[pos];
+            p.out_ids[o] = p.rows.stored[pos];
             if (p.out_groups) p.out_groups[o] = p.row_group[pos];
         } else {
             p.out_scores[o] = __uint_as_float(0x7fc00000u);
@@ -250,9 +250,9 @@ hipError_t launch_grouped(const GroupParams &p, hipStream_t st) {
     hipLaunchKernelGGL(group_prep_kernel, dim3(prep_blocks), dim3(SCAN_THREADS), 0, st, p, words);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (p.size > 0) {
-        const dim3 grid((unsigned)((p.size + GS_ROWS - 1) / GS_ROWS));
-        if (p.piece_shift == PS_BIG) hipLaunchKernelGGL(group_score_kernel<PS_BIG>, grid, dim3(SCAN_THREADS), 0, st, p);
+    if (p.rows.size > 0) {
+        const dim3 grid((unsigned)((p.rows.size + GS_ROWS - 1) / GS_ROWS));
+        if (p.rows.piece_shift == PS_BIG) hipLaunchKernelGGL(group_score_kernel<PS_BIG>, grid, dim3(SCAN_THREADS), 0, st, p);
         else hipLaunchKernelGGL(group_score_kernel<PS_SMALL>, grid, dim3(SCAN_THREADS), 0, st, p);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }

@@ -37,6 +37,18 @@ __attribute__((format(printf, 2, 3))) inline int fail(int code, const char *fmt,
                         __FILE__, __LINE__);                                                   \
     } while (0)
 
+// The two argument checks every entry point that works in a caller's scratch makes; `op` heads its messages, `sizer`
+// names the function that tells the size.
+inline int check_nq(const char *op, int nq) {   // (a grid dimension)
+    if (nq < 0 || nq > 65535) return fail(CRAG_EINVAL, "%s: nq must be in [0, 65535] (got %d)", op, nq);
+    return CRAG_OK;
+}
+inline int check_scratch(const char *op, const void *scratch, int64_t have, int64_t need, const char *sizer) {
+    if (have < need || ((uintptr_t)scratch & 7))
+        return fail(CRAG_EINVAL, "%s: scratch too small or not 8-byte aligned (%s)", op, sizer);
+    return CRAG_OK;
+}
+
 // behind one or more hipLaunchKernelGGL
 inline int launch_ok(const char *what) {
     hipError_t e = hipGetLastError();

@@ -97,3 +97,8 @@ struct crag_index {
 };
 
 static_assert(crag_index::MAX_WS == crag::PF_STAT_WS, "one block of statistics records per workspace");
+
+// the stored rows as the kernels of the list operators see them (crag_rows.h)
+inline crag::RowView row_view(const crag_index *ix) {
+    return {ix->corpus, ix->inv_norm, ix->ids, ix->size, crag::crag_piece_shift(ix->corpus16 != nullptr)};
+}

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "crag_arch.h"
+#include "crag_rows.h"
 
 namespace crag {
 
@@ -249,11 +250,7 @@ hipError_t launch_bm25_clause(const Bm25ClauseParams &p, hipStream_t st);
 
 // ---- near-duplicate suppression of ranked lists (crag_dedupe.hip) ----
 struct DedupeParams {
-    const float *corpus;        // tile32 layout
-    const float *inv_norm;
-    const int64_t *stored;      // [size] ids, ascending with the position
-    int64_t size;
-    int piece_shift;
+    RowView rows;               // the stored rows (crag_rows.h)
     const int64_t *ids;         // [nq, width] ranked lists, best first
     const int32_t *counts;      // [nq], clamped to [0, width]
     int width;                  // <= CRAG_DEDUPE_MAX_WIDTH
@@ -267,11 +264,7 @@ hipError_t launch_dedupe(const DedupeParams &p, int nq, hipStream_t st);
 
 // ---- exact top-k and scores over listed rows (crag_subset.hip) ----
 struct SubsetParams {
-    const float *corpus;        // tile32 layout
-    const float *inv_norm;
-    const int64_t *stored;      // [size] ids, ascending with the position
-    int64_t size;
-    int piece_shift;
+    RowView rows;               // the stored rows (crag_rows.h)
     const float *queries;       // [nq, dim] row-major fp32, raw
     int nq, dim, k;
     const int64_t *ids;         // [nq, width] lists (list_stride == width) or one shared [width] list (list_stride == 0)
@@ -289,11 +282,7 @@ hipError_t launch_subset(const SubsetParams &p, hipStream_t st);
 
 // ---- exact top-k under "at most per_group rows per group" (crag_group.hip) ----
 struct GroupParams {
-    const float *corpus;        // tile32 layout
-    const float *inv_norm;
-    const int64_t *stored;      // [size] ids, ascending with the position
-    int64_t size;
-    int piece_shift;
+    RowView rows;               // the stored rows (crag_rows.h)
     const float *queries;       // [nq, dim] row-major fp32, raw
     int nq, dim, k;
     const int32_t *row_group;   // [size] group number by row position; outside [0, n_groups): the row is ignored
@@ -314,11 +303,7 @@ hipError_t launch_grouped(const GroupParams &p, hipStream_t st);
 
 // ---- MMR diversification of ranked lists (crag_mmr.hip) ----
 struct MmrParams {
-    const float *corpus;        // tile32 layout
-    const float *inv_norm;
-    const int64_t *stored;      // [size] ids, ascending with the position
-    int64_t size;
-    int piece_shift;
+    RowView rows;               // the stored rows (crag_rows.h)
     const int64_t *ids;         // [nq, width]
     const float *rel;           // [nq, width] relevance of each slot
     const int32_t *counts;      // [nq], clamped to [0, width]

@@ -8,17 +8,15 @@
 // is picked, equal values going to the lower id; pen[i] is 0 until a picked comparable item p meets a comparable i, then
 // the largest cos(p, i) so far.  An item that is not comparable is never penalised and never penalises.
 //
-//   cos(i, j) = clamp(dot(i, j) * (inv_norm[i] * inv_norm[j]), -1, 1), the bits of crag_dedupe.hip: the eight 128-dim
-//   slice chains of v_mfma_f32_32x32x2_f32 steps over fragments loaded by load_block (restated here), summed in slice
-//   order.  cos(i, j) and cos(j, i) are the same bits and depend on the two rows alone.
+//   cos(i, j) is crag_gram.h's block of pair cosines, the one crag_dedupe.hip runs: the same code, hence the same bits.
+//   cos(i, j) and cos(j, i) are the same bits and depend on the two rows alone.
 //
 // Two launches:
 //  1. mmr_gram_kernel<PS>: grid (block pairs bi <= bj of 32 slots, queries), 512 threads.  A workgroup finds the row
-//     positions of its two blocks (binary search in the ascending stored ids), then does one (bi, bj) step of
-//     dedupe_kernel -- wave w the 32 x 32 partial Gram block over dims [128w, 128w + 128), 64 MFMA steps, the eight
-//     partials summed in LDS in wave order, scaled, clamped -- and writes the block and its transpose into the query's
-//     [width_pad, width_pad] matrix in the scratch, NaN where either item is not comparable.  Only block pairs below
-//     ceil(count / 32) are computed; the walk reads nothing else.
+//     positions of its two blocks (comparable_row, crag_rows.h), computes the (bi, bj) block -- gram_block_partial per
+//     wave, gram_block_cosines -- and writes the block and its transpose into the query's [width_pad, width_pad]
+//     matrix in the scratch, NaN where either item is not comparable.  Only block pairs below ceil(count / 32) are
+//     computed; the walk reads nothing else.
 //  2. mmr_walk_kernel: one 256-thread workgroup per query, one thread per slot.  Candidates and the rank of each id
 //     among the list's ids (the tie-break) from an all-pairs compare in LDS; per pick the values, a workgroup argmax
 //     over the 64-bit key (f2ord(value), 255 - id rank, slot), one coalesced read of the pick's Gram row, the penalty
@@ -30,6 +28,7 @@
 
 #include "../../include/crag_dense.h"
 #include "crag_exact.h"
+#include "crag_gram.h"
 #include "crag_kernels.h"
 #include "crag_layout.h"
 
@@ -37,32 +36,15 @@ namespace crag {
 namespace {
 
 constexpr int MM_W = CRAG_MMR_MAX_WIDTH;
-constexpr int MM_TILE_STRIDE = 33;   // floats per row of the finished block: the transposed write reads a column
 
 static_assert(MM_W == 256, "the walk runs one thread per slot in a 256-thread workgroup; slot and rank share a key word");
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 struct GramLds {
-    float part[SCAN_WAVES][16][64];     // 32 KiB: the waves' partial Gram blocks, accumulator order
-    float tile[32 * MM_TILE_STRIDE];    // cos(item 32 bi + i, item 32 bj + j); NaN: no pair
+    GramPartials part;
+    float tile[32 * GRAM_STRIDE];       // cos(item 32 bi + i, item 32 bj + j); NaN: no pair.  The transposed write reads a column
     int64_t pos[64];                    // row position of the items of block bi (0..31) and bj (32..63), -1: not comparable
     float inv[64];                      // 1/||row||, 0: not comparable
 };
-
-// crag_dedupe.hip's load_block: the wave's K slice of the 32 items of a block as MFMA operand fragments.  Lane
-// (j = lane & 31, h = lane >> 5) holds float4 2t + h of the slice of its item j (row position pos; -1: zeros) in f[t].
-template <int PS>
-__device__ __forceinline__ void load_block(const float *corpus, int64_t pos, int w, int h, f32x4 (&f)[16]) {
-    if (pos >= 0) {
-#pragma unroll
-        for (int t = 0; t < 16; ++t)
-            f[t] = *reinterpret_cast<const f32x4 *>(corpus + row_f4_offset<PS>(pos, w * 32 + 2 * t + h));
-    } else {
-#pragma unroll
-        for (int t = 0; t < 16; ++t) f[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-}
 
 __device__ __forceinline__ int mmr_width_pad(int width) { return (width + 31) & ~31; }
 
@@ -70,8 +52,7 @@ template <int PS>
 __global__ __launch_bounds__(SCAN_THREADS) void mmr_gram_kernel(MmrParams p) {
     __shared__ GramLds L;
     const int q = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int count = p.counts[q];
-    count = count < 0 ? 0 : (count > p.width ? p.width : count);
+    const int count = clamp_count(p.counts[q], p.width);
     // block pair blockIdx.x -> (bi <= bj), column blocks ascending
     int bj = 0;
     while ((bj + 1) * (bj + 2) / 2 <= (int)blockIdx.x) ++bj;
@@ -85,68 +66,21 @@ __global__ __launch_bounds__(SCAN_THREADS) void mmr_gram_kernel(MmrParams p) {
         const int slot = (tid < 32 ? bi : bj) * 32 + (tid & 31);
         int64_t pos = -1;
         float inv = 0.f;
-        if (slot < count) {
-            const int64_t id = p.ids[(size_t)q * p.width + slot];
-            int64_t lo = 0, hi = p.size;   // first position whose id is >= id
-            while (lo < hi) {
-                const int64_t mid = lo + ((hi - lo) >> 1);
-                if (p.stored[mid] < id) lo = mid + 1;
-                else hi = mid;
-            }
-            if (id != -1 && lo < p.size && p.stored[lo] == id) {
-                inv = p.inv_norm[lo];
-                if (inv > 0.f) pos = lo;
-                else inv = 0.f;
-            }
-        }
+        if (slot < count) comparable_row(p.rows, p.ids[(size_t)q * p.width + slot], pos, inv);
         L.pos[tid] = pos;
         L.inv[tid] = inv;
     }
     __syncthreads();
 
-    // ---- the block pair's partial products, one K slice per wave ----
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    f32x4 fb[16];
-    load_block<PS>(p.corpus, L.pos[32 + (lane & 31)], w, lane >> 5, fb);
-    if (bi < bj) {
-        f32x4 fa[16];
-        load_block<PS>(p.corpus, L.pos[lane & 31], w, lane >> 5, fa);
-#pragma unroll
-        for (int t = 0; t < 16; ++t)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[t][c], fb[t][c], acc, 0, 0, 0);
-    } else {
-#pragma unroll
-        for (int t = 0; t < 16; ++t)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fb[t][c], fb[t][c], acc, 0, 0, 0);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) L.part[w][r][lane] = acc[r];
-    __syncthreads();
-    // accumulator register r of lane (j, h) is row (r & 3) + 8 (r >> 2) + 4 h of the A block, column j of the B block
-#pragma unroll
-    for (int e = tid; e < 1024; e += SCAN_THREADS) {
-        const int r = e >> 6, ln = e & 63;
-        float s = L.part[0][r][ln];
-#pragma unroll
-        for (int ww = 1; ww < SCAN_WAVES; ++ww) s += L.part[ww][r][ln];
-        const int i = (r & 3) + 8 * (r >> 2) + 4 * (ln >> 5), j = ln & 31;
-        const float ii = L.inv[i], ij = L.inv[32 + j];
-        float c = s * (ii * ij);
-        c = c > 1.f ? 1.f : (c < -1.f ? -1.f : c);
-        if (!(ii > 0.f) || !(ij > 0.f)) c = __builtin_nanf("");
-        L.tile[i * MM_TILE_STRIDE + j] = c;
-    }
-    __syncthreads();
+    // ---- the block pair's cosines: one K slice per wave, then the eight partials in LDS ----
+    const f32x16 acc = gram_block_partial<PS>(p.rows.corpus, L.pos[lane & 31], L.pos[32 + (lane & 31)], bi == bj, w, lane);
+    gram_block_cosines(acc, L.part, L.inv, L.inv + 32, L.tile, GRAM_STRIDE);
     // ---- the block and its transpose, rows of 32 consecutive floats each ----
 #pragma unroll
     for (int e = tid; e < 1024; e += SCAN_THREADS) {
         const int a = e >> 5, b = e & 31;
-        gram[(size_t)(bi * 32 + a) * wp + bj * 32 + b] = L.tile[a * MM_TILE_STRIDE + b];
-        if (bi < bj) gram[(size_t)(bj * 32 + a) * wp + bi * 32 + b] = L.tile[b * MM_TILE_STRIDE + a];
+        gram[(size_t)(bi * 32 + a) * wp + bj * 32 + b] = L.tile[a * GRAM_STRIDE + b];
+        if (bi < bj) gram[(size_t)(bj * 32 + a) * wp + bi * 32 + b] = L.tile[b * GRAM_STRIDE + a];
     }
 }
 
@@ -154,8 +88,7 @@ __global__ __launch_bounds__(MM_W) void mmr_walk_kernel(MmrParams p) {
     __shared__ int64_t s_id[MM_W];
     __shared__ unsigned long long s_best[2][MM_W / 64];
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int count = p.counts[q];
-    count = count < 0 ? 0 : (count > p.width ? p.width : count);
+    const int count = clamp_count(p.counts[q], p.width);
     const int wp = mmr_width_pad(p.width);
     const float *gram = p.gram + (size_t)q * wp * wp;
     const float nan = __builtin_nanf("");
@@ -245,7 +178,7 @@ hipError_t launch_mmr(const MmrParams &p, hipStream_t st) {
     if (p.nq <= 0) return hipSuccess;
     const int nbw = (p.width + 31) >> 5;
     const dim3 grid(nbw * (nbw + 1) / 2, p.nq);
-    if (p.piece_shift == PS_BIG) hipLaunchKernelGGL(mmr_gram_kernel<PS_BIG>, grid, dim3(SCAN_THREADS), 0, st, p);
+    if (p.rows.piece_shift == PS_BIG) hipLaunchKernelGGL(mmr_gram_kernel<PS_BIG>, grid, dim3(SCAN_THREADS), 0, st, p);
     else hipLaunchKernelGGL(mmr_gram_kernel<PS_SMALL>, grid, dim3(SCAN_THREADS), 0, st, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -11,8 +11,8 @@
 //  1. subset_score_kernel, grid (ceil(width / 64), nq), 512 threads: a workgroup scores 64 slots of one query, 8 lanes
 //     per slot (lane `sub` = K slice).  It loads the query (load_query_quad -> canonical_qinv -> LDS in fragment order
 //     [slice][s][half]) while its 64 ids are on their way, resolves the ids to positions in the ascending stored ids
-//     (the lower-bound search of crag_dedupe.hip, nine-way: the 8 lanes of a slot probe 8 points per round -- 7 dependent
-//     round trips at a million rows instead of 20; this path is latency-bound), then fetches stored[pos], 1/||row|| and
+//     (lower_bound_asc_x8 of crag_rows.h: the 8 lanes of a slot probe 8 points per round -- 7 dependent round trips at
+//     a million rows instead of 20; this path is latency-bound), then fetches stored[pos], 1/||row|| and
 //     the row's 32 float4 per lane in flight together, and writes the key (f2ord(score) << 32) | ~pos per slot into the
 //     scratch (0: ignored) and the slot's score if asked for.
 //  2. subset_select_kernel, one workgroup per query: the query's keys into LDS (32 KiB at 4096), padded with zeros to
@@ -37,8 +37,6 @@ constexpr int SS_W = CRAG_SUBSET_MAX_WIDTH;
 static_assert(SS_SLOTS == 64, "the grid is ceil(width / 64) x nq");
 static_assert((SS_W & (SS_W - 1)) == 0 && SS_W >= SCAN_THREADS, "the select kernel sorts a power of two of keys in LDS");
 
-__device__ __forceinline__ int clamp_count(int c, int width) { return c < 0 ? 0 : (c > width ? width : c); }
-
 // (two to three waves per SIMD: left to itself the compiler holds the kernel to 64 registers and fetches a row in
 // batches of a few float4; with ~160 the loads of a row are in flight together, which is all this kernel waits for)
 template <int PS>
@@ -56,34 +54,20 @@ __global__ __launch_bounds__(SCAN_THREADS) __attribute__((amdgpu_waves_per_eu(2,
     if (tid < 256) qs[tid >> 5][(tid >> 1) & 15][tid & 1] = v;
     __syncthreads();
 
-    // ---- id -> first position whose stored id is >= id (crag_dedupe.hip's search, 8 probes per round) ----
-    // invariant: the answer lies in [lo, hi].  Lane `sub` probes the last position of the (sub + 1)-th of nine parts;
-    // the stored ids ascend, so the probes below the id are a prefix of the eight: their number c picks the part.
+    // ---- id -> first position whose stored id is >= id, the slot's 8 lanes together ----
     const bool wanted = listed && id != -1 && qinv > 0.f;   // (a zero / non-finite query scores nothing: no row is read)
-    int64_t lo = 0, hi = wanted ? p.size : 0;
-    while (__any(lo < hi)) {
-        const int64_t step = (hi - lo + 8) / 9;
-        const int64_t m = lo + (sub + 1) * step - 1;
-        const bool below = lo < hi && m < hi && p.stored[m] < id;
-        const unsigned long long b = __ballot(below);
-        const int c = __popc((unsigned)(b >> (lane & ~7)) & 0xffu);
-        if (lo < hi) {
-            const int64_t mc = lo + (c + 1) * step - 1;   // the first probe that is not below the id, if there is one
-            if (c < 8 && mc < hi) hi = mc;
-            lo += c * step;
-        }
-    }
+    const int64_t lo = lower_bound_asc_x8(p.rows.stored, 0, wanted ? p.rows.size : 0, id, lane);
 
     // ---- the row at that position, its id and 1/||row|| in flight together; the pair counts if the id is the one ----
-    const bool live = wanted && lo < p.size;
+    const bool live = wanted && lo < p.rows.size;
     float part = 0.f, inv_row = 0.f;
     int64_t found = -1;
     if (live) {
         if (sub == 0) {
-            found = p.stored[lo];
-            inv_row = p.inv_norm[lo];
+            found = p.rows.stored[lo];
+            inv_row = p.rows.inv_norm[lo];
         }
-        const f32x4 *ctile = reinterpret_cast<const f32x4 *>(p.corpus + (size_t)(lo >> 5) * TILE_FLOATS) + (size_t)sub * 32 * 32;
+        const f32x4 *ctile = reinterpret_cast<const f32x4 *>(p.rows.corpus + (size_t)(lo >> 5) * TILE_FLOATS) + (size_t)sub * 32 * 32;
         part = exact_slice_dot<PS>(&qs[sub][0][0], ctile, (int)(lo & 31));
     }
     // the 8 slice sums in wave order 0..7 (the scan kernels' split-K reduction order)
@@ -132,7 +116,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void subset_select_kernel(SubsetParam
         const uint64_t key = keys[i];
         if (key != 0ull && (i == 0 || key != keys[i - 1])) {
             p.out_scores[(size_t)q * k + rank] = ord2f((uint32_t)(key >> 32));
-            p.out_ids[(size_t)q * k + rank] = p.stored[~(uint32_t)key];
+            p.out_ids[(size_t)q * k + rank] = p.rows.stored[~(uint32_t)key];
             ++rank;
         }
     }
@@ -153,7 +137,7 @@ int64_t subset_scratch_bytes(int nq, int width) {
 hipError_t launch_subset(const SubsetParams &p, hipStream_t st) {
     if (p.nq <= 0) return hipSuccess;
     const dim3 grid((p.width + SS_SLOTS - 1) / SS_SLOTS, p.nq);
-    if (p.piece_shift == PS_BIG) hipLaunchKernelGGL(subset_score_kernel<PS_BIG>, grid, dim3(SCAN_THREADS), 0, st, p);
+    if (p.rows.piece_shift == PS_BIG) hipLaunchKernelGGL(subset_score_kernel<PS_BIG>, grid, dim3(SCAN_THREADS), 0, st, p);
     else hipLaunchKernelGGL(subset_score_kernel<PS_SMALL>, grid, dim3(SCAN_THREADS), 0, st, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -43,6 +43,37 @@ def _as_f32_2d(x, dim: int, what: str):
     return a.ctypes.data, int(a.shape[0]), a
 
 
+def _opt_ptr(t):
+    """the device pointer of an optional tensor argument of the async wrappers (None: NULL)"""
+    return None if t is None else t.data_ptr()
+
+
+def _pad_lists(ids, cap: int, what: str = "", extra=None):
+    """One flat list of ids or a sequence of ragged lists -> (single, lists, h_ids, counts): h_ids int64 [n_lists, width]
+    padded with -1 (width = the longest list, at least 1; ValueError above `cap`, its text ending in `what`), counts
+    int32 [n_lists].  extra: relevances shaped like ids; a fifth result is their float32 [n_lists, width], NaN padded."""
+    single = len(ids) == 0 or np.ndim(ids[0]) == 0
+    lists = [np.asarray(l, dtype=np.int64).reshape(-1) for l in ([ids] if single else ids)]
+    extras = None
+    if extra is not None:
+        extras = [np.asarray(e, dtype=np.float32).reshape(-1) for e in ([extra] if single else extra)]
+        if len(extras) != len(lists) or any(e.size != l.size for e, l in zip(extras, lists)):
+            raise ValueError("ids and rel must have the same shape")
+    width = max([int(l.size) for l in lists] + [1])
+    if width > cap:
+        raise ValueError(f"a list holds at most {cap} ids (got {width}){what}")
+    h_ids = np.full((len(lists), width), -1, dtype=np.int64)
+    for q, l in enumerate(lists):
+        h_ids[q, :l.size] = l
+    counts = np.asarray([l.size for l in lists], dtype=np.int32)
+    if extras is None:
+        return single, lists, h_ids, counts
+    h_extra = np.full((len(lists), width), np.nan, dtype=np.float32)
+    for q, e in enumerate(extras):
+        h_extra[q, :e.size] = e
+    return single, lists, h_ids, counts, h_extra
+
+
 class DenseIndex:
     """Exact cosine top-k over fp32 rows resident in one GPU's HBM."""
 
@@ -239,7 +270,7 @@ class DenseIndex:
         nq = int(d_queries.shape[0])
         _native.check(self._lib.crag_index_search_async(
             self._h, d_queries.data_ptr(), nq, int(k),
-            None if d_row_mask is None else d_row_mask.data_ptr(), int(mask_stride),
+            _opt_ptr(d_row_mask), int(mask_stride),
             d_out_ids.data_ptr(), d_out_scores.data_ptr(), d_out_counts.data_ptr(),
             ctypes.c_void_p(stream)), "crag_index_search_async")
 
@@ -252,7 +283,7 @@ class DenseIndex:
         nq = int(d_queries.shape[0])
         _native.check(self._lib.crag_index_search_pipelined(
             self._h, d_queries.data_ptr(), nq, int(k),
-            None if d_row_mask is None else d_row_mask.data_ptr(), int(mask_stride),
+            _opt_ptr(d_row_mask), int(mask_stride),
             d_out_ids.data_ptr(), d_out_scores.data_ptr(), d_out_counts.data_ptr(),
             ctypes.c_void_p(stream), 1 if inputs_ready else 0), "crag_index_search_pipelined")
 
@@ -274,8 +305,8 @@ class DenseIndex:
         nq, width = int(d_ids.shape[0]), int(d_ids.shape[1])
         _native.check(self._lib.crag_index_dedupe_async(
             self._h, d_ids.data_ptr(), d_counts.data_ptr(), nq, width, float(threshold), d_out_ids.data_ptr(),
-            d_out_counts.data_ptr(), None if d_out_dup_of is None else d_out_dup_of.data_ptr(),
-            None if d_out_sim is None else d_out_sim.data_ptr(), ctypes.c_void_p(stream)), "crag_index_dedupe_async")
+            d_out_counts.data_ptr(), _opt_ptr(d_out_dup_of), _opt_ptr(d_out_sim), ctypes.c_void_p(stream)),
+            "crag_index_dedupe_async")
 
     def dedupe(self, ids, threshold: float):
         """Host convenience over dedupe_async for one ranked list of ids (a flat sequence) or several (a sequence of
@@ -284,22 +315,13 @@ class DenseIndex:
         (NaN: kept) -- arrays for one list, lists of arrays for several.  Synchronises."""
         if torch is None:  # pragma: no cover
             raise _native.NativeLibraryError("DenseIndex.dedupe stages its buffers with torch")
-        single = len(ids) == 0 or np.ndim(ids[0]) == 0
-        lists = [np.asarray(ids, dtype=np.int64).reshape(-1)] if single else \
-            [np.asarray(l, dtype=np.int64).reshape(-1) for l in ids]
-        width = max([int(l.size) for l in lists] + [1])
-        if width > _native.CRAG_DEDUPE_MAX_WIDTH:
-            raise ValueError(f"a list holds at most {_native.CRAG_DEDUPE_MAX_WIDTH} ids (got {width})")
-        h_ids = np.full((len(lists), width), -1, dtype=np.int64)
-        for q, l in enumerate(lists):
-            h_ids[q, :l.size] = l
+        single, lists, h_ids, counts = _pad_lists(ids, _native.CRAG_DEDUPE_MAX_WIDTH)
         dev = torch.device("cuda", self.device)
-        d_ids = torch.from_numpy(h_ids).to(dev)
-        d_ct = torch.tensor([int(l.size) for l in lists], dtype=torch.int32, device=dev)
+        d_ids, d_ct = torch.from_numpy(h_ids).to(dev), torch.from_numpy(counts).to(dev)
         d_out = torch.empty_like(d_ids)
         d_oct = torch.empty_like(d_ct)
-        d_dup = torch.empty(len(lists), width, dtype=torch.int32, device=dev)
-        d_sim = torch.empty(len(lists), width, dtype=torch.float32, device=dev)
+        d_dup = torch.empty(h_ids.shape, dtype=torch.int32, device=dev)
+        d_sim = torch.empty(h_ids.shape, dtype=torch.float32, device=dev)
         self.dedupe_async(d_ids, d_ct, threshold, d_out, d_oct, d_dup, d_sim,
                           stream=torch.cuda.current_stream(dev).cuda_stream)
         dup, sim = d_dup.cpu().numpy(), d_sim.cpu().numpy()
@@ -331,7 +353,7 @@ class DenseIndex:
         _native.check(self._lib.crag_index_search_ids_async(
             self._h, d_queries.data_ptr(), nq, d_ids.data_ptr(), d_counts.data_ptr(), width, 0 if shared else width,
             int(k), d_out_ids.data_ptr(), d_out_scores.data_ptr(), d_out_counts.data_ptr(),
-            None if d_out_slot_scores is None else d_out_slot_scores.data_ptr(), scratch.data_ptr(),
+            _opt_ptr(d_out_slot_scores), scratch.data_ptr(),
             int(scratch.numel()) * scratch.element_size(), ctypes.c_void_p(stream)), "crag_index_search_ids_async")
 
     def search_ids(self, queries, ids, k: int, slot_scores: bool = False):
@@ -344,21 +366,14 @@ class DenseIndex:
         ptr, nq, keep = _as_f32_2d(queries, self.dim, "queries")
         if not 1 <= int(k) <= _native.CRAG_MAX_K:
             raise ValueError(f"k must be in [1, {_native.CRAG_MAX_K}] (got {k})")
-        shared = len(ids) == 0 or np.ndim(ids[0]) == 0
-        lists = [np.asarray(ids, dtype=np.int64).reshape(-1)] if shared else \
-            [np.asarray(l, dtype=np.int64).reshape(-1) for l in ids]
-        if not shared and len(lists) != nq:
+        if len(ids) and np.ndim(ids[0]) != 0 and len(ids) != nq:
             raise ValueError("per-query id lists must have one list per query")
-        width = max([int(l.size) for l in lists] + [1])
-        if width > _native.CRAG_SUBSET_MAX_WIDTH:
-            raise ValueError(f"a list holds at most {_native.CRAG_SUBSET_MAX_WIDTH} ids (got {width}): use a row_mask")
-        h_ids = np.full((len(lists), width), -1, dtype=np.int64)
-        for q, l in enumerate(lists):
-            h_ids[q, :l.size] = l
+        shared, _, h_ids, counts = _pad_lists(ids, _native.CRAG_SUBSET_MAX_WIDTH, ": use a row_mask")
+        width = h_ids.shape[1]
         dev = torch.device("cuda", self.device)
         d_q = keep.to(dev) if _is_torch(keep) else torch.from_numpy(keep).to(dev)
         d_ids = torch.from_numpy(h_ids[0] if shared else h_ids).to(dev)
-        d_ct = torch.tensor([int(l.size) for l in lists], dtype=torch.int32, device=dev)
+        d_ct = torch.from_numpy(counts).to(dev)
         out_ids = torch.empty(nq, int(k), dtype=torch.int64, device=dev)
         out_sc = torch.empty(nq, int(k), dtype=torch.float32, device=dev)
         out_ct = torch.empty(nq, dtype=torch.int32, device=dev)
@@ -392,11 +407,10 @@ class DenseIndex:
             if scratch is None:
                 scratch = self._mmr_scratch[(stream, nq, width)] = torch.empty(
                     self.mmr_scratch_bytes(nq, width), dtype=torch.uint8, device=d_ids.device)
-        opt = lambda t: None if t is None else t.data_ptr()   # noqa: E731
         _native.check(self._lib.crag_index_mmr_async(
             self._h, d_ids.data_ptr(), d_rel.data_ptr(), d_counts.data_ptr(), nq, width, float(lam), int(k),
-            d_out_ids.data_ptr(), d_out_rel.data_ptr(), opt(d_out_value), opt(d_out_slots), opt(d_out_sim_rows),
-            d_out_counts.data_ptr(), scratch.data_ptr(), int(scratch.numel()) * scratch.element_size(),
+            d_out_ids.data_ptr(), d_out_rel.data_ptr(), _opt_ptr(d_out_value), _opt_ptr(d_out_slots),
+            _opt_ptr(d_out_sim_rows), d_out_counts.data_ptr(), scratch.data_ptr(), int(scratch.numel()) * scratch.element_size(),
             ctypes.c_void_p(stream)), "crag_index_mmr_async")
 
     def mmr(self, ids, rel, lam: float, k: int):
@@ -405,29 +419,14 @@ class DenseIndex:
         order -- arrays for one list, lists of arrays for several.  Synchronises."""
         if torch is None:  # pragma: no cover
             raise _native.NativeLibraryError("DenseIndex.mmr stages its buffers with torch")
-        single = len(ids) == 0 or np.ndim(ids[0]) == 0
-        lists = [np.asarray(ids, dtype=np.int64).reshape(-1)] if single else \
-            [np.asarray(l, dtype=np.int64).reshape(-1) for l in ids]
-        rels = [np.asarray(rel, dtype=np.float32).reshape(-1)] if single else \
-            [np.asarray(r, dtype=np.float32).reshape(-1) for r in rel]
-        if len(rels) != len(lists) or any(r.size != l.size for r, l in zip(rels, lists)):
-            raise ValueError("ids and rel must have the same shape")
-        width = max([int(l.size) for l in lists] + [1])
-        if width > _native.CRAG_MMR_MAX_WIDTH:
-            raise ValueError(f"a list holds at most {_native.CRAG_MMR_MAX_WIDTH} ids (got {width})")
+        single, lists, h_ids, counts, h_rel = _pad_lists(ids, _native.CRAG_MMR_MAX_WIDTH, extra=rel)
         if not 1 <= int(k) <= _native.CRAG_MMR_MAX_WIDTH:
             raise ValueError(f"k must be in [1, {_native.CRAG_MMR_MAX_WIDTH}] (got {k})")
         if not 0.0 <= float(lam) <= 1.0:
             raise ValueError(f"lam must be finite, in [0, 1] (got {lam})")
         nq, k = len(lists), int(k)
-        h_ids = np.full((nq, width), -1, dtype=np.int64)
-        h_rel = np.full((nq, width), np.nan, dtype=np.float32)
-        for q, (l, r) in enumerate(zip(lists, rels)):
-            h_ids[q, :l.size] = l
-            h_rel[q, :r.size] = r
         dev = torch.device("cuda", self.device)
-        d_ids, d_rel = torch.from_numpy(h_ids).to(dev), torch.from_numpy(h_rel).to(dev)
-        d_ct = torch.tensor([int(l.size) for l in lists], dtype=torch.int32, device=dev)
+        d_ids, d_rel, d_ct = (torch.from_numpy(a).to(dev) for a in (h_ids, h_rel, counts))
         o_ids = torch.empty(nq, k, dtype=torch.int64, device=dev)
         o_rel = torch.empty(nq, k, dtype=torch.float32, device=dev)
         o_val = torch.empty(nq, k, dtype=torch.float32, device=dev)
@@ -465,8 +464,8 @@ class DenseIndex:
                                   device=d_queries.device)
         _native.check(self._lib.crag_index_search_grouped_async(
             self._h, d_queries.data_ptr(), nq, int(k), d_row_group.data_ptr(), int(n_groups), int(per_group),
-            None if d_row_mask is None else d_row_mask.data_ptr(), int(mask_stride), d_out_ids.data_ptr(),
-            d_out_scores.data_ptr(), None if d_out_groups is None else d_out_groups.data_ptr(), d_out_counts.data_ptr(),
+            _opt_ptr(d_row_mask), int(mask_stride), d_out_ids.data_ptr(),
+            d_out_scores.data_ptr(), _opt_ptr(d_out_groups), d_out_counts.data_ptr(),
             scratch.data_ptr(), int(scratch.numel()) * scratch.element_size(), ctypes.c_void_p(stream)),
             "crag_index_search_grouped_async")
 
