@@ -30,6 +30,14 @@ WHERE_MAX = 65535         # token positions at or above this are not indexed (po
 MAX_CLAUSES = 16          # constraint clauses per query (include/crag_dense.h CRAG_BM25_MAX_CLAUSES)
 MAX_PHRASE_TERMS = 8      # terms per phrase (CRAG_BM25_MAX_PHRASE)
 REQ_TERM, EXC_TERM, REQ_PHRASE, EXC_PHRASE, MATCH_NOTHING = 0, 1, 2, 3, 4   # clause kinds of the C ABI
+# prefix and fuzzy items (include/crag_dense.h states the rule at crag_bm25_expand_host)
+BM25_EXPAND_SLICE = 4096  # vocabulary terms per workgroup of the match kernel (csrc/crag_kernels.h BM25_EXPAND_SLICE)
+MAX_EXPANSIONS = 64       # kept terms per expanding item (CRAG_BM25_MAX_EXPANSIONS)
+MAX_EXPAND_ITEMS = 8      # expanding items per query (CRAG_BM25_MAX_EXPAND_ITEMS)
+MAX_PATTERNS = 512        # patterns per call of the expand entry (CRAG_BM25_MAX_PATTERNS)
+PREFIX, FUZZY1, FUZZY2 = 0, 1, 2            # kinds of an expanding item
+OPTIONAL, REQUIRED, EXCLUDED = 0, 1, 2      # its roles
+REQ_ANY, EXC_ANY = 0, 1                     # group kinds of crag_bm25_group_masks_host
 
 # [^\W_] is exactly str.isalnum() per character (the re module's \w is "isalnum() or '_'")
 _RUN = re.compile(r"[^\W_]+")
@@ -62,6 +70,10 @@ class ParsedQuery:
     clauses: Tuple[Tuple[int, Tuple[str, ...]], ...]
     bag: Tuple[str, ...]
     text: str
+    # the expanding items (parse_query(text, expand=True)) in item order: (role, kind, token), role one of
+    # OPTIONAL, REQUIRED, EXCLUDED, kind one of PREFIX, FUZZY1, FUZZY2.  Their tokens are neither in `bag` nor in
+    # `clauses`; `text` holds them, operator removed, unless excluded
+    expansions: Tuple[Tuple[int, int, str], ...] = ()
 
     @property
     def has_constraints(self) -> bool:
@@ -73,23 +85,48 @@ class ParsedQuery:
 _ITEM = re.compile(r'(?:(?<!\S)([+-]))?(?:"([^"]*)"?|([^\s"]+))')
 
 
-def parse_query(text: str) -> ParsedQuery:
+# an unquoted item that ends in one operator: `*`, `~`, `~1` or `~2` (the shortest text in front of it)
+_OPERATOR = re.compile(r"(.*?)(\*|~[12]?)\Z", re.S)
+_KIND_OF = {"*": PREFIX, "~": FUZZY1, "~1": FUZZY1, "~2": FUZZY2}
+
+
+def parse_query(text: str, expand: bool = False) -> ParsedQuery:
     """Items are separated by whitespace outside double quotes; `"` opens a quoted item (it also ends an unquoted one),
     an unclosed quote runs to the end.  An item may carry one prefix, `+` or `-`, directly in front of it, at the start
     of the string or after whitespace; anywhere else the character is text.  Every item's text goes through `tokenize`;
     an item without tokens is dropped.  Unquoted: every token is a term of the item's kind (`+` required, `-` excluded,
     none optional).  Quoted: one token is a term, more are a phrase, required unless prefixed `-`.  Nothing else is
-    syntax.  Raises QuerySyntaxError over 16 constraint clauses or 8 terms in a phrase."""
+    syntax, unless `expand`: then an unquoted item may end in one operator -- `*` prefix, `~` / `~1` fuzzy with distance
+    1, `~2` with distance 2 -- which counts only if the text in front of it tokenises to exactly one token (otherwise the
+    whole item is read as without `expand`); such an item goes to `expansions`, not to `bag` or `clauses`.
+    Raises QuerySyntaxError over 16 constraint clauses (required and excluded expanding items count), 8 terms in a
+    phrase or 8 expanding items."""
     clauses: List[Tuple[int, Tuple[str, ...]]] = []
     bag: List[str] = []
     kept: List[str] = []
+    expansions: List[Tuple[int, int, str]] = []
+    constrained = 0             # required and excluded expanding items
     for prefix, inside, bare in _ITEM.findall(text or ""):
         quoted = not bare           # (a bare item is never empty; a quoted one may be)
         raw = inside if quoted else bare
+        excluded = prefix == "-"
+        op = _OPERATOR.match(raw) if expand and not quoted else None
+        if op is not None:
+            front = tokenize(op.group(1))
+            if len(front) == 1:
+                role = EXCLUDED if excluded else REQUIRED if prefix == "+" else OPTIONAL
+                expansions.append((role, _KIND_OF[op.group(2)], front[0]))
+                constrained += role != OPTIONAL
+                if not excluded:
+                    kept.append(op.group(1).strip())
+                if len(expansions) > MAX_EXPAND_ITEMS:
+                    raise QuerySyntaxError(f"a query holds at most {MAX_EXPAND_ITEMS} prefix or fuzzy items")
+                if len(clauses) + constrained > MAX_CLAUSES:
+                    raise QuerySyntaxError(f"a query holds at most {MAX_CLAUSES} constraint clauses")
+                continue
         toks = tokenize(raw)
         if not toks:
             continue
-        excluded = prefix == "-"
         if quoted and len(toks) > 1:
             if len(toks) > MAX_PHRASE_TERMS:
                 raise QuerySyntaxError(f"a phrase holds at most {MAX_PHRASE_TERMS} terms ({len(toks)} given)")
@@ -101,9 +138,9 @@ def parse_query(text: str) -> ParsedQuery:
         if not excluded:
             bag.extend(toks)
             kept.append(raw.strip())
-        if len(clauses) > MAX_CLAUSES:
+        if len(clauses) + constrained > MAX_CLAUSES:
             raise QuerySyntaxError(f"a query holds at most {MAX_CLAUSES} constraint clauses")
-    return ParsedQuery(tuple(clauses), tuple(bag), " ".join(kept))
+    return ParsedQuery(tuple(clauses), tuple(bag), " ".join(kept), tuple(expansions))
 
 
 class Bm25Index:
@@ -261,6 +298,8 @@ class Bm25Index:
             self.d_post_off, self.d_post_where = dev(post_off), dev(post_where, np.int16)   # (bits of the uint16 values)
         self._scratch = {}
         self._clause_masks = {}
+        self._dictionary = None      # (d_term_ptr, d_term_bytes): uploaded by the first `expand`, dropped here
+        self._expand_scratch = {}
 
     def extend(self, texts: Sequence[str], ids: Sequence[int]) -> None:
         """Rows appended at the end (what the backfill does): only the new rows are tokenised; the device CSR is rebuilt
@@ -365,18 +404,162 @@ class Bm25Index:
         return (c_ptr, np.asarray(kinds, dtype=np.int32), np.asarray(ct_ptr, dtype=np.int32),
                 np.asarray(ct_terms, dtype=np.int32))
 
-    def search_query(self, query_texts: Sequence[str], k: int, row_mask=None, mask_stride: int = 0, stream: int = 0):
+    # ---- prefix and fuzzy items ----------------------------------------------------------------------
+    def term_strings(self) -> List[str]:
+        """The vocabulary's terms in term-id order (an index without a vocabulary: the decimal strings of the ids)."""
+        if isinstance(self.vocab, _DecimalVocab):
+            return [str(t) for t in range(len(self.vocab))]
+        terms: List[Optional[str]] = [None] * len(self.vocab)
+        for tok, t in self.vocab.items():
+            terms[t] = tok
+        if any(t is None for t in terms):
+            raise ValueError("the vocabulary's term ids must be 0 .. len(vocab) - 1, each once")
+        return terms
+
+    def _device_dictionary(self):
+        """d_term_ptr [V + 1] int64 and d_term_bytes, the UTF-8 bytes of the terms in term-id order: built and uploaded
+        on first use, dropped by `_upload` (so `extend` stays correct)."""
+        import torch
+        if getattr(self, "_dictionary", None) is None:
+            encoded = [t.encode("utf-8") for t in self.term_strings()]
+            term_ptr = np.zeros(len(encoded) + 1, dtype=np.int64)
+            np.cumsum(np.fromiter(map(len, encoded), dtype=np.int64, count=len(encoded)), out=term_ptr[1:])
+            flat = np.frombuffer(b"".join(encoded) or b"\0", dtype=np.uint8)
+            self._dictionary = (torch.from_numpy(term_ptr).to(self.device), torch.from_numpy(flat.copy()).to(self.device))
+        return self._dictionary
+
+    def expand(self, patterns: Sequence[Tuple[int, str]], stream: int = 0):
+        """The vocabulary terms that the patterns stand for: patterns are (kind, token) with kind PREFIX, FUZZY1 or
+        FUZZY2, at most 512 per call.  Returns per pattern (kept term ids int32, their distances int32, the number of all
+        matches): the first 64 matches by distance ascending, df descending, term id ascending (crag_bm25_expand_host).
+        One launch pair on `stream` and ONE stream synchronisation for the read-back."""
+        import torch
+
+        from .fusion import _on_stream
+        patterns = list(patterns)
+        if len(patterns) > MAX_PATTERNS:
+            raise ValueError(f"the expand entry takes at most {MAX_PATTERNS} patterns per call")
+        if not patterns:
+            return []
+        lib = _native.load()
+        encoded = [tok.encode("utf-8") for _, tok in patterns]
+        npat = len(patterns)
+        pat_ptr = np.zeros(npat + 1, dtype=np.int32)
+        np.cumsum([len(e) for e in encoded], out=pat_ptr[1:])
+        pat_bytes = np.frombuffer(b"".join(encoded) or b"\0", dtype=np.uint8)
+        pat_kind = np.asarray([kind for kind, _ in patterns], dtype=np.int32)
+        d_term_ptr, d_term_bytes = self._device_dictionary()
+        need = int(lib.crag_bm25_expand_scratch_bytes(self.n_terms, npat))
+        with _on_stream(stream, self.device):
+            scratch = self._expand_scratch.get(stream)
+            if scratch is None or scratch.numel() * 8 < need:
+                scratch = self._expand_scratch[stream] = torch.empty(max(need // 8, 1), dtype=torch.int64,
+                                                                     device=self.device)
+            # one buffer, one copy back: terms [np, 64] | dist [np, 64] | kept [np] | pad | total [np] int64
+            words = 2 * npat * MAX_EXPANSIONS + (npat + 1) // 2 * 2
+            out = torch.empty(words * 4 + npat * 8, dtype=torch.uint8, device=self.device)
+        base = out.data_ptr()
+        rc = lib.crag_bm25_expand_host(
+            d_term_ptr.data_ptr(), d_term_bytes.data_ptr(), self.d_post_ptr.data_ptr(), self.n_terms,
+            pat_ptr.ctypes.data, pat_bytes.ctypes.data, pat_kind.ctypes.data, npat, self._slot(stream),
+            scratch.data_ptr(), scratch.numel() * 8, base, base + npat * MAX_EXPANSIONS * 4,
+            base + 2 * npat * MAX_EXPANSIONS * 4, base + words * 4, ctypes.c_void_p(stream))
+        _native.check(rc, "crag_bm25_expand_host")
+        with _on_stream(stream, self.device):
+            host = out.cpu().numpy()    # (synchronises the stream)
+        i32 = host[:words * 4].view(np.int32)
+        terms = i32[:npat * MAX_EXPANSIONS].reshape(npat, MAX_EXPANSIONS)
+        dist = i32[npat * MAX_EXPANSIONS:2 * npat * MAX_EXPANSIONS].reshape(npat, MAX_EXPANSIONS)
+        kept = i32[2 * npat * MAX_EXPANSIONS:2 * npat * MAX_EXPANSIONS + npat]
+        total = host[words * 4:].view(np.int64)
+        return [(terms[i, :kept[i]].copy(), dist[i, :kept[i]].copy(), int(total[i])) for i in range(npat)]
+
+    def expanded_terms(self, parsed_list: Sequence[ParsedQuery], expansions):
+        """The weights of DESIGN.md 4.7d for a batch: `expansions` holds the result of `expand` for every expanding item
+        of the batch, in query order and item order.  Returns the arrays of `query_terms` (q_ptr, term ids ascending
+        inside a query, fp32 weights): today's qtf * idf * (k1 + 1) for a term of the plain bag, plus base_j * 2^-d for
+        every non-excluded item j that keeps the term, in item order, fp64, rounded once."""
+        q_ptr = np.zeros(len(parsed_list) + 1, dtype=np.int32)
+        terms: List[int] = []
+        weights: List[float] = []
+        get = self.vocab.get
+        n = float(self.n)
+        at = 0
+        for q, parsed in enumerate(parsed_list):
+            qtf: Dict[int, int] = {}
+            for tok in parsed.bag:
+                t = get(tok)
+                if t is not None:
+                    qtf[t] = qtf.get(t, 0) + 1
+            w: Dict[int, float] = {}
+            for t, c in qtf.items():
+                df = float(self.df[t])
+                w[t] = float(c) * float(np.log(1.0 + (n - df + 0.5) / (df + 0.5))) * (K1 + 1.0)
+            for role, _, _ in parsed.expansions:
+                ids, dist, _ = expansions[at]
+                at += 1
+                if role == EXCLUDED or len(ids) == 0:
+                    continue
+                df = float(self.df[ids].max())
+                base = float(np.log(1.0 + (n - df + 0.5) / (df + 0.5))) * (K1 + 1.0)
+                for t, d in zip(ids.tolist(), dist.tolist()):
+                    w[t] = w.get(t, 0.0) + base * 2.0 ** (-d)
+            ordered = sorted(w)
+            terms.extend(ordered)
+            weights.extend(w[t] for t in ordered)
+            q_ptr[q + 1] = len(terms)
+        return q_ptr, np.asarray(terms, dtype=np.int32), np.asarray(weights, dtype=np.float64).astype(np.float32)
+
+    @staticmethod
+    def group_arrays(parsed_list: Sequence[ParsedQuery], expansions):
+        """The required and excluded expanding items of a batch as the host arrays of crag_bm25_group_masks_host: g_ptr
+        [nq + 1], g_kind, gt_ptr [n_groups + 1], gt_terms (all int32).  A required item without a match stays as an empty
+        group (it matches nothing); an excluded one without a match is dropped."""
+        g_ptr = np.zeros(len(parsed_list) + 1, dtype=np.int32)
+        kinds: List[int] = []
+        gt_ptr: List[int] = [0]
+        gt_terms: List[int] = []
+        at = 0
+        for q, parsed in enumerate(parsed_list):
+            for role, _, _ in parsed.expansions:
+                ids = expansions[at][0]
+                at += 1
+                if role == OPTIONAL or (role == EXCLUDED and len(ids) == 0):
+                    continue
+                kinds.append(REQ_ANY if role == REQUIRED else EXC_ANY)
+                gt_terms.extend(ids.tolist())
+                gt_ptr.append(len(gt_terms))
+            g_ptr[q + 1] = len(kinds)
+        return (g_ptr, np.asarray(kinds, dtype=np.int32), np.asarray(gt_ptr, dtype=np.int32),
+                np.asarray(gt_terms, dtype=np.int32))
+
+    def _mask_buffer(self, stream: int, which: int, stride: int):
+        import torch
+
+        from .fusion import _on_stream
+        with _on_stream(stream, self.device):
+            buf = self._clause_masks.get((stream, which) if which else stream)
+            if buf is None:
+                buf = self._clause_masks[(stream, which) if which else stream] = torch.empty(
+                    MAX_QUERIES * stride, dtype=torch.uint8, device=self.device)
+        return buf
+
+    def search_query(self, query_texts: Sequence[str], k: int, row_mask=None, mask_stride: int = 0, stream: int = 0,
+                     expand: bool = False):
         """`search` for queries in the clause syntax of `parse_query` (+required, -excluded, "quoted phrase"): the rows
         that pass every clause and the mask, ranked by the BM25 score of the query's non-excluded tokens.  A batch
         without any constraint IS `search` (same calls, same bits).  Otherwise one launch turns the clauses into a row
         mask per query (crag_bm25_clause_masks_host, into a buffer this stream keeps) and `search_terms` scores under it.
+        expand: also read `*`, `~`, `~1`, `~2` behind a token.  A batch without such an item makes exactly
+        the calls above.  Otherwise: `expand` (one stream synchronisation), the required and excluded items as any-of row
+        masks (crag_bm25_group_masks_host), the clause masks on top of them when plain clauses exist, and `search_terms`
+        with the rule's weights.
         Raises QuerySyntaxError for a query over the limits, ValueError for a phrase on an index without positions."""
-        import torch
-
-        from .fusion import _on_stream
         if len(query_texts) > MAX_QUERIES:
             raise ValueError("the BM25 lane takes at most 64 queries per call")
-        parsed = [parse_query(text) for text in query_texts]
+        parsed = [parse_query(text, expand=expand) for text in query_texts]
+        if any(p.expansions for p in parsed):
+            return self._search_expanded(parsed, k, row_mask, mask_stride, stream)
         if not any(p.has_constraints for p in parsed):
             return self.search(query_texts, k, row_mask=row_mask, mask_stride=mask_stride, stream=stream)
         c_ptr, c_kind, ct_ptr, ct_terms = self.clause_arrays(parsed)
@@ -384,20 +567,45 @@ class Bm25Index:
         if self.n == 0:                                              #  themselves)
             return self.search_terms(*bags, k, stream=stream)
         stride = (self.n + 31) // 32 * 4
-        with _on_stream(stream, self.device):
-            buf = self._clause_masks.get(stream)
-            if buf is None:
-                buf = self._clause_masks[stream] = torch.empty(MAX_QUERIES * stride, dtype=torch.uint8, device=self.device)
+        buf = self._mask_buffer(stream, 0, stride)
+        self._clause_launch(c_ptr, c_kind, ct_ptr, ct_terms, len(parsed), row_mask, mask_stride, buf, stride, stream)
+        return self.search_terms(*bags, k, row_mask=buf, mask_stride=stride, stream=stream)
+
+    def _clause_launch(self, c_ptr, c_kind, ct_ptr, ct_terms, nq, in_mask, in_stride, buf, stride, stream) -> None:
         rc = _native.load().crag_bm25_clause_masks_host(
             self.d_post_ptr.data_ptr(), self.d_post_pos.data_ptr(),
             None if self.d_post_off is None else self.d_post_off.data_ptr(),
             None if self.d_post_where is None else self.d_post_where.data_ptr(), self.n, self.n_terms,
             c_ptr.ctypes.data, c_kind.ctypes.data if c_kind.size else None, ct_ptr.ctypes.data,
-            ct_terms.ctypes.data if ct_terms.size else None, len(parsed),
-            None if row_mask is None else row_mask.data_ptr(), int(mask_stride), self._slot(stream), buf.data_ptr(), stride,
+            ct_terms.ctypes.data if ct_terms.size else None, nq,
+            None if in_mask is None else in_mask.data_ptr(), int(in_stride), self._slot(stream), buf.data_ptr(), stride,
             ctypes.c_void_p(stream))
         _native.check(rc, "crag_bm25_clause_masks_host")
-        return self.search_terms(*bags, k, row_mask=buf, mask_stride=stride, stream=stream)
+
+    def _search_expanded(self, parsed, k, row_mask, mask_stride, stream):
+        """`search_query` for a batch with expanding items: expand -> group masks -> clause masks -> search_terms."""
+        expansions = self.expand([(kind, tok) for p in parsed for _, kind, tok in p.expansions], stream=stream)
+        bags = self.expanded_terms(parsed, expansions)
+        clauses = self.clause_arrays(parsed) if any(p.has_constraints for p in parsed) else None
+        if self.n == 0:
+            return self.search_terms(*bags, k, stream=stream)
+        g_ptr, g_kind, gt_ptr, gt_terms = self.group_arrays(parsed, expansions)
+        stride = (self.n + 31) // 32 * 4
+        mask, in_stride = row_mask, int(mask_stride)
+        if g_kind.size:
+            buf = self._mask_buffer(stream, 1, stride)
+            rc = _native.load().crag_bm25_group_masks_host(
+                self.d_post_ptr.data_ptr(), self.d_post_pos.data_ptr(), self.n, self.n_terms, g_ptr.ctypes.data,
+                g_kind.ctypes.data, gt_ptr.ctypes.data, gt_terms.ctypes.data if gt_terms.size else None, len(parsed),
+                None if mask is None else mask.data_ptr(), in_stride, self._slot(stream), buf.data_ptr(), stride,
+                ctypes.c_void_p(stream))
+            _native.check(rc, "crag_bm25_group_masks_host")
+            mask, in_stride = buf, stride
+        if clauses is not None:     # (the group mask is the clause launch's input: in and out must not overlap)
+            buf = self._mask_buffer(stream, 0, stride)
+            self._clause_launch(*clauses, len(parsed), mask, in_stride, buf, stride, stream)
+            mask, in_stride = buf, stride
+        return self.search_terms(*bags, k, row_mask=mask, mask_stride=in_stride, stream=stream)
 
     def search_terms(self, q_ptr, terms, weights, k: int, row_mask=None, mask_stride: int = 0, stream: int = 0):
         """`search` for queries that are term ids and weights already (the arrays of `query_terms`)."""

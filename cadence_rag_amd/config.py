@@ -65,6 +65,10 @@ class Settings:
     # self-defined rule, not Tantivy's parser).  Phrases need lanes built with positions (build_bm25_lane(...,
     # positions=True)).  Off: the query string is a bag of tokens and nothing is launched
     bm25_query_syntax: bool = False
+    # prefix and fuzzy items of that syntax (`deploy*`, `kubernets~`, `kubernets~2`: parse_query(text, expand=True),
+    # DESIGN.md 4.7d): the word lane expands them over its vocabulary on the GPU, one stream synchronisation per query that
+    # holds one.  Takes effect only together with bm25_query_syntax.  Off: `*` and `~` separate tokens as ever
+    bm25_query_expand: bool = False
     # /answer (PHASED_PLAN.md:318-326): "" = off, "native" = the in-process Qwen3Generator, http(s) = an OpenAI-compatible
     # chat-completions service
     llm_base_url: str = ""

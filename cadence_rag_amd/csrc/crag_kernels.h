@@ -247,6 +247,52 @@ struct Bm25ClauseParams {
 };
 hipError_t launch_bm25_clause(const Bm25ClauseParams &p, hipStream_t st);
 
+// ---- BM25 prefix and fuzzy terms expanded over the vocabulary (crag_bm25_expand.hip) ----
+constexpr int BM25_EXPAND_SLICE = 4096;             // vocabulary terms per workgroup of the match kernel
+constexpr int BM25_EXPAND_KEEP = 64;                // kept expansions per pattern (CRAG_BM25_MAX_EXPANSIONS)
+constexpr int BM25_EXPAND_MAX_PATTERNS = 512;       // patterns per call
+constexpr int BM25_EXPAND_MAX_BYTES = 255;          // bytes per pattern (the tokenizer's limit)
+constexpr int BM25_EXPAND_PREFIX = 0, BM25_EXPAND_FUZZY1 = 1, BM25_EXPAND_FUZZY2 = 2;
+constexpr int BM25_GROUP_MAX = 16;                  // any-of groups per query
+constexpr int BM25_GROUP_REQ = 0, BM25_GROUP_EXC = 1;
+
+struct Bm25ExpandParams {
+    const int64_t *term_ptr;     // [V + 1] byte offsets of the terms in term_bytes
+    const uint8_t *term_bytes;   // UTF-8, term-id order
+    const int64_t *post_ptr;     // [V + 1]: df(t) = post_ptr[t + 1] - post_ptr[t]
+    const int32_t *pat_ptr;      // [np + 1] byte offsets of the patterns in pat_bytes
+    const int32_t *pat_kind;     // [np] BM25_EXPAND_*
+    const uint8_t *pat_bytes;
+    uint64_t *slice_keys;        // [np][n_slices][BM25_EXPAND_KEEP] sorted descending, 0 padded
+    int32_t *slice_count;        // [np][n_slices] matches of the slice
+    int32_t *out_terms;          // [np][BM25_EXPAND_KEEP] -1 padded
+    int32_t *out_dist;           // [np][BM25_EXPAND_KEEP] -1 padded
+    int32_t *out_kept;           // [np]
+    int64_t *out_total;          // [np]
+    int64_t n_terms;
+    int n_slices;
+    int np;
+    int pat_chunk;               // patterns per workgroup of the match kernel (blockIdx.y picks the chunk)
+};
+int64_t bm25_expand_scratch_bytes(int64_t n_terms, int np);
+hipError_t launch_bm25_expand(const Bm25ExpandParams &p, hipStream_t st);
+
+struct Bm25GroupParams {
+    const int64_t *post_ptr;     // [V + 1]
+    const int32_t *post_pos;     // [nnz] row positions, ascending inside a term
+    const int32_t *g_ptr;        // [nq + 1] groups of query q: [g_ptr[q], g_ptr[q + 1]), at most BM25_GROUP_MAX
+    const int32_t *g_kind;       // [n_groups] BM25_GROUP_*
+    const int32_t *gt_ptr;       // [n_groups + 1] terms of group g: gt_terms[gt_ptr[g] .. gt_ptr[g + 1]), at most 64
+    const int32_t *gt_terms;
+    const uint32_t *in;          // nullable: every row below n is admitted
+    int64_t in_stride_w;         // mask words per input run, 0: one run shared by all queries
+    uint32_t *out;               // [nq][stride_w]
+    int64_t stride_w;
+    int64_t n, n_words;
+    int nq;
+};
+hipError_t launch_bm25_groups(const Bm25GroupParams &p, hipStream_t st);
+
 
 // ---- near-duplicate suppression of ranked lists (crag_dedupe.hip) ----
 struct DedupeParams {

@@ -300,8 +300,13 @@ class HybridSearcher:
 
     def __init__(self, index, tech_index: "TechTokenIndex | None" = None, *, dense_k: int = 50, tech_k: int = 50,
                  rrf_k: int = DEFAULT_RRF_K, verify_tokens: bool = False, overlap_lanes: bool = True,
-                 bm25_index=None, bm25_k: int = 50, dedupe_cosine: "float | None" = None) -> None:
-        """dedupe_cosine: when set (a cosine in (-1, 1]), the fused list is deduped on the same stream behind the
+                 bm25_index=None, bm25_k: int = 50, dedupe_cosine: "float | None" = None,
+                 bm25_query_syntax: bool = False, bm25_query_expand: bool = False) -> None:
+        """bm25_query_syntax: the native BM25 lane reads `query_texts` in the clause syntax (Bm25Index.search_query:
+        +required, -excluded, "quoted phrase") instead of as bags of tokens; bm25_query_expand: with it,
+        also `*` and `~` behind a token (prefix and fuzzy items, DESIGN.md 4.7d: one stream synchronisation per step whose
+        batch holds one).  Both off by default: the lane is `search`, as ever.
+        dedupe_cosine: when set (a cosine in (-1, 1]), the fused list is deduped on the same stream behind the
         fusion kernel (DenseIndex.dedupe_async: an item is dropped iff a KEPT earlier item of its list is at least
         that similar to it): "ids" and "counts" of the result are the deduped ones, "scores" and "lanes" are compacted
         to match, "dup_of" / "dup_sim" tell per FUSED slot which slot suppressed it.  A fused width above 256 is then a
@@ -319,6 +324,8 @@ class HybridSearcher:
         self.overlap_lanes = bool(overlap_lanes)
         self.dense_k, self.tech_k, self.rrf_k = int(dense_k), int(tech_k), int(rrf_k)
         self.bm25_index, self.bm25_k = bm25_index, int(bm25_k)
+        self.bm25_query_syntax = bool(bm25_query_syntax)
+        self.bm25_query_expand = bool(bm25_query_expand) and self.bm25_query_syntax
         self.dedupe_cosine = None if dedupe_cosine is None else float(dedupe_cosine)
         self._dedupe_out: dict = {}  # per (stream, batch size, out_k): the deduped lists and the compaction's scratch
         self._dense_out: dict = {}  # per (stream, batch size): results of calls on different streams stay apart
@@ -394,8 +401,13 @@ class HybridSearcher:
         lanes = []
         bm25_native = None
         if bm25 is None and self.bm25_index is not None and query_texts is not None:
-            bm25_native = self.bm25_index.search(query_texts, self.bm25_k, row_mask=row_mask, mask_stride=mask_stride,
-                                                 stream=stream)
+            if self.bm25_query_syntax:
+                more = {"expand": True} if self.bm25_query_expand else {}
+                bm25_native = self.bm25_index.search_query(query_texts, self.bm25_k, row_mask=row_mask,
+                                                           mask_stride=mask_stride, stream=stream, **more)
+            else:
+                bm25_native = self.bm25_index.search(query_texts, self.bm25_k, row_mask=row_mask,
+                                                     mask_stride=mask_stride, stream=stream)
             bm25 = (bm25_native[0], bm25_native[2])
         if bm25 is not None:
             lanes.append(bm25)

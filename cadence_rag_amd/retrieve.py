@@ -1038,7 +1038,8 @@ class GpuRetrieveBackend(RetrieveBackend):
         string as a bag of tokens.  Logged once per request: the lanes of one request ask with the same string."""
         from .bm25 import QuerySyntaxError, parse_query
         try:
-            return parse_query(query)
+            # (the keyword only when the setting is on: prefix and fuzzy items, DESIGN.md 4.7d)
+            return parse_query(query, expand=True) if settings.bm25_query_expand else parse_query(query)
         except QuerySyntaxError as exc:
             if getattr(self, "_syntax_logged", None) != query:
                 self._syntax_logged = query
@@ -1064,7 +1065,9 @@ class GpuRetrieveBackend(RetrieveBackend):
         lane = lanes[name] = getattr(table, sync)(fn)
         d_mask = self._lane_mask(table, lane, filters, call_ids)
         search = lane.search_query if parsed is not None and field == "bm25" else lane.search
-        ids, scores, counts = search([query], min(int(limit), _native_max_k()), row_mask=d_mask, mask_stride=0)
+        # (a duck-typed lane's search_query may not know the keyword: it is passed only when the setting is on)
+        more = {"expand": True} if parsed is not None and field == "bm25" and settings.bm25_query_expand else {}
+        ids, scores, counts = search([query], min(int(limit), _native_max_k()), row_mask=d_mask, mask_stride=0, **more)
         n = int(counts[0])
         pos_of = table._positions()
         out = []

@@ -423,7 +423,8 @@ int crag_bm25_lane_host(const int64_t *d_post_ptr, const int32_t *d_post_pos, co
  *   optional (`+foo-bar` is two required terms).
  *   A quoted item: one token makes a term clause, two or more make a phrase clause; either is required unless the item
  *   is prefixed `-` (then excluded).  An unprefixed quoted phrase is a REQUIREMENT (in Tantivy it is a SHOULD clause with
- *   a phrase score).  Nothing else is syntax: `field:`, `*`, `~` and parentheses separate tokens as before.
+ *   a phrase score).  Nothing else is syntax: `field:`, `*`, `~` and parentheses separate tokens as before -- `*` and `~`
+ *   unless `expand` (parse_query(text, expand=True), crag_bm25_expand_host below).
  * Matching.  A row passes a query iff its input mask bit is set, it holds every required term, no excluded term, every
  *   required phrase and no excluded phrase.  A row holds the phrase t0 .. t(m-1) iff some token position p exists with
  *   token t_i at position p + i for every i.  Positions index the tokens the tokenizer keeps for that row (they count as
@@ -467,6 +468,84 @@ int crag_bm25_clause_masks_host(const int64_t *d_post_ptr, const int32_t *d_post
                                 const int32_t *h_c_ptr, const int32_t *h_c_kind, const int32_t *h_ct_ptr,
                                 const int32_t *h_ct_terms, int nq, const uint8_t *d_in_mask, int64_t in_stride,
                                 crag_upload_slot *slot, uint8_t *d_out_mask, int64_t mask_stride, void *stream);
+
+/* Prefix and fuzzy terms of the BM25 lane, expanded over the vocabulary on the device.  `deploy*` stands
+ * for the vocabulary terms that begin with "deploy", `kubernets~` for those within edit distance 1 of "kubernets".  The
+ * reference's pg_search would read `*` and `~` with Tantivy's parser; the rule here is this tree's own, NOT parity.
+ * Parsing (host, cadence_rag_amd.bm25.parse_query(text, expand=True); without `expand` nothing below is syntax):
+ *   An UNQUOTED item (behind its optional `+` / `-` prefix) may end in ONE operator: `*` (a prefix item, kind 0), `~` or
+ *   `~1` (a fuzzy item of distance 1, kind 1), `~2` (distance 2, kind 2).  The operator counts only if the text in front
+ *   of it goes through the tokenizer to EXACTLY ONE token; otherwise the whole item is read by the rule of
+ *   crag_bm25_clause_masks_host: `b)*` is the prefix item "b", `~2` alone is the text "2", `foo-bar*` is the two plain
+ *   tokens "foo" and "bar", `x~3` and `x~0` are plain text, `x**` is the prefix item "x" (the last `*` is the operator,
+ *   the one in front of it separates tokens as ever).  Nothing inside quotes is syntax.  `+` makes the item required, `-`
+ *   excluded, none optional.  The item's token is neither in the scored bag nor a clause of the clause entry; the text
+ *   handed to a lane without clauses (the trigram field) holds it, operator removed, unless the item is excluded.
+ *   Limits: at most CRAG_BM25_MAX_EXPAND_ITEMS expanding items per query; required and excluded expanding items count
+ *   towards the CRAG_BM25_MAX_CLAUSES constraint clauses of the query.
+ * Matching is over the Unicode code points of the (lower-cased) token and of the vocabulary's terms.
+ *   Prefix: the term's code points begin with the pattern's; the term equal to the pattern is included; every match has
+ *   distance 0.
+ *   Fuzzy: the plain Levenshtein distance (insertions, deletions and substitutions of one code point cost 1 each, so a
+ *   transposition of two neighbours costs 2) is at most d; the term equal to the pattern is included, distance 0.
+ *   A pattern is 1 to 255 bytes of UTF-8 (the tokenizer's limit); there is no other length limit.
+ * Kept expansions.  Per pattern the first CRAG_BM25_MAX_EXPANSIONS matches are kept in this order: distance ascending,
+ *   then df descending (df(t) = d_post_ptr[t + 1] - d_post_ptr[t]), then term id ascending.  The number of ALL matches is
+ *   reported beside them.  DEPARTURE: matches beyond the 64th take no part in scoring or in the item's clause (Tantivy's
+ *   fuzzy and prefix queries expand to 50 terms by default and rank them differently).
+ * Clauses (crag_bm25_group_masks_host).  A required expanding item passes the rows that hold AT LEAST ONE of its kept terms;
+ *   an excluded item fails the rows that hold ANY of them.  An item without a match behaves as an unknown token does: a
+ *   required one makes the query match nothing, an excluded or optional one is dropped.
+ * Scoring.  Excluded items score nothing.  For an item j that is not excluded, with kept terms T_j:
+ *     df*    = the largest df over T_j
+ *     base_j = ln(1 + (N - df* + 0.5) / (df* + 0.5)) * (k1 + 1)                       (fp64)
+ *   and a term of T_j at distance d contributes base_j * 2^(-d).  The weight of a term is the lane's qtf * idf * (k1 + 1)
+ *   (one product, when the term is in the plain bag) plus the contributions of the items in item order, all in fp64,
+ *   rounded ONCE to fp32; terms reach crag_bm25_lane_host in ascending id.  Its kernels are untouched.
+ *
+ * crag_bm25_expand_host:
+ *   d_term_ptr [n_terms + 1] int64, d_term_bytes: the UTF-8 bytes of the terms in term-id order, term t at
+ *               d_term_bytes[d_term_ptr[t] .. d_term_ptr[t + 1]); d_post_ptr [n_terms + 1] as for crag_bm25_lane_host
+ *   Patterns from the HOST in CSR form: h_pat_ptr [n_patterns + 1] int32 byte offsets (h_pat_ptr[0] = 0), h_pat_bytes,
+ *               h_pat_kind [n_patterns] (0 prefix, 1 fuzzy 1, 2 fuzzy 2); 0 <= n_patterns <= CRAG_BM25_MAX_PATTERNS
+ *   slot        an upload slot as for crag_tech_lane_host: ONE host-to-device copy per call
+ *   d_scratch   crag_bm25_expand_scratch_bytes(n_terms, n_patterns) bytes (-1: arguments out of range), 8-byte aligned
+ *   outputs (device): d_out_terms [n_patterns, 64] int32 kept term ids in the order above, -1 padded; d_out_dist
+ *               [n_patterns, 64] int32 their distances, -1 padded; d_out_kept [n_patterns] int32; d_out_total [n_patterns]
+ *               int64, the number of all matches
+ * Everything is enqueued on `stream`, no host synchronisation; the output depends on the input alone, whatever the slice
+ * size or the grid.  n_patterns == 0 is CRAG_OK and writes nothing; n_terms == 0 writes the padding and zero counts.
+ * CRAG_EINVAL with a message that contains "bm25_expand_host", checked before any HIP call, nothing enqueued: a NULL
+ * required pointer, n_patterns outside [0, 512], n_terms outside [0, 2^31), h_pat_ptr not ascending from 0, an empty
+ * pattern or one above 255 bytes, an unknown kind, misaligned arrays, a scratch that is too small or misaligned.
+ *
+ * crag_bm25_group_masks_host: the any-of clauses of up to 64 queries as row masks.
+ *   Groups from the HOST in CSR form: h_g_ptr [nq + 1] int32 (h_g_ptr[0] = 0; at most 16 groups per query), h_g_kind
+ *               [n_groups] -- 0 required-any, 1 excluded-any --, h_gt_ptr [n_groups + 1] int32 (h_gt_ptr[0] = 0; 0 to 64
+ *               terms per group), h_gt_terms: term ids.
+ *   out = in_mask AND (for every required group: the OR of its terms' rows) AND NOT (the OR of the excluded groups'
+ *   terms' rows).  An empty required group matches nothing; an empty excluded group has no effect.
+ *   d_in_mask / in_stride / d_out_mask / mask_stride / slot: the contract of crag_bm25_clause_masks_host, word for word --
+ *   every byte of every run is written with plain stores (never OR), bits at positions >= n_rows and the bytes up to
+ *   mask_stride are 0, in_stride 0 is one shared input run, a query without groups copies its input, in and out must not
+ *   overlap.  Everything is enqueued on `stream`.
+ * CRAG_EINVAL with a message that contains "bm25_group_masks_host", checked before any HIP call, nothing enqueued: a NULL
+ * required pointer, nq outside 1..64, n_rows or n_terms outside [0, 2^31), bad mask_stride or in_stride, a misaligned
+ * mask, h_g_ptr / h_gt_ptr not ascending from 0, an unknown kind, a term id outside [0, n_terms), a group of more than 64
+ * terms, more than 16 groups in a query.  n_rows == 0 is CRAG_OK (the runs are zeroed when mask_stride > 0). */
+#define CRAG_BM25_MAX_EXPANSIONS   64
+#define CRAG_BM25_MAX_EXPAND_ITEMS 8
+#define CRAG_BM25_MAX_PATTERNS     512
+int64_t crag_bm25_expand_scratch_bytes(int64_t n_terms, int n_patterns);
+int crag_bm25_expand_host(const int64_t *d_term_ptr, const uint8_t *d_term_bytes, const int64_t *d_post_ptr,
+                          int64_t n_terms, const int32_t *h_pat_ptr, const uint8_t *h_pat_bytes,
+                          const int32_t *h_pat_kind, int n_patterns, crag_upload_slot *slot, void *d_scratch,
+                          int64_t scratch_bytes, int32_t *d_out_terms, int32_t *d_out_dist, int32_t *d_out_kept,
+                          int64_t *d_out_total, void *stream);
+int crag_bm25_group_masks_host(const int64_t *d_post_ptr, const int32_t *d_post_pos, int64_t n_rows, int64_t n_terms,
+                               const int32_t *h_g_ptr, const int32_t *h_g_kind, const int32_t *h_gt_ptr,
+                               const int32_t *h_gt_terms, int nq, const uint8_t *d_in_mask, int64_t in_stride,
+                               crag_upload_slot *slot, uint8_t *d_out_mask, int64_t mask_stride, void *stream);
 
 /* Character-trigram field of the BM25 lane: the inverted CSR crag_bm25_lane_host scores, built on the device from the
  * rows' bytes (cadence_rag_amd.ngram.NgramIndex drives it).  Stands in for the reference's second index over every
