@@ -85,6 +85,8 @@ SIGNATURES = {
                                          _P]),
     "crag_bm25_group_masks_host": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _P, _P, _P, _P, _c.c_int, _P, _c.c_int64,
                                               _P, _P, _c.c_int64, _P]),
+    "crag_bm25_snippets_host": (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int64, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _P,
+                                           _P, _P, _P, _P, _P]),
     "crag_ngram_scratch_bytes": (_c.c_int64, [_c.c_int64, _c.c_int64]),
     "crag_ngram_extract": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _P, _P, _P, _P, _c.c_int64, _P]),
     "crag_ngram_heads": (_c.c_int, [_P, _P, _c.c_int64, _P, _P]),

@@ -27,6 +27,8 @@ MAX_QUERIES = 64
 MAX_TOKEN_BYTES = 255
 TF_MAX = 65535            # tf is stored in 16 bits, saturating
 WHERE_MAX = 65535         # token positions at or above this are not indexed (post_where is 16 bits wide)
+SNIPPET_MAX_TERMS = 64    # term slots per query of the snippet windows (CRAG_BM25_SNIPPET_MAX_TERMS)
+SNIPPET_STAGE = 1024      # positions of one (query, row) pair the snippet kernel keeps in LDS (BM25_SNIPPET_STAGE)
 MAX_CLAUSES = 16          # constraint clauses per query (include/crag_dense.h CRAG_BM25_MAX_CLAUSES)
 MAX_PHRASE_TERMS = 8      # terms per phrase (CRAG_BM25_MAX_PHRASE)
 REQ_TERM, EXC_TERM, REQ_PHRASE, EXC_PHRASE, MATCH_NOTHING = 0, 1, 2, 3, 4   # clause kinds of the C ABI
@@ -639,6 +641,90 @@ class Bm25Index:
             ctypes.c_void_p(stream))
         _native.check(rc, "crag_bm25_lane_host")
         return out_ids, out_scores, out_counts
+
+    # ---- query-aware snippet windows ---------------------------------------------------------------
+    def snippet_terms(self, query_texts: Sequence[str]):
+        """The term slots of `snippet_windows`: the bag reading of every query -- `query_terms` of the non-excluded
+        tokens of the clause syntax (required terms and phrase members count as plain terms; a query over the syntax's
+        limits is tokenised as it stands) --, cut to the SNIPPET_MAX_TERMS heaviest slots of a query, equal weights by
+        the lower term id, the kept slots back in ascending term-id order."""
+        bags = []
+        for text in query_texts:
+            try:
+                bags.append(" ".join(parse_query(text).bag))
+            except QuerySyntaxError:
+                bags.append(text)
+        return heaviest_slots(*self.query_terms(bags), SNIPPET_MAX_TERMS)
+
+    def snippet_windows(self, query_texts: Sequence[str], row_ids_per_query: Sequence[Sequence[int]], window: int,
+                        stream: int = 0):
+        """For every query and every row id listed for it: the window of `window` tokens of the row that holds the most of
+        the query, by the rule of crag_bm25_snippets_host (include/crag_dense.h).  Returns CUDA tensors laid out along
+        r_ptr, the running count of the lists: start int32 (-1: no query term in the row), last int32, score fp32, covered
+        int64 (the bits of the rule's uint64: bit j is slot j of `snippet_terms`).  One upload and one launch on `stream`.
+        Raises ValueError for an id the index does not hold and for an index built without positions."""
+        if not self.positions:
+            raise ValueError("snippet windows need an index built with positions=True")
+        if len(query_texts) != len(row_ids_per_query):
+            raise ValueError("one list of row ids per query")
+        r_ptr = np.zeros(len(query_texts) + 1, dtype=np.int32)
+        np.cumsum([len(ids) for ids in row_ids_per_query], out=r_ptr[1:])
+        flat = np.asarray([rid for ids in row_ids_per_query for rid in ids], dtype=np.int64)
+        rows = np.searchsorted(self.ids, flat)
+        if flat.size and (np.any(rows >= self.ids.size) or np.any(self.ids[np.minimum(rows, self.ids.size - 1)] != flat)):
+            raise ValueError("snippet_windows: a row id the index does not hold")
+        return self.snippet_windows_terms(*self.snippet_terms(query_texts), r_ptr, rows.astype(np.int32), window,
+                                          stream=stream)
+
+    def snippet_windows_terms(self, q_ptr, terms, weights, r_ptr, rows, window: int, stream: int = 0):
+        """`snippet_windows` for queries that are term slots already (the arrays of `query_terms`, at most
+        SNIPPET_MAX_TERMS slots per query) and rows that are row positions: r_ptr [nq + 1] int32, rows int32."""
+        import torch
+
+        from .fusion import _on_stream
+        if not self.positions:
+            raise ValueError("snippet windows need an index built with positions=True")
+        nq = len(q_ptr) - 1
+        if nq > MAX_QUERIES or len(r_ptr) != nq + 1:
+            raise ValueError("snippet windows take at most 64 queries per call, with one r_ptr entry per query + 1")
+        q_ptr, r_ptr = np.ascontiguousarray(q_ptr, dtype=np.int32), np.ascontiguousarray(r_ptr, dtype=np.int32)
+        terms, rows = np.ascontiguousarray(terms, dtype=np.int32), np.ascontiguousarray(rows, dtype=np.int32)
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+        npairs = int(r_ptr[-1]) if nq else 0
+        with _on_stream(stream, self.device):
+            start = torch.empty(npairs, dtype=torch.int32, device=self.device)
+            last = torch.empty(npairs, dtype=torch.int32, device=self.device)
+            score = torch.empty(npairs, dtype=torch.float32, device=self.device)
+            covered = torch.empty(npairs, dtype=torch.int64, device=self.device)
+        if nq == 0:
+            return start, last, score, covered
+        rc = _native.load().crag_bm25_snippets_host(
+            self.d_post_ptr.data_ptr(), self.d_post_pos.data_ptr(), self.d_post_off.data_ptr(),
+            self.d_post_where.data_ptr(), self.n, self.n_terms, q_ptr.ctypes.data,
+            terms.ctypes.data if terms.size else None, weights.ctypes.data if weights.size else None, r_ptr.ctypes.data,
+            rows.ctypes.data if rows.size else None, nq, int(window), self._slot(stream),
+            start.data_ptr(), last.data_ptr(), score.data_ptr(), covered.data_ptr(), ctypes.c_void_p(stream))
+        _native.check(rc, "crag_bm25_snippets_host")
+        return start, last, score, covered
+
+
+def heaviest_slots(q_ptr, terms, weights, keep: int):
+    """The CSR of `query_terms` with every query cut to its `keep` heaviest slots -- equal weights by the lower term id --,
+    the kept slots back in ascending term-id order.  A batch within the limit comes back as it is."""
+    if np.all(np.diff(q_ptr) <= keep):
+        return q_ptr, terms, weights
+    out_ptr = np.zeros_like(q_ptr)
+    picks = []
+    for q in range(len(q_ptr) - 1):
+        a, b = int(q_ptr[q]), int(q_ptr[q + 1])
+        idx = np.arange(a, b)
+        if b - a > keep:
+            order = np.lexsort((terms[a:b], -weights[a:b].astype(np.float64)))[:keep]   # weight descending, then term id
+            idx = a + order[np.argsort(terms[a:b][order], kind="stable")]
+        picks.append(idx)
+        out_ptr[q + 1] = out_ptr[q] + idx.size
+    take = np.concatenate(picks)
+    return out_ptr, terms[take], weights[take]
 
 
 class _DecimalVocab:

@@ -69,6 +69,12 @@ class Settings:
     # DESIGN.md 4.7d): the word lane expands them over its vocabulary on the GPU, one stream synchronisation per query that
     # holds one.  Takes effect only together with bm25_query_syntax.  Off: `*` and `~` separate tokens as ever
     bm25_query_expand: bool = False
+    # query-aware snippets of /retrieve (env RETRIEVE_SNIPPET_BEST, RETRIEVE_SNIPPET_WINDOW_TOKENS): an
+    # evidence item's snippet is cut around the window of snippet_window_tokens tokens that holds the most of the query,
+    # found by the word lane on the GPU (it must be built with positions), instead of the first 800 characters.  Off:
+    # nothing is asked, nothing is launched and every response is what it was
+    snippet_best: bool = False
+    snippet_window_tokens: int = 120
     # /answer (PHASED_PLAN.md:318-326): "" = off, "native" = the in-process Qwen3Generator, http(s) = an OpenAI-compatible
     # chat-completions service
     llm_base_url: str = ""
@@ -123,7 +129,11 @@ class Settings:
 
     @classmethod
     def from_env(cls) -> "Settings":
-        return cls(**{f.name: _env(f.name, f.default) for f in fields(cls)})
+        return cls(**{f.name: _env(_ENV_NAMES.get(f.name, f.name), f.default) for f in fields(cls)})
+
+
+# knobs whose environment variable is not the field's own name
+_ENV_NAMES = {"snippet_best": "RETRIEVE_SNIPPET_BEST", "snippet_window_tokens": "RETRIEVE_SNIPPET_WINDOW_TOKENS"}
 
 
 settings = Settings.from_env()

@@ -293,6 +293,28 @@ struct Bm25GroupParams {
 };
 hipError_t launch_bm25_groups(const Bm25GroupParams &p, hipStream_t st);
 
+// ---- BM25 query-aware snippet windows (crag_bm25_snippet.hip) ----
+constexpr int BM25_SNIPPET_TERMS = 64;              // term slots per query: one per lane (CRAG_BM25_SNIPPET_MAX_TERMS)
+constexpr int BM25_SNIPPET_STAGE = 1024;            // positions of one pair the kernel keeps in LDS (bm25.SNIPPET_STAGE)
+
+struct Bm25SnippetParams {
+    const int64_t *post_ptr;     // [V + 1]
+    const int32_t *post_pos;     // [nnz] row positions, ascending inside a term
+    const int64_t *post_off;     // [nnz + 1] token positions of posting j: post_where[post_off[j] .. post_off[j + 1])
+    const uint16_t *post_where;  // token positions, ascending inside a posting
+    const int32_t *q_ptr;        // [nq + 1] slots of query q: [q_ptr[q], q_ptr[q + 1]), at most BM25_SNIPPET_TERMS
+    const int32_t *terms;        // term ids
+    const float *weights;
+    const int32_t *r_ptr;        // [nq + 1] pairs of query q: [r_ptr[q], r_ptr[q + 1])
+    const int32_t *rows;         // [npairs] row positions
+    int32_t *out_start;          // [npairs]
+    int32_t *out_last;
+    float *out_score;
+    uint64_t *out_covered;
+    int nq, npairs, window;
+};
+hipError_t launch_bm25_snippets(const Bm25SnippetParams &p, hipStream_t st);
+
 
 // ---- near-duplicate suppression of ranked lists (crag_dedupe.hip) ----
 struct DedupeParams {

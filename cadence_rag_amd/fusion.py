@@ -332,6 +332,14 @@ class HybridSearcher:
         self._fused_out: dict = {}  # per (stream, batch size, out_k): the fusion's outputs
         self._side: dict = {}       # per caller stream: (side stream, fork event, join event)
 
+    def snippet_windows(self, query_texts, fused_ids, window: int, stream: int = 0):
+        """Where the snippet of every fused row should begin: Bm25Index.snippet_windows of the native
+        BM25 lane for the batch -- fused_ids: per query the row ids to place (a row of `search`'s fused ids, read back and
+        cut at its count).  One upload and one launch on `stream`."""
+        if self.bm25_index is None:
+            raise ValueError("snippet windows need the native BM25 lane (bm25_index)")
+        return self.bm25_index.snippet_windows(query_texts, fused_ids, window, stream=stream)
+
     def _dedupe(self, fused, nq: int, ok: int, stream: int, dev) -> Dict[str, torch.Tensor]:
         """The fused lists deduped on `stream`: one kernel, then the scores and lane masks of the kept slots moved up
         (a scatter of the slot numbers to their new places, two gathers), padded like rrf_fuse's (NaN / 0)."""

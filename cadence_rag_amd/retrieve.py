@@ -20,6 +20,7 @@ import numpy as np
 
 from .config import settings
 from .dense_index import DenseIndex
+from .snippets import clip as _clip, cut_snippet   # (_clip: the head clip of retrieve.py:24-29)
 
 _log = logging.getLogger(__name__)
 
@@ -957,15 +958,6 @@ class RetrieveRequest:
             raise ValueError(f"facet_top must be in 1..{MAX_FACET_TOP} (got {self.facet_top})")
 
 
-def _clip(text: str, max_chars: int) -> str:
-    """retrieve.py:24-29."""
-    if max_chars <= 0:
-        return ""
-    if len(text) <= max_chars:
-        return text
-    return text[: max_chars - 1].rstrip() + "…"
-
-
 def _build_debug_lane(rows: Sequence[Dict[str, Any]], id_field: str) -> List[Dict[str, Any]]:
     """retrieve.py:32-41."""
     return [{id_field: row[id_field], "rank": rank, "score": row.get("score")}
@@ -993,6 +985,12 @@ class RetrieveBackend:
         """Near-duplicate suppression of one side's fused ids (best first): per id (slot of the kept id that suppresses
         it, their cosine) or (None, None).  A backend without vectors drops nothing."""
         return [(None, None)] * len(ids)
+
+    def snippet_windows(self, table_name, query, ids):
+        """Where the snippet of every listed row should begin (settings.snippet_best): per id the pair
+        (start, last) of token positions in the row's body column -- start < 0: no query word found -- or None when
+        this backend cannot place snippets on that table: every row then keeps the head clip."""
+        return None
 
     def facets(self, table_name, filters, call_ids, namespaces, top):
         """Facet counts of one table over the rows that pass the request's filters: {"rows": int, "facets": {namespace:
@@ -1140,6 +1138,21 @@ class GpuRetrieveBackend(RetrieveBackend):
     def facets(self, table_name, filters, call_ids, namespaces, top):
         return self.tables[table_name].facets([(filters, call_ids)], namespaces, top)[0]
 
+    def snippet_windows(self, table_name, query, ids):
+        """From the native word lane of the table when it was built with positions: one launch for all the rows
+        (Bm25Index.snippet_windows, crag_bm25_snippets_host).  None for a callable lane, a lane without positions or
+        rows the lane does not hold."""
+        lane, table = self._bm25[table_name], self.tables[table_name]
+        if lane is None or callable(lane) or not getattr(lane, "positions", False) or not ids or len(table) == 0:
+            return None
+        lane = self._bm25[table_name] = table.sync_bm25_lane(lane)
+        try:
+            start, last, _, _ = lane.snippet_windows([query], [list(ids)], int(settings.snippet_window_tokens))
+        except ValueError as exc:
+            _log.warning("snippet windows of %s: %s; the snippets are head clips", table_name, exc)
+            return None
+        return list(zip(start.tolist(), last.tolist()))
+
     def dedupe(self, table_name, ids, threshold):
         return self.tables[table_name].dedupe(ids, threshold)
 
@@ -1198,9 +1211,11 @@ class _Purse:
         return self.items <= 0 or self.chars <= 0
 
 
-def _pack(ranked, side: _Side, purse: _Purse, item_cap: Optional[int]) -> List[Dict[str, Any]]:
+def _pack(ranked, side: _Side, purse: _Purse, item_cap: Optional[int],
+          windows: Optional[Dict[Any, Tuple[int, int]]] = None) -> List[Dict[str, Any]]:
     """Ranked rows of one side -> evidence items, best first, until the purse or the side's caps run out.
-    A row over its call's quota is passed over without ending the walk."""
+    A row over its call's quota is passed over without ending the walk.  windows: row id -> (start, last), the token
+    window its snippet is cut around (settings.snippet_best); a row without one gets the head clip."""
     out: List[Dict[str, Any]] = []
     used_by_call: Dict[str, int] = {}
     for row, lanes, _ in ranked:
@@ -1211,7 +1226,11 @@ def _pack(ranked, side: _Side, purse: _Purse, item_cap: Optional[int]) -> List[D
             if used_by_call.get(call, 0) >= side.per_call:
                 continue
             used_by_call[call] = used_by_call.get(call, 0) + 1
-        snippet = _clip(row[side.body], min(DEFAULT_SNIPPET_CHARS, purse.chars))
+        at = windows.get(row[side.id_field]) if windows else None
+        if at is None:
+            snippet = _clip(row[side.body], min(DEFAULT_SNIPPET_CHARS, purse.chars))
+        else:
+            snippet = cut_snippet(row[side.body], at[0], at[1], min(DEFAULT_SNIPPET_CHARS, purse.chars))
         purse.chars -= len(snippet)
         purse.items -= 1
         item = {"evidence_id": f"{side.letter}-{row[side.id_field]}", "call_id": call}
@@ -1404,7 +1423,17 @@ def _retrieval_notes(tokens: List[str], dense: _DenseState, rerank: Optional[_Re
         notes["dense_per_call_cap"] = _dense_per_call_cap()
     if _dense_mmr() is not None:   # likewise
         notes["dense_mmr_lambda"] = _dense_mmr().lam
+    if settings.snippet_best:   # likewise
+        notes["snippet_mode"] = "best"
     return notes
+
+
+def _snippet_windows(be, query: str, side: _Side, ranked) -> Optional[Dict[Any, Tuple[int, int]]]:
+    """settings.snippet_best: one question to the backend per side, for the ranked rows `_pack` is about to walk."""
+    ids = [row[side.id_field] for row, _, _ in ranked]
+    ask = getattr(be, "snippet_windows", None)   # (a duck-typed backend may not have the method)
+    found = ask(side.table, query, ids) if ask is not None and ids else None
+    return None if found is None else dict(zip(ids, found))
 
 
 def retrieve_evidence(payload: RetrieveRequest, backend: Optional[RetrieveBackend] = None) -> Dict[str, Any]:
@@ -1454,7 +1483,10 @@ def retrieve_evidence(payload: RetrieveRequest, backend: Optional[RetrieveBacken
         packed = {}
         for s in _SIDES:  # artifacts are packed first and share the purse with the quotes
             cap = None if s.list_cap is None else min(s.list_cap, budget.max_evidence_items)
-            packed[s.out] = _pack(fused[s.table], s, purse, cap)
+            if settings.snippet_best:   # (off: no new call, the snippets are the head clips)
+                packed[s.out] = _pack(fused[s.table], s, purse, cap, _snippet_windows(be, query, s, fused[s.table]))
+            else:
+                packed[s.out] = _pack(fused[s.table], s, purse, cap)
         response = {**head, "intent": payload.intent, "budget": budget.model_dump(), **packed,
                     "notes": {"retrieval": _retrieval_notes(tokens, dense, rerank, dedupe, lanes)}}
     response.update(facets)

@@ -547,6 +547,41 @@ int crag_bm25_group_masks_host(const int64_t *d_post_ptr, const int32_t *d_post_
                                const int32_t *h_gt_terms, int nq, const uint8_t *d_in_mask, int64_t in_stride,
                                crag_upload_slot *slot, uint8_t *d_out_mask, int64_t mask_stride, void *stream);
 
+/* Query-aware snippet windows of the BM25 word lane: for every (query, row) pair of a batch, where in
+ * the row a window of `window` tokens holds the most of the query, read from the token positions the index keeps on the
+ * device (d_post_off / d_post_where, the arrays of the phrase clauses).  The reference has no code for this
+ * (APP_SPEC.md:269 asks for "snippets [that] are actually relevant (not just 'first N chars of the doc')"): the rule is
+ * this tree's own.
+ *
+ * The rule.  A query is its term slots j = 0 .. m - 1 (m <= CRAG_BM25_SNIPPET_MAX_TERMS), each a term id and an fp32
+ * weight, finite and >= 0.  For a pair (query, row r), a window width W and a start s:
+ *   covered(s) = the slots whose term has a token position of row r in [s, s + W),
+ *   score(s)   = the fp32 sum of the weights of covered(s), added one by one in ascending slot order onto +0.0f (no
+ *                FMA, no reassociation).
+ *   A start is a position of row r that holds the term of some slot (an occurrence).  Starts in between need no
+ *   trying: a window moved right to the first occurrence inside it still holds every occurrence it held, so its covered
+ *   set does not shrink, and -- the weights are >= 0 and a rounded addition is monotone -- its score does not fall.
+ *   The answer is the start with the largest score; among equal scores the lowest start.
+ * Only positions the index holds (< 65 535) exist for this rule.
+ *   Queries from the HOST in CSR form (what crag_bm25_lane_host takes): h_q_ptr [nq + 1] int32 (h_q_ptr[0] = 0), h_terms,
+ *               h_weights.  The rows of every query likewise: h_r_ptr [nq + 1] int32 (h_r_ptr[0] = 0), h_rows [npairs]
+ *               row POSITIONS in [0, n_rows), in any order, repeats allowed.  1 <= window <= 65535.
+ *   Outputs [npairs], laid out along h_r_ptr: d_start int32 (-1 when no slot's term occurs in the row; the other three are
+ *               then 0), d_last int32 (the largest occurrence inside the chosen window), d_score fp32, d_covered uint64
+ *               (bit j for slot j).
+ * One upload through `slot` and one launch on `stream`, asynchronous; integer work and the fixed-order sum: the outputs
+ * are a function of the inputs alone.
+ * CRAG_EINVAL with a message that contains "bm25_snippets_host", checked before any HIP call, nothing enqueued: a NULL
+ * required pointer (the position arrays included), nq outside 1..64, n_rows or n_terms outside [0, 2^31), h_q_ptr or
+ * h_r_ptr not ascending from 0, a query of more than 64 slots, a term id outside [0, n_terms), a weight that is negative or
+ * not finite, a row outside [0, n_rows), window outside 1..65535.  npairs == 0 is CRAG_OK and enqueues nothing. */
+#define CRAG_BM25_SNIPPET_MAX_TERMS 64
+int crag_bm25_snippets_host(const int64_t *d_post_ptr, const int32_t *d_post_pos, const int64_t *d_post_off,
+                            const uint16_t *d_post_where, int64_t n_rows, int64_t n_terms, const int32_t *h_q_ptr,
+                            const int32_t *h_terms, const float *h_weights, const int32_t *h_r_ptr, const int32_t *h_rows,
+                            int nq, int window, crag_upload_slot *slot, int32_t *d_start, int32_t *d_last, float *d_score,
+                            uint64_t *d_covered, void *stream);
+
 /* Character-trigram field of the BM25 lane: the inverted CSR crag_bm25_lane_host scores, built on the device from the
  * rows' bytes (cadence_rag_amd.ngram.NgramIndex drives it).  Stands in for the reference's second index over every
  * lexical column, the `pdb.ngram(3,3)` aliases of alembic/versions/0005_add_bm25_ngram.py and 0006_add_artifact_chunks.py
