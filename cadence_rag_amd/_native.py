@@ -223,3 +223,45 @@ def last_error() -> str:
 def check(rc: int, what: str) -> None:
     if rc != 0:
         raise NativeLibraryError(f"{what} failed (code {rc}): {last_error()}")
+
+
+class UploadRing:
+    """Per stream a ring of four upload slots, for the lanes that take host query data (the *_host entry points): a
+    crag_upload_slot of the library is a pinned host buffer, its device twin and the event of its last upload, so a
+    call may fill a slot while the three calls before it on the stream are still in flight.  Slots are created on
+    first use and freed by `close` (also when the ring is collected)."""
+    SIZE = 4
+
+    def __init__(self, device) -> None:
+        self.device = device
+        self._rings: dict = {}      # stream -> [calls so far, handles]
+
+    def take(self, stream: int):
+        """The stream's next slot: (its place in the ring, its handle) -- the place for owners that keep something of
+        their own per slot."""
+        ring = self._rings.setdefault(stream, [0, []])
+        if len(ring[1]) < self.SIZE:
+            import torch
+            with torch.cuda.device(self.device):
+                handle = load().crag_upload_slot_create()
+            if not handle:
+                raise NativeLibraryError(f"crag_upload_slot_create failed: {last_error()}")
+            ring[1].append(handle)
+        at = ring[0] % len(ring[1])
+        ring[0] += 1
+        return at, ring[1][at]
+
+    def slot(self, stream: int):
+        return self.take(stream)[1]
+
+    def close(self) -> None:
+        rings, self._rings = getattr(self, "_rings", {}), {}
+        for _, handles in rings.values():
+            for handle in handles:
+                load().crag_upload_slot_destroy(handle)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown: the library may be gone already
+            pass

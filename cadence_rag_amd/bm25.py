@@ -164,15 +164,14 @@ class Bm25Index:
         self.positions = bool(positions)
         self.pair_off = np.zeros(1, dtype=np.int64)
         self.pair_where = np.empty(0, dtype=np.uint16)
-        self._clause_masks: dict = {}   # per stream: the clause masks of a full batch
         self.vocab: Dict[str, int] = {}
         self.row_ptr = np.zeros(1, dtype=np.int64)
         self.row_terms = np.empty(0, dtype=np.int32)
         self.row_tf = np.empty(0, dtype=np.int64)
         self.doc_len = np.empty(0, dtype=np.int32)
         self.ids = np.empty(0, dtype=np.int64)
-        self._slots: dict = {}     # per stream: ring of upload slots
-        self._scratch: dict = {}   # per stream: the partial top-k lists
+        self._ring = _native.UploadRing(self.device)
+        self._buffers: dict = {}   # per (stream, name): grow-only device buffers (`_stream_buffer`)
         self._append(texts, ids)
         self._upload()
 
@@ -298,10 +297,8 @@ class Bm25Index:
         if self.positions:
             post_off, post_where = self.host_positions()
             self.d_post_off, self.d_post_where = dev(post_off), dev(post_where, np.int16)   # (bits of the uint16 values)
-        self._scratch = {}
-        self._clause_masks = {}
+        self._buffers = {}
         self._dictionary = None      # (d_term_ptr, d_term_bytes): uploaded by the first `expand`, dropped here
-        self._expand_scratch = {}
 
     def extend(self, texts: Sequence[str], ids: Sequence[int]) -> None:
         """Rows appended at the end (what the backfill does): only the new rows are tokenised; the device CSR is rebuilt
@@ -341,35 +338,30 @@ class Bm25Index:
             q_ptr[q + 1] = len(terms)
         term_ids = np.asarray(terms, dtype=np.int32)
         df = self.df[term_ids].astype(np.float64)
-        weights = np.asarray(qtfs, dtype=np.float64) * np.log(1.0 + (float(self.n) - df + 0.5) / (df + 0.5)) * (K1 + 1.0)
+        weights = _idf_weight(float(self.n), df, np.asarray(qtfs, dtype=np.float64))
         return q_ptr, term_ids, weights.astype(np.float32)   # fp64 up to here, rounded once
 
     # ---- device side -------------------------------------------------------------------------------------------
     def _slot(self, stream: int):
-        """Next upload slot of the stream's ring of four (the idiom of TechTokenIndex._slot)."""
-        import torch
-        ring = self._slots.setdefault(stream, {"next": 0, "slots": []})
-        if len(ring["slots"]) < 4:
-            with torch.cuda.device(self.device):
-                handle = _native.load().crag_upload_slot_create()
-            if not handle:
-                raise _native.NativeLibraryError(f"crag_upload_slot_create failed: {_native.last_error()}")
-            ring["slots"].append(handle)
-        slot = ring["slots"][ring["next"] % len(ring["slots"])]
-        ring["next"] += 1
-        return slot
+        """Next upload slot of the stream's ring of four."""
+        return self._ring.slot(stream)
 
     def close(self) -> None:
-        rings, self._slots = getattr(self, "_slots", {}), {}
-        for ring in rings.values():
-            for handle in ring["slots"]:
-                _native.load().crag_upload_slot_destroy(handle)
+        self._ring.close()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # interpreter shutdown: the library may be gone already
-            pass
+    def _stream_buffer(self, stream: int, name: str, min_bytes: int, dtype, alloc_bytes=None):
+        """The stream's grow-only device buffer `name`, at least min_bytes large (`_upload` drops them all).  A buffer
+        that has to be allocated takes max(min_bytes, alloc_bytes()) bytes, on `stream`."""
+        buf = self._buffers.get((stream, name))
+        if buf is None or buf.numel() * buf.element_size() < min_bytes:
+            import torch
+
+            from .fusion import _on_stream
+            size = max(int(min_bytes), int(alloc_bytes()) if alloc_bytes else 0)
+            with _on_stream(stream, self.device):
+                buf = self._buffers[(stream, name)] = torch.empty(max(-(-size // dtype.itemsize), 1), dtype=dtype,
+                                                                  device=self.device)
+        return buf
 
     def search(self, query_texts: Sequence[str], k: int, row_mask=None, mask_stride: int = 0, stream: int = 0):
         """Top-k rows of every query by BM25 score (descending, equal scores by ascending id) among the rows that hold
@@ -385,12 +377,10 @@ class Bm25Index:
         """The batch's constraint clauses as the host arrays of crag_bm25_clause_masks_host: c_ptr [nq + 1], c_kind,
         ct_ptr [n_clauses + 1], ct_terms (all int32).  An unknown token turns a required clause into kind 4 ("matches
         nothing") and drops an excluded one.  A phrase clause on an index without positions raises ValueError."""
-        c_ptr = np.zeros(len(parsed_list) + 1, dtype=np.int32)
-        kinds: List[int] = []
-        ct_ptr: List[int] = [0]
-        ct_terms: List[int] = []
         get = self.vocab.get
-        for q, parsed in enumerate(parsed_list):
+        per_query = []
+        for parsed in parsed_list:
+            items = []
             for kind, toks in parsed.clauses:
                 if kind in (REQ_PHRASE, EXC_PHRASE) and not self.positions:
                     raise ValueError("a phrase clause needs an index built with positions=True")
@@ -399,12 +389,9 @@ class Bm25Index:
                     if kind in (EXC_TERM, EXC_PHRASE):
                         continue
                     kind, ids = MATCH_NOTHING, []
-                kinds.append(kind)
-                ct_terms.extend(ids)
-                ct_ptr.append(len(ct_terms))
-            c_ptr[q + 1] = len(kinds)
-        return (c_ptr, np.asarray(kinds, dtype=np.int32), np.asarray(ct_ptr, dtype=np.int32),
-                np.asarray(ct_terms, dtype=np.int32))
+                items.append((kind, ids))
+            per_query.append(items)
+        return _nested_csr(per_query)
 
     # ---- prefix and fuzzy items ----------------------------------------------------------------------
     def term_strings(self) -> List[str]:
@@ -452,11 +439,8 @@ class Bm25Index:
         pat_kind = np.asarray([kind for kind, _ in patterns], dtype=np.int32)
         d_term_ptr, d_term_bytes = self._device_dictionary()
         need = int(lib.crag_bm25_expand_scratch_bytes(self.n_terms, npat))
+        scratch = self._stream_buffer(stream, "expand", need, torch.int64)
         with _on_stream(stream, self.device):
-            scratch = self._expand_scratch.get(stream)
-            if scratch is None or scratch.numel() * 8 < need:
-                scratch = self._expand_scratch[stream] = torch.empty(max(need // 8, 1), dtype=torch.int64,
-                                                                     device=self.device)
             # one buffer, one copy back: terms [np, 64] | dist [np, 64] | kept [np] | pad | total [np] int64
             words = 2 * npat * MAX_EXPANSIONS + (npat + 1) // 2 * 2
             out = torch.empty(words * 4 + npat * 8, dtype=torch.uint8, device=self.device)
@@ -495,15 +479,13 @@ class Bm25Index:
                     qtf[t] = qtf.get(t, 0) + 1
             w: Dict[int, float] = {}
             for t, c in qtf.items():
-                df = float(self.df[t])
-                w[t] = float(c) * float(np.log(1.0 + (n - df + 0.5) / (df + 0.5))) * (K1 + 1.0)
+                w[t] = float(_idf_weight(n, float(self.df[t]), float(c)))
             for role, _, _ in parsed.expansions:
                 ids, dist, _ = expansions[at]
                 at += 1
                 if role == EXCLUDED or len(ids) == 0:
                     continue
-                df = float(self.df[ids].max())
-                base = float(np.log(1.0 + (n - df + 0.5) / (df + 0.5))) * (K1 + 1.0)
+                base = float(_idf_weight(n, float(self.df[ids].max())))
                 for t, d in zip(ids.tolist(), dist.tolist()):
                     w[t] = w.get(t, 0.0) + base * 2.0 ** (-d)
             ordered = sorted(w)
@@ -517,34 +499,18 @@ class Bm25Index:
         """The required and excluded expanding items of a batch as the host arrays of crag_bm25_group_masks_host: g_ptr
         [nq + 1], g_kind, gt_ptr [n_groups + 1], gt_terms (all int32).  A required item without a match stays as an empty
         group (it matches nothing); an excluded one without a match is dropped."""
-        g_ptr = np.zeros(len(parsed_list) + 1, dtype=np.int32)
-        kinds: List[int] = []
-        gt_ptr: List[int] = [0]
-        gt_terms: List[int] = []
+        per_query = []
         at = 0
-        for q, parsed in enumerate(parsed_list):
+        for parsed in parsed_list:
+            items = []
             for role, _, _ in parsed.expansions:
                 ids = expansions[at][0]
                 at += 1
                 if role == OPTIONAL or (role == EXCLUDED and len(ids) == 0):
                     continue
-                kinds.append(REQ_ANY if role == REQUIRED else EXC_ANY)
-                gt_terms.extend(ids.tolist())
-                gt_ptr.append(len(gt_terms))
-            g_ptr[q + 1] = len(kinds)
-        return (g_ptr, np.asarray(kinds, dtype=np.int32), np.asarray(gt_ptr, dtype=np.int32),
-                np.asarray(gt_terms, dtype=np.int32))
-
-    def _mask_buffer(self, stream: int, which: int, stride: int):
-        import torch
-
-        from .fusion import _on_stream
-        with _on_stream(stream, self.device):
-            buf = self._clause_masks.get((stream, which) if which else stream)
-            if buf is None:
-                buf = self._clause_masks[(stream, which) if which else stream] = torch.empty(
-                    MAX_QUERIES * stride, dtype=torch.uint8, device=self.device)
-        return buf
+                items.append((REQ_ANY if role == REQUIRED else EXC_ANY, ids.tolist()))
+            per_query.append(items)
+        return _nested_csr(per_query)
 
     def search_query(self, query_texts: Sequence[str], k: int, row_mask=None, mask_stride: int = 0, stream: int = 0,
                      expand: bool = False):
@@ -564,25 +530,37 @@ class Bm25Index:
             return self._search_expanded(parsed, k, row_mask, mask_stride, stream)
         if not any(p.has_constraints for p in parsed):
             return self.search(query_texts, k, row_mask=row_mask, mask_stride=mask_stride, stream=stream)
-        c_ptr, c_kind, ct_ptr, ct_terms = self.clause_arrays(parsed)
+        clauses = self.clause_arrays(parsed)
         bags = self.query_terms([" ".join(p.bag) for p in parsed])   # (tokens are alphanumeric runs: they re-tokenise as
         if self.n == 0:                                              #  themselves)
             return self.search_terms(*bags, k, stream=stream)
         stride = (self.n + 31) // 32 * 4
-        buf = self._mask_buffer(stream, 0, stride)
-        self._clause_launch(c_ptr, c_kind, ct_ptr, ct_terms, len(parsed), row_mask, mask_stride, buf, stride, stream)
+        buf = self._clause_masks(clauses, len(parsed), row_mask, mask_stride, stride, stream)
         return self.search_terms(*bags, k, row_mask=buf, mask_stride=stride, stream=stream)
 
+    def _mask_launch(self, entry_name, extra_pointers, ptr, kind, t_ptr, terms, nq, in_mask, in_stride, buf, stride,
+                     stream) -> None:
+        """One launch of a mask entry (crag_bm25_clause_masks_host, crag_bm25_group_masks_host): the arrays of
+        `clause_arrays` / `group_arrays` under `in_mask` into `buf`.  extra_pointers: what the entry takes between the
+        postings and n_rows."""
+        rc = getattr(_native.load(), entry_name)(
+            self.d_post_ptr.data_ptr(), self.d_post_pos.data_ptr(), *extra_pointers, self.n, self.n_terms,
+            ptr.ctypes.data, kind.ctypes.data if kind.size else None, t_ptr.ctypes.data,
+            terms.ctypes.data if terms.size else None, nq, None if in_mask is None else in_mask.data_ptr(),
+            int(in_stride), self._slot(stream), buf.data_ptr(), stride, ctypes.c_void_p(stream))
+        _native.check(rc, entry_name)
+
     def _clause_launch(self, c_ptr, c_kind, ct_ptr, ct_terms, nq, in_mask, in_stride, buf, stride, stream) -> None:
-        rc = _native.load().crag_bm25_clause_masks_host(
-            self.d_post_ptr.data_ptr(), self.d_post_pos.data_ptr(),
-            None if self.d_post_off is None else self.d_post_off.data_ptr(),
-            None if self.d_post_where is None else self.d_post_where.data_ptr(), self.n, self.n_terms,
-            c_ptr.ctypes.data, c_kind.ctypes.data if c_kind.size else None, ct_ptr.ctypes.data,
-            ct_terms.ctypes.data if ct_terms.size else None, nq,
-            None if in_mask is None else in_mask.data_ptr(), int(in_stride), self._slot(stream), buf.data_ptr(), stride,
-            ctypes.c_void_p(stream))
-        _native.check(rc, "crag_bm25_clause_masks_host")
+        where = tuple(None if t is None else t.data_ptr() for t in (self.d_post_off, self.d_post_where))
+        self._mask_launch("crag_bm25_clause_masks_host", where, c_ptr, c_kind, ct_ptr, ct_terms, nq, in_mask, in_stride,
+                          buf, stride, stream)
+
+    def _clause_masks(self, clauses, nq, in_mask, in_stride, stride, stream):
+        """The clause masks of a batch under `in_mask`, in the buffer this stream keeps for a full batch of them."""
+        import torch
+        buf = self._stream_buffer(stream, "clause_masks", MAX_QUERIES * stride, torch.uint8)
+        self._clause_launch(*clauses, nq, in_mask, in_stride, buf, stride, stream)
+        return buf
 
     def _search_expanded(self, parsed, k, row_mask, mask_stride, stream):
         """`search_query` for a batch with expanding items: expand -> group masks -> clause masks -> search_terms."""
@@ -591,22 +569,16 @@ class Bm25Index:
         clauses = self.clause_arrays(parsed) if any(p.has_constraints for p in parsed) else None
         if self.n == 0:
             return self.search_terms(*bags, k, stream=stream)
-        g_ptr, g_kind, gt_ptr, gt_terms = self.group_arrays(parsed, expansions)
+        groups = self.group_arrays(parsed, expansions)
         stride = (self.n + 31) // 32 * 4
         mask, in_stride = row_mask, int(mask_stride)
-        if g_kind.size:
-            buf = self._mask_buffer(stream, 1, stride)
-            rc = _native.load().crag_bm25_group_masks_host(
-                self.d_post_ptr.data_ptr(), self.d_post_pos.data_ptr(), self.n, self.n_terms, g_ptr.ctypes.data,
-                g_kind.ctypes.data, gt_ptr.ctypes.data, gt_terms.ctypes.data if gt_terms.size else None, len(parsed),
-                None if mask is None else mask.data_ptr(), in_stride, self._slot(stream), buf.data_ptr(), stride,
-                ctypes.c_void_p(stream))
-            _native.check(rc, "crag_bm25_group_masks_host")
+        if groups[1].size:
+            import torch
+            buf = self._stream_buffer(stream, "group_masks", MAX_QUERIES * stride, torch.uint8)
+            self._mask_launch("crag_bm25_group_masks_host", (), *groups, len(parsed), mask, in_stride, buf, stride, stream)
             mask, in_stride = buf, stride
         if clauses is not None:     # (the group mask is the clause launch's input: in and out must not overlap)
-            buf = self._mask_buffer(stream, 0, stride)
-            self._clause_launch(*clauses, len(parsed), mask, in_stride, buf, stride, stream)
-            mask, in_stride = buf, stride
+            mask, in_stride = self._clause_masks(clauses, len(parsed), mask, in_stride, stride, stream), stride
         return self.search_terms(*bags, k, row_mask=mask, mask_stride=in_stride, stream=stream)
 
     def search_terms(self, q_ptr, terms, weights, k: int, row_mask=None, mask_stride: int = 0, stream: int = 0):
@@ -620,13 +592,10 @@ class Bm25Index:
             raise ValueError(f"the BM25 lane takes at most 64 queries per call and k in [1, {_native.CRAG_MAX_K}]")
         k = int(k)
         need = int(lib.crag_bm25_scratch_bytes(self.n, max(nq, 1), k))
+        # the partial top-k lists: sized for a full batch at this k, so that a stream allocates once
+        scratch = self._stream_buffer(stream, "topk", need, torch.int64,
+                                      lambda: lib.crag_bm25_scratch_bytes(self.n, MAX_QUERIES, k))
         with _on_stream(stream, self.device):
-            scratch = self._scratch.get(stream)
-            if scratch is None or scratch.numel() * 8 < need:
-                # sized for a full batch at this k, so that a stream allocates once
-                full = int(lib.crag_bm25_scratch_bytes(self.n, MAX_QUERIES, k))
-                scratch = self._scratch[stream] = torch.empty((max(need, full) + 7) // 8, dtype=torch.int64,
-                                                              device=self.device)
             out_ids = torch.empty(nq, k, dtype=torch.int64, device=self.device)
             out_scores = torch.empty(nq, k, dtype=torch.float32, device=self.device)
             out_counts = torch.empty(nq, dtype=torch.int32, device=self.device)
@@ -706,6 +675,28 @@ class Bm25Index:
             start.data_ptr(), last.data_ptr(), score.data_ptr(), covered.data_ptr(), ctypes.c_void_p(stream))
         _native.check(rc, "crag_bm25_snippets_host")
         return start, last, score, covered
+
+
+def _idf_weight(n, df, qtf=1.0):
+    """qtf * idf(df) * (k1 + 1) in fp64, in this order of operations: numpy arrays or Python floats (numpy's vector
+    and scalar log are not promised to agree in the last bit, so a caller stays with the kind it always used)."""
+    return qtf * np.log(1.0 + (n - df + 0.5) / (df + 0.5)) * (K1 + 1.0)
+
+
+def _nested_csr(per_query):
+    """Per query a list of (kind, term ids) -> the host arrays of a mask entry: ptr [nq + 1], kind [n], inner ptr
+    [n + 1], the term ids flat (all int32)."""
+    ptr = np.zeros(len(per_query) + 1, dtype=np.int32)
+    kinds: List[int] = []
+    inner: List[int] = [0]
+    flat: List[int] = []
+    for q, items in enumerate(per_query):
+        for kind, ids in items:
+            kinds.append(kind)
+            flat.extend(ids)
+            inner.append(len(flat))
+        ptr[q + 1] = len(kinds)
+    return (ptr, np.asarray(kinds, dtype=np.int32), np.asarray(inner, dtype=np.int32), np.asarray(flat, dtype=np.int32))
 
 
 def heaviest_slots(q_ptr, terms, weights, keep: int):

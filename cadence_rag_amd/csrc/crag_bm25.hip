@@ -20,6 +20,7 @@
 
 #include "../../include/crag_dense.h"
 #include "crag_kernels.h"
+#include "crag_postings.h"
 #include "crag_host.h"
 
 namespace crag {
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(BM25_THREADS) void bm25_score_kernel(Bm25Params p) 
     __shared__ int s_n;
     const int rg = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
     const int64_t base = (int64_t)rg * BM25_RANGE;
-    const int64_t end = base + BM25_RANGE < p.n ? base + BM25_RANGE : p.n;
+    const int64_t end = base + BM25_RANGE < p.n ? base + BM25_RANGE : p.n;   // (n_ranges comes from n: no empty range)
     const int t0 = p.q_ptr[q], t1 = p.q_ptr[q + 1];
     int32_t *cnt_out = p.part_cnt + ((size_t)q * p.n_ranges + rg);
     bool zeroed = false;
@@ -87,12 +88,8 @@ __global__ __launch_bounds__(BM25_THREADS) void bm25_score_kernel(Bm25Params p) 
     for (int c0 = t0; c0 < t1; c0 += BM25_TCHUNK) {
         const int nt = t1 - c0 < BM25_TCHUNK ? t1 - c0 : BM25_TCHUNK;
         int64_t lo = 0, hi = 0;
-        if (tid < nt) {   // lanes search different terms: the workgroup pays one latency chain per round
-            const int term = p.q_term[c0 + tid];
-            const int64_t a = p.post_ptr[term], b = p.post_ptr[term + 1];
-            lo = lower_bound_asc(p.post_pos, a, b, base);
-            hi = lower_bound_asc(p.post_pos, lo, b, end);
-        }
+        if (tid < nt)   // lanes search different terms: the workgroup pays one latency chain per round
+            posting_slice(p.post_ptr, p.post_pos, p.q_term[c0 + tid], base, end, lo, hi);
         // (the barrier of this vote also keeps the previous round's readers of s_lo / s_len ahead of the writes below)
         if (!__syncthreads_or(hi > lo)) continue;   // no term of this round has a posting in the range
         if (tid < nt) {
@@ -170,9 +167,7 @@ __global__ __launch_bounds__(BM25_THREADS) void bm25_score_kernel(Bm25Params p) 
     __syncthreads();
     if (tid < kk) {
         const uint64_t mine = s_sel[tid];
-        int r = 0;
-        for (int i = 0; i < kk; ++i) r += s_sel[i] > mine;
-        p.part_keys[((size_t)q * p.n_ranges + rg) * p.k + r] = mine;
+        p.part_keys[((size_t)q * p.n_ranges + rg) * p.k + rank_desc(s_sel, kk, mine)] = mine;
     }
     if (tid == 0) *cnt_out = kk;
 }
@@ -225,8 +220,7 @@ __global__ __launch_bounds__(BM25_THREADS) void bm25_merge_kernel(Bm25Params p) 
         float sc = __uint_as_float(0x7fc00000u);
         if (tid < nb) {
             const uint64_t mine = s_best[tid];
-            int r = 0;
-            for (int i = 0; i < nb; ++i) r += s_best[i] > mine;
+            const int r = rank_desc(s_best, nb, mine);
             const int64_t pos = (int64_t)(0xffffffffu - (uint32_t)mine);
             p.out_ids[(size_t)q * k + r] = p.ids ? p.ids[pos] : pos;
             p.out_scores[(size_t)q * k + r] = __uint_as_float((uint32_t)(mine >> 32));
@@ -275,10 +269,9 @@ int crag_bm25_lane_host(const int64_t *d_post_ptr, const int32_t *d_post_pos, co
         !d_out_scores || !d_out_counts)
         return fail(CRAG_EINVAL, "bm25_lane_host: NULL pointer argument");
     if (((uintptr_t)d_scratch & 7) != 0) return fail(CRAG_EINVAL, "bm25_lane_host: scratch must be 8-byte aligned");
-    if (nq < 0 || nq > crag::BM25_MAX_Q || k <= 0 || k > CRAG_MAX_K)
-        return fail(CRAG_EINVAL, "bm25_lane_host: need 0 <= nq <= 64 and 1 <= k <= %d (nq=%d k=%d)", CRAG_MAX_K, nq, k);
-    if (n_rows < 0 || n_rows > INT32_MAX || n_terms < 0 || n_terms > INT32_MAX)
-        return fail(CRAG_EINVAL, "bm25_lane_host: n_rows / n_terms out of range");
+    int rc = check_bm25_counts("bm25_lane_host", nq, 0, n_rows, n_terms);
+    if (rc != CRAG_OK) return rc;
+    if (k <= 0 || k > CRAG_MAX_K) return fail(CRAG_EINVAL, "bm25_lane_host: need 1 <= k <= %d (k=%d)", CRAG_MAX_K, k);
     if (n_rows > 0 && !(avgdl > 0.0f && avgdl < 3.0e38f)) return fail(CRAG_EINVAL, "bm25_lane_host: avgdl must be positive and finite");
     if (d_row_mask) {
         if (((uintptr_t)d_row_mask & 3) != 0) return fail(CRAG_EINVAL, "bm25_lane_host: row_mask must be 4-byte aligned");
@@ -288,41 +281,32 @@ int crag_bm25_lane_host(const int64_t *d_post_ptr, const int32_t *d_post_pos, co
     if (scratch_bytes < crag::bm25_scratch_bytes(n_rows, nq, k))
         return fail(CRAG_EINVAL, "bm25_lane_host: scratch too small (crag_bm25_scratch_bytes)");
     if (nq == 0) return CRAG_OK;
-    if (h_q_ptr[0] != 0) return fail(CRAG_EINVAL, "bm25_lane_host: q_ptr[0] must be 0");
-    for (int q = 0; q < nq; ++q) {
-        const int a = h_q_ptr[q], b = h_q_ptr[q + 1];
-        if (b < a) return fail(CRAG_EINVAL, "bm25_lane_host: q_ptr must not descend");
-        if (b > a && (!h_term_ids || !h_weights)) return fail(CRAG_EINVAL, "bm25_lane_host: NULL term arrays");
-        for (int i = a; i < b; ++i) {
-            if (h_term_ids[i] < 0 || h_term_ids[i] >= n_terms || (i > a && h_term_ids[i] <= h_term_ids[i - 1]))
-                return fail(CRAG_EINVAL, "bm25_lane_host: term ids of a query must ascend strictly inside [0, n_terms)");
+    if ((rc = check_csr("bm25_lane_host", "q_ptr", "query", h_q_ptr, nq, -1)) != CRAG_OK) return rc;
+    const int nt = h_q_ptr[nq];
+    if (nt > 0 && (!h_term_ids || !h_weights)) return fail(CRAG_EINVAL, "bm25_lane_host: NULL term arrays");
+    if ((rc = check_terms("bm25_lane_host", h_term_ids, 0, nt, n_terms)) != CRAG_OK) return rc;
+    for (int q = 0; q < nq; ++q)
+        for (int i = h_q_ptr[q]; i < h_q_ptr[q + 1]; ++i) {
+            if (i > h_q_ptr[q] && h_term_ids[i] <= h_term_ids[i - 1])
+                return fail(CRAG_EINVAL, "bm25_lane_host: the term ids of query %d must ascend strictly", q);
             if (!(h_weights[i] > 0.0f && h_weights[i] < 3.0e38f))
                 return fail(CRAG_EINVAL, "bm25_lane_host: weights must be positive and finite");
         }
-    }
-    const int nt = h_q_ptr[nq];
     // slot layout: q_ptr [BM25_MAX_Q + 4] int32 | term ids [nt] int32 | weights [nt] fp32
-    const size_t head = (size_t)(crag::BM25_MAX_Q + 4) * 4;
-    const size_t bytes = head + (size_t)nt * 8;
-    void *h = nullptr, *d = nullptr;
-    int rc = crag_upload_slot_begin_(slot, bytes, &h, &d);
-    if (rc != CRAG_OK) return rc;
-    memcpy(h, h_q_ptr, (size_t)(nq + 1) * 4);
-    if (nt > 0) {
-        memcpy((char *)h + head, h_term_ids, (size_t)nt * 4);
-        memcpy((char *)h + head + (size_t)nt * 4, h_weights, (size_t)nt * 4);
-    }
-    rc = crag_upload_slot_commit_(slot, bytes, stream);
-    if (rc != CRAG_OK) return rc;
+    UploadPack up;
+    const int i_ptr = up.add(h_q_ptr, (size_t)nq + 1, (size_t)(crag::BM25_MAX_Q + 4) * 4);
+    const int i_terms = up.add(h_term_ids, (size_t)nt);
+    const int i_w = up.add(h_weights, (size_t)nt);
+    if ((rc = up.begin(slot)) != CRAG_OK || (rc = up.commit(slot, stream)) != CRAG_OK) return rc;
     crag::Bm25Params p;
     p.post_ptr = d_post_ptr;
     p.post_pos = d_post_pos;
     p.post_tf = d_post_tf;
     p.doc_len = d_doc_len;
     p.ids = d_ids;
-    p.q_ptr = (const int32_t *)d;
-    p.q_term = (const int32_t *)((const char *)d + head);
-    p.q_w = (const float *)((const char *)d + head + (size_t)nt * 4);
+    p.q_ptr = up.dev<int32_t>(i_ptr);
+    p.q_term = up.dev<int32_t>(i_terms);
+    p.q_w = up.dev<float>(i_w);
     p.mask = (const uint32_t *)d_row_mask;
     p.mask_stride_w = mask_stride / 4;
     p.n = n_rows;

@@ -1,5 +1,5 @@
 // crag_bm25_expand.hip -- prefix and fuzzy query terms of the BM25 lane expanded over the vocabulary on the GPU (gfx950),
-// and the any-of clauses they become, DESIGN.md 4.7d.  `deploy*` stands for every vocabulary term that begins with
+// DESIGN.md 4.7d (the any-of row masks they become are made in crag_bm25_clause.hip).  `deploy*` stands for every vocabulary term that begins with
 // "deploy", `kubernets~` for every term within Levenshtein distance 1 of it; the rule (include/crag_dense.h states it) is
 // this tree's own.  The vocabulary lives on the device as a CSR of UTF-8 bytes in term-id order, df is a difference of
 // post_ptr, and the two kernels of crag_bm25.hip score the kept terms with the bits they always had.
@@ -19,16 +19,13 @@
 // Both selections are one routine: the keys are distinct (the term id is in them), so the 64th largest is found bit by bit
 // from the top with one block-wide count per bit (the idea of crag_bm25.hip), and the at most 64 keys at or above it are
 // ranked by counting.  LDS atomics only hand out list slots; what is kept and its order are functions of the key set.
-//
-// bm25_group_mask_kernel, grid (ranges of BM25_RANGE row positions, queries): the frame of bm25_clause_mask_kernel.  A
-// group's terms are streamed into one bitmap, one term per wave at a time (integer LDS atomicOr: it commutes), and the
-// bitmap ANDs into `keep` (required-any) or its complement does (excluded-any).  Integer work only, no floating point.
 #include "crag_arch.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/crag_dense.h"
 #include "crag_kernels.h"
+#include "crag_postings.h"
 #include "crag_host.h"
 
 namespace crag {
@@ -39,15 +36,10 @@ constexpr int EX_WAVES = EX_THREADS / 64;
 constexpr int EX_INF = 1 << 20;
 constexpr int EX_MERGE_LDS = 4096;                               // keys the merge kernel holds in LDS
 constexpr int EX_TARGET_GROUPS = 1024;                           // workgroups wanted of the match launch (256 CUs x 4)
-constexpr int GR_THREADS = BM25_RANGE_WORDS;                     // one thread per mask word of the range
-constexpr int GR_WAVES = GR_THREADS / 64;
-constexpr int GR_TERMS = BM25_GROUP_MAX * BM25_EXPAND_KEEP;      // group terms of one query, at most
 
 static_assert(BM25_EXPAND_KEEP == CRAG_BM25_MAX_EXPANSIONS && BM25_EXPAND_KEEP == 64, "one lane per kept key");
-static_assert(BM25_GROUP_MAX == CRAG_BM25_MAX_CLAUSES, "groups count as constraint clauses");
 static_assert(BM25_EXPAND_MAX_PATTERNS == CRAG_BM25_MAX_PATTERNS &&
               BM25_EXPAND_MAX_PATTERNS == BM25_MAX_Q * CRAG_BM25_MAX_EXPAND_ITEMS, "64 queries of 8 expanding items");
-static_assert(GR_THREADS == 512, "one mask word per thread");
 
 // next code point of b[0 .. len) at pos (pos < len); never reads at or beyond len, whatever the bytes
 __device__ __forceinline__ uint32_t ex_decode(const uint8_t *b, int len, int &pos) {
@@ -152,9 +144,7 @@ __device__ void ex_select_top(const uint64_t *keys, int64_t n, uint64_t *out, ui
     if (tid < BM25_EXPAND_KEEP) {
         if (tid < kept) {   // the ranks of distinct keys are a permutation of 0 .. kept - 1
             const uint64_t mine = s_top[tid];
-            int rank = 0;
-            for (int j = 0; j < kept; ++j) rank += s_top[j] > mine;
-            out[rank] = mine;
+            out[rank_desc(s_top, kept, mine)] = mine;
         } else {
             out[tid] = 0ull;
         }
@@ -272,64 +262,6 @@ __global__ __launch_bounds__(EX_THREADS) void bm25_expand_merge_kernel(Bm25Expan
     }
 }
 
-// tmp |= the rows of [base, end) among post_pos[l0 .. l0 + len), one wave's lanes striding over them
-__device__ __forceinline__ void gr_stream_term(const int32_t *post_pos, int64_t l0, int len, int64_t base, int64_t end,
-                                               uint32_t *tmp, int lane) {
-    for (int i = lane; i < len; i += 64) {
-        const int64_t li = (int64_t)post_pos[l0 + i] - base;
-        if ((uint64_t)li >= (uint64_t)(end - base)) continue;   // (a list that does not ascend)
-        atomicOr(&tmp[li >> 5], 1u << (li & 31));
-    }
-}
-
-__global__ __launch_bounds__(GR_THREADS) void bm25_group_mask_kernel(Bm25GroupParams p) {
-    __shared__ uint32_t keep[GR_THREADS];
-    __shared__ uint32_t tmp[GR_THREADS];
-    __shared__ int64_t s_lo[GR_TERMS];
-    __shared__ int s_len[GR_TERMS];
-    const int rg = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
-    const int64_t gw = (int64_t)rg * BM25_RANGE_WORDS + tid;
-    const int64_t base = (int64_t)rg * BM25_RANGE;
-    int64_t end = base + BM25_RANGE < p.n ? base + BM25_RANGE : p.n;
-    if (end < base) end = base;   // a range of the stride padding: no rows
-
-    uint32_t word = 0;
-    if (gw < p.n_words) {
-        word = p.in ? p.in[(int64_t)q * p.in_stride_w + gw] : 0xffffffffu;
-        if (gw == p.n_words - 1 && (p.n & 31)) word &= (1u << (p.n & 31)) - 1u;
-    }
-    keep[tid] = word;
-    const int g0 = p.g_ptr[q], g1 = p.g_ptr[q + 1];
-    bool alive = g1 > g0 && __syncthreads_or(word != 0u);   // (g1 > g0 is uniform)
-    if (alive) {
-        const int tt0 = p.gt_ptr[g0], ntm = p.gt_ptr[g1] - tt0;   // <= GR_TERMS (the host checked the limits)
-        for (int i = tid; i < ntm; i += GR_THREADS) {
-            const int term = p.gt_terms[tt0 + i];
-            const int64_t a = p.post_ptr[term], b = p.post_ptr[term + 1];
-            const int64_t lo = lower_bound_asc(p.post_pos, a, b, base);
-            const int64_t hi = lower_bound_asc(p.post_pos, lo, b, end);
-            s_lo[i] = lo;
-            s_len[i] = (int)(hi - lo);
-        }
-        __syncthreads();
-        for (int g = g0; g < g1 && alive; ++g) {
-            const int kind = p.g_kind[g];
-            const int a = p.gt_ptr[g] - tt0, m = p.gt_ptr[g + 1] - p.gt_ptr[g];
-            if (kind == BM25_GROUP_EXC && m == 0) continue;   // (uniform) an empty excluded group has no effect
-            tmp[tid] = 0u;
-            __syncthreads();
-            for (int j = tid >> 6; j < m; j += GR_WAVES)
-                gr_stream_term(p.post_pos, s_lo[a + j], s_len[a + j], base, end, tmp, tid & 63);
-            __syncthreads();
-            keep[tid] = kind == BM25_GROUP_REQ ? keep[tid] & tmp[tid] : keep[tid] & ~tmp[tid];
-            // (the barrier of this vote also orders this group's reads of tmp before the next group zeroes it)
-            alive = __syncthreads_or(keep[tid] != 0u);
-        }
-    }
-    // keep[tid] is this thread's own word from the first line to the last: no barrier is needed for it
-    if (gw < p.stride_w) p.out[(int64_t)q * p.stride_w + gw] = keep[tid];
-}
-
 // scratch layout: slice_keys [np][n_slices][64] uint64 | slice_count [np][n_slices] int32
 inline int64_t ex_slices(int64_t n_terms) { return (n_terms + BM25_EXPAND_SLICE - 1) / BM25_EXPAND_SLICE; }
 
@@ -350,13 +282,6 @@ hipError_t launch_bm25_expand(const Bm25ExpandParams &p, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t launch_bm25_groups(const Bm25GroupParams &p, hipStream_t st) {
-    const int64_t n_ranges = (p.stride_w + BM25_RANGE_WORDS - 1) / BM25_RANGE_WORDS;
-    if (n_ranges > 0)
-        hipLaunchKernelGGL(bm25_group_mask_kernel, dim3((unsigned)n_ranges, (unsigned)p.nq), dim3(GR_THREADS), 0, st, p);
-    return hipGetLastError();
-}
-
 }  // namespace crag
 
 extern "C" int64_t crag_bm25_expand_scratch_bytes(int64_t n_terms, int n_patterns) {
@@ -373,7 +298,8 @@ extern "C" int crag_bm25_expand_host(const int64_t *d_term_ptr, const uint8_t *d
     if (n_patterns < 0 || n_patterns > crag::BM25_EXPAND_MAX_PATTERNS)
         return fail(CRAG_EINVAL, "bm25_expand_host: need 0 <= n_patterns <= %d (got %d)", crag::BM25_EXPAND_MAX_PATTERNS,
                     n_patterns);
-    if (n_terms < 0 || n_terms > INT32_MAX) return fail(CRAG_EINVAL, "bm25_expand_host: n_terms must be in [0, 2^31)");
+    int rc = check_bm25_counts("bm25_expand_host", 0, 0, 0, n_terms);   // (no queries, no rows: the vocabulary alone)
+    if (rc != CRAG_OK) return rc;
     if (n_patterns == 0) return CRAG_OK;   // no pattern: no output
     if (!h_pat_ptr || !h_pat_bytes || !h_pat_kind || !slot)
         return fail(CRAG_EINVAL, "bm25_expand_host: NULL pointer argument");
@@ -386,44 +312,34 @@ extern "C" int crag_bm25_expand_host(const int64_t *d_term_ptr, const uint8_t *d
         return fail(CRAG_EINVAL, "bm25_expand_host: NULL dictionary pointer");
     if (((uintptr_t)d_term_ptr & 7) || ((uintptr_t)d_post_ptr & 7))
         return fail(CRAG_EINVAL, "bm25_expand_host: term_ptr and post_ptr must be 8-byte aligned");
-    if (h_pat_ptr[0] != 0) return fail(CRAG_EINVAL, "bm25_expand_host: pat_ptr[0] must be 0");
+    rc = check_csr("bm25_expand_host", "pat_ptr", "pattern", h_pat_ptr, n_patterns, crag::BM25_EXPAND_MAX_BYTES);
+    if (rc != CRAG_OK) return rc;
     for (int i = 0; i < n_patterns; ++i) {
-        const int64_t len = (int64_t)h_pat_ptr[i + 1] - h_pat_ptr[i];
-        if (len < 0) return fail(CRAG_EINVAL, "bm25_expand_host: pat_ptr must not descend (pattern %d)", i);
-        if (len == 0) return fail(CRAG_EINVAL, "bm25_expand_host: pattern %d is empty", i);
-        if (len > crag::BM25_EXPAND_MAX_BYTES)
-            return fail(CRAG_EINVAL, "bm25_expand_host: pattern %d holds %lld bytes, at most %d", i, (long long)len,
-                        crag::BM25_EXPAND_MAX_BYTES);
+        if (h_pat_ptr[i + 1] == h_pat_ptr[i]) return fail(CRAG_EINVAL, "bm25_expand_host: pattern %d is empty", i);
         if (h_pat_kind[i] < crag::BM25_EXPAND_PREFIX || h_pat_kind[i] > crag::BM25_EXPAND_FUZZY2)
             return fail(CRAG_EINVAL, "bm25_expand_host: pattern %d has the unknown kind %d", i, h_pat_kind[i]);
     }
     const int64_t need = crag::bm25_expand_scratch_bytes(n_terms, n_patterns);
     if (need > 0) {
         if (!d_scratch) return fail(CRAG_EINVAL, "bm25_expand_host: NULL scratch");
-        int rc = check_scratch("bm25_expand_host", d_scratch, scratch_bytes, need, "crag_bm25_expand_scratch_bytes");
+        rc = check_scratch("bm25_expand_host", d_scratch, scratch_bytes, need, "crag_bm25_expand_scratch_bytes");
         if (rc != CRAG_OK) return rc;
     }
 
-    const int nb = h_pat_ptr[n_patterns];
     // slot layout: pat_ptr [np + 1] int32 | pat_kind [np] int32 | the patterns' bytes
-    const size_t head = (size_t)(2 * n_patterns + 1) * 4;
-    const size_t bytes = head + (size_t)nb;
-    void *h = nullptr, *d = nullptr;
-    int rc = crag_upload_slot_begin_(slot, bytes, &h, &d);
-    if (rc != CRAG_OK) return rc;
-    memcpy(h, h_pat_ptr, (size_t)(n_patterns + 1) * 4);
-    memcpy((char *)h + (size_t)(n_patterns + 1) * 4, h_pat_kind, (size_t)n_patterns * 4);
-    memcpy((char *)h + head, h_pat_bytes, (size_t)nb);
-    rc = crag_upload_slot_commit_(slot, bytes, stream);
-    if (rc != CRAG_OK) return rc;
+    UploadPack up;
+    const int i_ptr = up.add(h_pat_ptr, (size_t)n_patterns + 1);
+    const int i_kind = up.add(h_pat_kind, (size_t)n_patterns);
+    const int i_bytes = up.add(h_pat_bytes, (size_t)h_pat_ptr[n_patterns]);
+    if ((rc = up.begin(slot)) != CRAG_OK || (rc = up.commit(slot, stream)) != CRAG_OK) return rc;
 
     crag::Bm25ExpandParams p;
     p.term_ptr = d_term_ptr;
     p.term_bytes = d_term_bytes;
     p.post_ptr = d_post_ptr;
-    p.pat_ptr = (const int32_t *)d;
-    p.pat_kind = p.pat_ptr + n_patterns + 1;
-    p.pat_bytes = (const uint8_t *)d + head;
+    p.pat_ptr = up.dev<int32_t>(i_ptr);
+    p.pat_kind = up.dev<int32_t>(i_kind);
+    p.pat_bytes = up.dev<uint8_t>(i_bytes);
     p.n_terms = n_terms;
     p.n_slices = (int)crag::ex_slices(n_terms);
     p.np = n_patterns;
@@ -439,89 +355,5 @@ extern "C" int crag_bm25_expand_host(const int64_t *d_term_ptr, const uint8_t *d
     p.out_kept = d_out_kept;
     p.out_total = d_out_total;
     HIP_TRY(crag::launch_bm25_expand(p, (hipStream_t)stream));
-    return CRAG_OK;
-}
-
-extern "C" int crag_bm25_group_masks_host(const int64_t *d_post_ptr, const int32_t *d_post_pos, int64_t n_rows,
-                                          int64_t n_terms, const int32_t *h_g_ptr, const int32_t *h_g_kind,
-                                          const int32_t *h_gt_ptr, const int32_t *h_gt_terms, int nq,
-                                          const uint8_t *d_in_mask, int64_t in_stride, crag_upload_slot *slot,
-                                          uint8_t *d_out_mask, int64_t mask_stride, void *stream) {
-    // every check comes before the first HIP call: on error nothing is enqueued
-    if (nq < 1 || nq > crag::BM25_MAX_Q) return fail(CRAG_EINVAL, "bm25_group_masks_host: need 1 <= nq <= 64 (nq=%d)", nq);
-    if (n_rows < 0 || n_rows > INT32_MAX) return fail(CRAG_EINVAL, "bm25_group_masks_host: n_rows must be in [0, 2^31)");
-    if (n_terms < 0 || n_terms > INT32_MAX) return fail(CRAG_EINVAL, "bm25_group_masks_host: n_terms must be in [0, 2^31)");
-    const int64_t min_stride = (n_rows + 31) / 32 * 4;
-    if (mask_stride < 0 || mask_stride % 4 != 0 || mask_stride < min_stride || mask_stride > ((int64_t)1 << 32))
-        return fail(CRAG_EINVAL, "bm25_group_masks_host: mask_stride must be a multiple of 4 in [ceil(n_rows/32)*4, 2^32]");
-    if (d_in_mask && in_stride != 0 && (in_stride % 4 != 0 || in_stride < min_stride || in_stride > ((int64_t)1 << 32)))
-        return fail(CRAG_EINVAL, "bm25_group_masks_host: in_stride must be 0 or a multiple of 4 in [ceil(n_rows/32)*4, 2^32]");
-    if (!h_g_ptr || !slot) return fail(CRAG_EINVAL, "bm25_group_masks_host: NULL pointer argument");
-    if (n_rows > 0 && (!d_post_ptr || !d_post_pos)) return fail(CRAG_EINVAL, "bm25_group_masks_host: NULL postings pointer");
-    if (mask_stride > 0 && !d_out_mask) return fail(CRAG_EINVAL, "bm25_group_masks_host: NULL output pointer");
-    if (((uintptr_t)d_out_mask & 3) != 0) return fail(CRAG_EINVAL, "bm25_group_masks_host: the output must be 4-byte aligned");
-    if (((uintptr_t)d_in_mask & 3) != 0) return fail(CRAG_EINVAL, "bm25_group_masks_host: the input mask must be 4-byte aligned");
-    if (h_g_ptr[0] != 0) return fail(CRAG_EINVAL, "bm25_group_masks_host: g_ptr[0] must be 0");
-    for (int q = 0; q < nq; ++q) {
-        const int64_t cnt = (int64_t)h_g_ptr[q + 1] - h_g_ptr[q];
-        if (cnt < 0) return fail(CRAG_EINVAL, "bm25_group_masks_host: g_ptr must not descend (query %d)", q);
-        if (cnt > crag::BM25_GROUP_MAX)
-            return fail(CRAG_EINVAL, "bm25_group_masks_host: query %d has %lld groups, at most %d", q, (long long)cnt,
-                        crag::BM25_GROUP_MAX);
-    }
-    const int ng = h_g_ptr[nq];
-    if (ng > 0 && (!h_g_kind || !h_gt_ptr)) return fail(CRAG_EINVAL, "bm25_group_masks_host: NULL group arrays");
-    if (ng > 0 && h_gt_ptr[0] != 0) return fail(CRAG_EINVAL, "bm25_group_masks_host: gt_ptr[0] must be 0");
-    for (int g = 0; g < ng; ++g) {
-        const int kind = h_g_kind[g];
-        const int64_t m = (int64_t)h_gt_ptr[g + 1] - h_gt_ptr[g];
-        if (m < 0) return fail(CRAG_EINVAL, "bm25_group_masks_host: gt_ptr must not descend (group %d)", g);
-        if (kind != crag::BM25_GROUP_REQ && kind != crag::BM25_GROUP_EXC)
-            return fail(CRAG_EINVAL, "bm25_group_masks_host: group %d has the unknown kind %d", g, kind);
-        if (m > crag::BM25_EXPAND_KEEP)
-            return fail(CRAG_EINVAL, "bm25_group_masks_host: group %d holds %lld terms, at most %d", g, (long long)m,
-                        crag::BM25_EXPAND_KEEP);
-        if (m > 0 && !h_gt_terms) return fail(CRAG_EINVAL, "bm25_group_masks_host: NULL term array");
-        for (int i = h_gt_ptr[g]; i < h_gt_ptr[g + 1]; ++i)
-            if (h_gt_terms[i] < 0 || (int64_t)h_gt_terms[i] >= n_terms)
-                return fail(CRAG_EINVAL, "bm25_group_masks_host: term id %d of group %d is outside [0, n_terms)",
-                            h_gt_terms[i], g);
-    }
-    if (mask_stride == 0) return CRAG_OK;   // (n_rows is 0: the runs are empty)
-
-    const int ntm = ng > 0 ? h_gt_ptr[ng] : 0;
-    // slot layout: g_ptr [BM25_MAX_Q + 4] int32 | g_kind [ng] | gt_ptr [ng + 1] | gt_terms [ntm]
-    const size_t head = (size_t)(crag::BM25_MAX_Q + 4) * 4;
-    const size_t bytes = head + ((size_t)ng + (size_t)ng + 1 + (size_t)ntm) * 4;
-    void *h = nullptr, *d = nullptr;
-    int rc = crag_upload_slot_begin_(slot, bytes, &h, &d);
-    if (rc != CRAG_OK) return rc;
-    int32_t *hk = (int32_t *)((char *)h + head), *hp = hk + ng, *ht = hp + ng + 1;
-    memcpy(h, h_g_ptr, (size_t)(nq + 1) * 4);
-    if (ng > 0) {
-        memcpy(hk, h_g_kind, (size_t)ng * 4);
-        memcpy(hp, h_gt_ptr, (size_t)(ng + 1) * 4);
-        if (ntm > 0) memcpy(ht, h_gt_terms, (size_t)ntm * 4);
-    } else {
-        hp[0] = 0;
-    }
-    rc = crag_upload_slot_commit_(slot, bytes, stream);
-    if (rc != CRAG_OK) return rc;
-
-    crag::Bm25GroupParams p;
-    p.post_ptr = d_post_ptr;
-    p.post_pos = d_post_pos;
-    p.g_ptr = (const int32_t *)d;
-    p.g_kind = (const int32_t *)((const char *)d + head);
-    p.gt_ptr = p.g_kind + ng;
-    p.gt_terms = p.gt_ptr + ng + 1;
-    p.in = (const uint32_t *)d_in_mask;
-    p.in_stride_w = d_in_mask ? in_stride / 4 : 0;
-    p.out = (uint32_t *)d_out_mask;
-    p.stride_w = mask_stride / 4;
-    p.n = n_rows;
-    p.n_words = (n_rows + 31) / 32;
-    p.nq = nq;
-    HIP_TRY(crag::launch_bm25_groups(p, (hipStream_t)stream));
     return CRAG_OK;
 }

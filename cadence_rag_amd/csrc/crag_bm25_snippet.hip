@@ -28,6 +28,7 @@
 
 #include "../../include/crag_dense.h"
 #include "crag_kernels.h"
+#include "crag_postings.h"
 #include "crag_host.h"
 
 namespace crag {
@@ -56,17 +57,6 @@ __device__ __forceinline__ int sn_slot_of(const SnSlots &sl, int cnt, int i) {
     return lo;
 }
 
-// first index of a[0 .. n) (ascending) whose value is >= x
-template <class P> __device__ __forceinline__ int sn_lower(P a, int n, int x) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if ((int)a[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // round 2 and its reduction; STAGED: the slices are read from `stage`, else from post_where
 template <bool STAGED>
 __device__ __forceinline__ void sn_search(const SnSlots &sl, const uint16_t *stage, const uint16_t *where, int cnt, int total,
@@ -87,11 +77,11 @@ __device__ __forceinline__ void sn_search(const SnSlots &sl, const uint16_t *sta
             int at, v = INT32_MAX;
             if constexpr (STAGED) {
                 const uint16_t *a = stage + sl.base[k];
-                at = sn_lower(a, n, s);
+                at = lower_bound_u16(a, n, s);
                 if (at < n) v = a[at];
             } else {
                 const uint16_t *a = where + sl.off[k];
-                at = sn_lower(a, n, s);
+                at = lower_bound_u16(a, n, s);
                 if (at < n) v = a[at];
             }
             if (v < s + window) sc = __fadd_rn(sc, sl.w[k]);
@@ -133,11 +123,7 @@ __global__ __launch_bounds__(SN_LANES) void bm25_snippet_kernel(Bm25SnippetParam
         w = p.weights[t0 + lane];
         const int64_t a = p.post_ptr[term], b = p.post_ptr[term + 1];
         const int64_t pi = lower_bound_asc(p.post_pos, a, b, r);
-        if (pi < b && (int64_t)p.post_pos[pi] == r) {
-            off = p.post_off[pi];
-            const int64_t n = p.post_off[pi + 1] - off;
-            len = n > 0 ? (int)(n < 65536 ? n : 65536) : 0;
-        }
+        if (pi < b && (int64_t)p.post_pos[pi] == r) len = where_slice(p.post_off, pi, off);
     }
     const unsigned long long kept = __ballot(len > 0);
     if (!kept) {
@@ -189,11 +175,11 @@ __global__ __launch_bounds__(SN_LANES) void bm25_snippet_kernel(Bm25SnippetParam
         int at, v = -1;
         if (staged) {
             const uint16_t *a = stage + (incl - len);
-            at = sn_lower(a, len, end);
+            at = lower_bound_u16(a, len, end);
             if (at > 0) v = a[at - 1];
         } else {
             const uint16_t *a = p.post_where + off;
-            at = sn_lower(a, len, end);
+            at = lower_bound_u16(a, len, end);
             if (at > 0) v = a[at - 1];
         }
         if (v >= start) last = v;
@@ -228,32 +214,23 @@ extern "C" int crag_bm25_snippets_host(const int64_t *d_post_ptr, const int32_t 
                                        crag_upload_slot *slot, int32_t *d_start, int32_t *d_last, float *d_score,
                                        uint64_t *d_covered, void *stream) {
     // every check comes before the first HIP call: on error nothing is enqueued
-    if (nq < 1 || nq > crag::BM25_MAX_Q) return fail(CRAG_EINVAL, "bm25_snippets_host: need 1 <= nq <= 64 (nq=%d)", nq);
-    if (n_rows < 0 || n_rows > INT32_MAX) return fail(CRAG_EINVAL, "bm25_snippets_host: n_rows must be in [0, 2^31)");
-    if (n_terms < 0 || n_terms > INT32_MAX) return fail(CRAG_EINVAL, "bm25_snippets_host: n_terms must be in [0, 2^31)");
+    int rc = check_bm25_counts("bm25_snippets_host", nq, 1, n_rows, n_terms);
+    if (rc != CRAG_OK) return rc;
     if (window < 1 || window > 65535)
         return fail(CRAG_EINVAL, "bm25_snippets_host: window must be in [1, 65535] (got %d)", window);
     if (!h_q_ptr || !h_r_ptr || !slot) return fail(CRAG_EINVAL, "bm25_snippets_host: NULL pointer argument");
     if (!d_post_ptr || !d_post_pos) return fail(CRAG_EINVAL, "bm25_snippets_host: NULL postings pointer");
     if (!d_post_off || !d_post_where)
         return fail(CRAG_EINVAL, "bm25_snippets_host: NULL position arrays (an index built without positions)");
-    if (h_q_ptr[0] != 0 || h_r_ptr[0] != 0) return fail(CRAG_EINVAL, "bm25_snippets_host: q_ptr[0] and r_ptr[0] must be 0");
-    for (int q = 0; q < nq; ++q) {
-        const int64_t cnt = (int64_t)h_q_ptr[q + 1] - h_q_ptr[q];
-        if (cnt < 0) return fail(CRAG_EINVAL, "bm25_snippets_host: q_ptr must not descend (query %d)", q);
-        if (cnt > CRAG_BM25_SNIPPET_MAX_TERMS)
-            return fail(CRAG_EINVAL, "bm25_snippets_host: query %d has %lld term slots, at most %d", q, (long long)cnt,
-                        CRAG_BM25_SNIPPET_MAX_TERMS);
-        if (h_r_ptr[q + 1] < h_r_ptr[q]) return fail(CRAG_EINVAL, "bm25_snippets_host: r_ptr must not descend (query %d)", q);
-    }
+    rc = check_csr("bm25_snippets_host", "q_ptr", "query", h_q_ptr, nq, CRAG_BM25_SNIPPET_MAX_TERMS);
+    if (rc == CRAG_OK) rc = check_csr("bm25_snippets_host", "r_ptr", "query", h_r_ptr, nq, -1);
+    if (rc != CRAG_OK) return rc;
     const int nt = h_q_ptr[nq], npairs = h_r_ptr[nq];
     if (nt > 0 && (!h_terms || !h_weights)) return fail(CRAG_EINVAL, "bm25_snippets_host: NULL term or weight array");
-    for (int i = 0; i < nt; ++i) {
-        if (h_terms[i] < 0 || (int64_t)h_terms[i] >= n_terms)
-            return fail(CRAG_EINVAL, "bm25_snippets_host: term id %d is outside [0, n_terms)", h_terms[i]);
+    if ((rc = check_terms("bm25_snippets_host", h_terms, 0, nt, n_terms)) != CRAG_OK) return rc;
+    for (int i = 0; i < nt; ++i)
         if (!(h_weights[i] >= 0.f) || isinf(h_weights[i]))
             return fail(CRAG_EINVAL, "bm25_snippets_host: weight %d must be finite and >= 0", i);
-    }
     if (npairs > 0 && !h_rows) return fail(CRAG_EINVAL, "bm25_snippets_host: NULL row array");
     for (int i = 0; i < npairs; ++i)
         if (h_rows[i] < 0 || (int64_t)h_rows[i] >= n_rows)
@@ -266,32 +243,24 @@ extern "C" int crag_bm25_snippets_host(const int64_t *d_post_ptr, const int32_t 
 
     // slot layout: q_ptr [BM25_MAX_Q + 4] int32 | r_ptr [BM25_MAX_Q + 4] | terms [nt] | weights [nt] fp32 | rows [npairs]
     const size_t head = (size_t)(crag::BM25_MAX_Q + 4) * 4;
-    const size_t bytes = 2 * head + ((size_t)nt * 2 + (size_t)npairs) * 4;
-    void *h = nullptr, *d = nullptr;
-    int rc = crag_upload_slot_begin_(slot, bytes, &h, &d);
-    if (rc != CRAG_OK) return rc;
-    char *hb = (char *)h;
-    memcpy(hb, h_q_ptr, (size_t)(nq + 1) * 4);
-    memcpy(hb + head, h_r_ptr, (size_t)(nq + 1) * 4);
-    if (nt > 0) {
-        memcpy(hb + 2 * head, h_terms, (size_t)nt * 4);
-        memcpy(hb + 2 * head + (size_t)nt * 4, h_weights, (size_t)nt * 4);
-    }
-    memcpy(hb + 2 * head + (size_t)nt * 8, h_rows, (size_t)npairs * 4);
-    rc = crag_upload_slot_commit_(slot, bytes, stream);
-    if (rc != CRAG_OK) return rc;
+    UploadPack up;
+    const int i_q = up.add(h_q_ptr, (size_t)nq + 1, head);
+    const int i_r = up.add(h_r_ptr, (size_t)nq + 1, head);
+    const int i_terms = up.add(h_terms, (size_t)nt);
+    const int i_w = up.add(h_weights, (size_t)nt);
+    const int i_rows = up.add(h_rows, (size_t)npairs);
+    if ((rc = up.begin(slot)) != CRAG_OK || (rc = up.commit(slot, stream)) != CRAG_OK) return rc;
 
     crag::Bm25SnippetParams p;
-    const char *db = (const char *)d;
     p.post_ptr = d_post_ptr;
     p.post_pos = d_post_pos;
     p.post_off = d_post_off;
     p.post_where = d_post_where;
-    p.q_ptr = (const int32_t *)db;
-    p.r_ptr = (const int32_t *)(db + head);
-    p.terms = (const int32_t *)(db + 2 * head);
-    p.weights = (const float *)(db + 2 * head + (size_t)nt * 4);
-    p.rows = (const int32_t *)(db + 2 * head + (size_t)nt * 8);
+    p.q_ptr = up.dev<int32_t>(i_q);
+    p.r_ptr = up.dev<int32_t>(i_r);
+    p.terms = up.dev<int32_t>(i_terms);
+    p.weights = up.dev<float>(i_w);
+    p.rows = up.dev<int32_t>(i_rows);
     p.out_start = d_start;
     p.out_last = d_last;
     p.out_score = d_score;

@@ -1,5 +1,6 @@
 // crag_host.h — the host helpers shared by the translation units of the C ABI: error reporting, device selection,
-// grow-only device buffers, host-or-device inputs.  Host code only; hidden visibility: nothing here is exported.
+// grow-only device buffers, host-or-device inputs, the argument checks and the upload packer of the BM25 entries.  Host
+// code only; hidden visibility: nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -48,6 +49,79 @@ inline int check_scratch(const char *op, const void *scratch, int64_t have, int6
         return fail(CRAG_EINVAL, "%s: scratch too small or not 8-byte aligned (%s)", op, sizer);
     return CRAG_OK;
 }
+
+// The argument checks the BM25 entries share (crag_bm25*.hip).  All of them are host work: an entry runs them before its
+// first HIP call.
+// ptr [n + 1] is a CSR pointer: it starts at 0, never descends, and no entry holds more than `limit` (< 0: any number)
+inline int check_csr(const char *op, const char *name, const char *noun, const int32_t *ptr, int n, int64_t limit) {
+    if (ptr[0] != 0) return fail(CRAG_EINVAL, "%s: %s[0] must be 0", op, name);
+    for (int i = 0; i < n; ++i) {
+        const int64_t cnt = (int64_t)ptr[i + 1] - ptr[i];
+        if (cnt < 0) return fail(CRAG_EINVAL, "%s: %s must not descend (%s %d)", op, name, noun, i);
+        if (limit >= 0 && cnt > limit)
+            return fail(CRAG_EINVAL, "%s: %s %d holds %lld by %s, at most %lld", op, noun, i, (long long)cnt, name,
+                        (long long)limit);
+    }
+    return CRAG_OK;
+}
+inline int check_terms(const char *op, const int32_t *terms, int64_t a, int64_t b, int64_t n_terms) {
+    for (int64_t i = a; i < b; ++i)
+        if (terms[i] < 0 || (int64_t)terms[i] >= n_terms)
+            return fail(CRAG_EINVAL, "%s: term id %d (entry %lld) is outside [0, n_terms)", op, terms[i], (long long)i);
+    return CRAG_OK;
+}
+inline int check_bm25_counts(const char *op, int nq, int nq_min, int64_t n_rows, int64_t n_terms) {
+    if (nq < nq_min || nq > 64) return fail(CRAG_EINVAL, "%s: need %d <= nq <= 64 (nq=%d)", op, nq_min, nq);
+    if (n_rows < 0 || n_rows > INT32_MAX) return fail(CRAG_EINVAL, "%s: n_rows must be in [0, 2^31)", op);
+    if (n_terms < 0 || n_terms > INT32_MAX) return fail(CRAG_EINVAL, "%s: n_terms must be in [0, 2^31)", op);
+    return CRAG_OK;
+}
+// the input and output runs of an entry that turns row masks into row masks
+inline int check_mask_strides(const char *op, int64_t n_rows, const void *d_in, int64_t in_stride, const void *d_out,
+                              int64_t out_stride) {
+    const int64_t min_stride = (n_rows + 31) / 32 * 4;
+    if (out_stride < 0 || out_stride % 4 != 0 || out_stride < min_stride || out_stride > ((int64_t)1 << 32))
+        return fail(CRAG_EINVAL, "%s: mask_stride must be a multiple of 4 in [ceil(n_rows/32)*4, 2^32]", op);
+    if (d_in && in_stride != 0 && (in_stride % 4 != 0 || in_stride < min_stride || in_stride > ((int64_t)1 << 32)))
+        return fail(CRAG_EINVAL, "%s: in_stride must be 0 or a multiple of 4 in [ceil(n_rows/32)*4, 2^32]", op);
+    if (out_stride > 0 && !d_out) return fail(CRAG_EINVAL, "%s: NULL output pointer", op);
+    if (((uintptr_t)d_out & 3) != 0) return fail(CRAG_EINVAL, "%s: the output must be 4-byte aligned", op);
+    if (((uintptr_t)d_in & 3) != 0) return fail(CRAG_EINVAL, "%s: the input mask must be 4-byte aligned", op);
+    return CRAG_OK;
+}
+
+// One upload through a slot, laid out once: add() declares the arrays in slot order (count elements are copied from p,
+// `reserve` bytes are kept for them -- a padded head reserves more than it copies), begin() takes the slot's buffers and
+// copies, commit() enqueues the upload, dev<T>(i) is array i on the device.  What begin() does not copy is not written.
+struct UploadPack {
+    static constexpr int MAX_ARRAYS = 6;
+    const void *src[MAX_ARRAYS];
+    size_t copy[MAX_ARRAYS], off[MAX_ARRAYS];
+    int n = 0;
+    size_t bytes = 0;
+    char *h = nullptr, *d = nullptr;
+    template <class T> int add(const T *p, size_t count, size_t reserve) {
+        src[n] = p;
+        copy[n] = count * sizeof(T);
+        off[n] = bytes;
+        bytes += reserve;
+        return n++;
+    }
+    template <class T> int add(const T *p, size_t count) { return add(p, count, count * sizeof(T)); }
+    int begin(crag_upload_slot *slot) {
+        void *hv = nullptr, *dv = nullptr;
+        const int rc = crag_upload_slot_begin_(slot, bytes, &hv, &dv);
+        if (rc != CRAG_OK) return rc;
+        h = (char *)hv;
+        d = (char *)dv;
+        for (int i = 0; i < n; ++i)
+            if (copy[i] > 0) memcpy(h + off[i], src[i], copy[i]);
+        return CRAG_OK;
+    }
+    int commit(crag_upload_slot *slot, void *stream) { return crag_upload_slot_commit_(slot, bytes, stream); }
+    template <class T> T *host(int i) const { return (T *)(h + off[i]); }
+    template <class T> const T *dev(int i) const { return (const T *)(d + off[i]); }
+};
 
 // behind one or more hipLaunchKernelGGL
 inline int launch_ok(const char *what) {

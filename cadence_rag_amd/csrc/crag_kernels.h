@@ -221,21 +221,25 @@ struct Bm25Params {
 int64_t bm25_scratch_bytes(int64_t n_rows, int nq, int k);
 hipError_t launch_bm25(const Bm25Params &p, hipStream_t st);
 
-// ---- BM25 query clauses as row masks (crag_bm25_clause.hip) ----
+// ---- BM25 query clauses and any-of groups as row masks (crag_bm25_clause.hip) ----
 constexpr int BM25_RANGE_WORDS = BM25_RANGE / 32;   // mask words one workgroup owns
 constexpr int BM25_CLAUSE_MAX = 16;                 // constraint clauses per query
 constexpr int BM25_PHRASE_MAX = 8;                  // terms per phrase
 constexpr int BM25_KIND_REQ_TERM = 0, BM25_KIND_EXC_TERM = 1, BM25_KIND_REQ_PHRASE = 2, BM25_KIND_EXC_PHRASE = 3,
               BM25_KIND_NOTHING = 4;
+constexpr int BM25_GROUP_MAX = 16;                  // any-of groups per query
+constexpr int BM25_GROUP_REQ = 0, BM25_GROUP_EXC = 1;
 
-struct Bm25ClauseParams {
+// one block for both mask kernels: "clause" below is a clause of bm25_clause_mask_kernel or a group of
+// bm25_group_mask_kernel (whose launch leaves post_off, post_where and has_phrase unset)
+struct Bm25MaskParams {
     const int64_t *post_ptr;     // [V + 1]
     const int32_t *post_pos;     // [nnz] row positions, ascending inside a term
     const int64_t *post_off;     // [nnz + 1] token positions of posting j: post_where[post_off[j] .. post_off[j + 1])
     const uint16_t *post_where;  // token positions, ascending inside a posting (NULL with post_off: no phrase clause)
-    const int32_t *c_ptr;        // [nq + 1] clauses of query q: [c_ptr[q], c_ptr[q + 1]), at most BM25_CLAUSE_MAX
-    const int32_t *c_kind;       // [n_clauses] BM25_KIND_*
-    const int32_t *ct_ptr;       // [n_clauses + 1] terms of clause c: ct_terms[ct_ptr[c] .. ct_ptr[c + 1])
+    const int32_t *c_ptr;        // [nq + 1] clauses of query q: [c_ptr[q], c_ptr[q + 1]), at most BM25_CLAUSE_MAX / _GROUP_MAX
+    const int32_t *c_kind;       // [n_clauses] BM25_KIND_* / BM25_GROUP_*
+    const int32_t *ct_ptr;       // [n_clauses + 1] terms of clause c: ct_terms[ct_ptr[c] .. ct_ptr[c + 1]); a group: at most 64
     const int32_t *ct_terms;     // term ids, in phrase order
     const uint32_t *in;          // nullable: every row below n is admitted
     int64_t in_stride_w;         // mask words per input run, 0: one run shared by all queries
@@ -245,7 +249,8 @@ struct Bm25ClauseParams {
     int nq;
     int has_phrase;              // some clause is a phrase: the kernel variant with the phrase's LDS
 };
-hipError_t launch_bm25_clause(const Bm25ClauseParams &p, hipStream_t st);
+hipError_t launch_bm25_clause(const Bm25MaskParams &p, hipStream_t st);
+hipError_t launch_bm25_groups(const Bm25MaskParams &p, hipStream_t st);
 
 // ---- BM25 prefix and fuzzy terms expanded over the vocabulary (crag_bm25_expand.hip) ----
 constexpr int BM25_EXPAND_SLICE = 4096;             // vocabulary terms per workgroup of the match kernel
@@ -253,8 +258,6 @@ constexpr int BM25_EXPAND_KEEP = 64;                // kept expansions per patte
 constexpr int BM25_EXPAND_MAX_PATTERNS = 512;       // patterns per call
 constexpr int BM25_EXPAND_MAX_BYTES = 255;          // bytes per pattern (the tokenizer's limit)
 constexpr int BM25_EXPAND_PREFIX = 0, BM25_EXPAND_FUZZY1 = 1, BM25_EXPAND_FUZZY2 = 2;
-constexpr int BM25_GROUP_MAX = 16;                  // any-of groups per query
-constexpr int BM25_GROUP_REQ = 0, BM25_GROUP_EXC = 1;
 
 struct Bm25ExpandParams {
     const int64_t *term_ptr;     // [V + 1] byte offsets of the terms in term_bytes
@@ -276,22 +279,6 @@ struct Bm25ExpandParams {
 };
 int64_t bm25_expand_scratch_bytes(int64_t n_terms, int np);
 hipError_t launch_bm25_expand(const Bm25ExpandParams &p, hipStream_t st);
-
-struct Bm25GroupParams {
-    const int64_t *post_ptr;     // [V + 1]
-    const int32_t *post_pos;     // [nnz] row positions, ascending inside a term
-    const int32_t *g_ptr;        // [nq + 1] groups of query q: [g_ptr[q], g_ptr[q + 1]), at most BM25_GROUP_MAX
-    const int32_t *g_kind;       // [n_groups] BM25_GROUP_*
-    const int32_t *gt_ptr;       // [n_groups + 1] terms of group g: gt_terms[gt_ptr[g] .. gt_ptr[g + 1]), at most 64
-    const int32_t *gt_terms;
-    const uint32_t *in;          // nullable: every row below n is admitted
-    int64_t in_stride_w;         // mask words per input run, 0: one run shared by all queries
-    uint32_t *out;               // [nq][stride_w]
-    int64_t stride_w;
-    int64_t n, n_words;
-    int nq;
-};
-hipError_t launch_bm25_groups(const Bm25GroupParams &p, hipStream_t st);
 
 // ---- BM25 query-aware snippet windows (crag_bm25_snippet.hip) ----
 constexpr int BM25_SNIPPET_TERMS = 64;              // term slots per query: one per lane (CRAG_BM25_SNIPPET_MAX_TERMS)

@@ -59,36 +59,17 @@ class FilterColumns:
         self.generation = generation
         self.device = device
         self.d_started_us = self.d_call_slot = None
-        self._slots: dict = {}   # per stream: ring of upload slots (the idiom of TechTokenIndex._slot)
+        self._ring = _native.UploadRing(device)
         if device is not None:
             import torch
             self.d_started_us = torch.from_numpy(self.started_us).to(device)
             self.d_call_slot = torch.from_numpy(self.call_slot).to(device)
 
     def _slot(self, stream: int):
-        import torch
-        ring = self._slots.setdefault(stream, {"next": 0, "slots": []})
-        if len(ring["slots"]) < 4:
-            with torch.cuda.device(self.device):
-                handle = _native.load().crag_upload_slot_create()
-            if not handle:
-                raise _native.NativeLibraryError(f"crag_upload_slot_create failed: {_native.last_error()}")
-            ring["slots"].append(handle)
-        slot = ring["slots"][ring["next"] % len(ring["slots"])]
-        ring["next"] += 1
-        return slot
+        return self._ring.slot(stream)
 
     def close(self) -> None:
-        rings, self._slots = getattr(self, "_slots", {}), {}
-        for ring in rings.values():
-            for handle in ring["slots"]:
-                _native.load().crag_upload_slot_destroy(handle)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # interpreter shutdown: the library may be gone already
-            pass
+        self._ring.close()
 
     def masks(self, qset: Optional[np.ndarray], date_from: np.ndarray, date_to: np.ndarray, stride: Optional[int] = None,
               out=None, stream: Optional[int] = None):
@@ -276,7 +257,7 @@ class AttributeColumns:
         self.generation = generation
         self.device = device
         self.d_attr_ptr = self.d_attr_ids = None
-        self._slots: dict = {}
+        self._ring = _native.UploadRing(device)
         if device is not None:
             import torch
             self.d_attr_ptr = torch.from_numpy(self.attr_ptr).to(device)
@@ -285,7 +266,6 @@ class AttributeColumns:
 
     _slot = FilterColumns._slot
     close = FilterColumns.close
-    __del__ = FilterColumns.__del__
 
     def masks(self, compiled: Tuple[np.ndarray, np.ndarray, np.ndarray], in_mask=None, in_stride: int = 0,
               stride: Optional[int] = None, out=None, stream: Optional[int] = None, nq: Optional[int] = None):

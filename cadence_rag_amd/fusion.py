@@ -119,7 +119,8 @@ class TechTokenIndex:
         self.tokens = torch.from_numpy(toks.view(np.int64)).to(device)
         self.ids = torch.from_numpy(ids).to(device)
         self._bitmaps: dict = {}   # per stream: two streams sharing one index must not share scratch
-        self._pinned: dict = {}    # per stream: ring of pinned upload buffers for the query tokens
+        self._ring = _native.UploadRing(device)   # pinned upload buffers for the query tokens
+        self._outs: dict = {}      # per stream: the borrowed output tensors of every slot of the ring, by k
         self._rank_of_id = None
         self._order_host, self._ids_host = order, ids
         self._row_tokens = [frozenset(t) for t in row_tokens] if verify else None
@@ -132,29 +133,15 @@ class TechTokenIndex:
         [Round 3: four torch.empty on the device per call, two copies, blake2b per token: 156 us of host time around
         22 us of kernels; round 4 first: a pinned torch buffer packed with numpy, 65 us; the packing, the copy and the
         event now live behind crag_tech_lane_host.]"""
-        ring = self._pinned.setdefault(stream, {"next": 0, "slots": []})
-        if len(ring["slots"]) < 4:
-            with torch.cuda.device(self.device):
-                handle = _native.load().crag_upload_slot_create()
-            if not handle:
-                raise _native.NativeLibraryError(f"crag_upload_slot_create failed: {_native.last_error()}")
-            ring["slots"].append({"handle": handle, "out": {}})
-        slot = ring["slots"][ring["next"] % len(ring["slots"])]
-        ring["next"] += 1
-        return slot
+        at, handle = self._ring.take(stream)
+        outs = self._outs.get(stream)
+        if outs is None:
+            outs = self._outs[stream] = [{} for _ in range(self._ring.SIZE)]
+        return handle, outs[at]
 
     def close(self) -> None:
-        """Free the upload slots (pinned host memory).  Called by __del__ as well."""
-        rings, self._pinned = getattr(self, "_pinned", {}), {}
-        for ring in rings.values():
-            for slot in ring["slots"]:
-                _native.load().crag_upload_slot_destroy(slot["handle"])
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # interpreter shutdown: the library may be gone already
-            pass
+        """Free the upload slots (pinned host memory); the ring does so as well when it is collected."""
+        self._ring.close()
 
     _E2BIG = -5   # crag_dense.h CRAG_E2BIG: a query with more than 32 distinct tokens, nothing was enqueued
 
@@ -171,17 +158,17 @@ class TechTokenIndex:
         if not len(flat):
             flat = _ONE_ZERO                     # (a valid address; no query reads it: all counts are 0)
         words = max((self.n + 63) // 64, 1)
-        slot = self._slot(stream)
+        handle, slot_out = self._slot(stream)
         bitmap = self._bitmaps.get(stream)
         if bitmap is None or bitmap.numel() < nq * words:
             with _on_stream(stream, self.device):
                 bitmap = self._bitmaps[stream] = torch.empty(64 * words, dtype=torch.int64, device=self.device)
         if borrow:
-            outs = slot["out"].get(k)
+            outs = slot_out.get(k)
             if outs is None:
                 with _on_stream(stream, self.device):
-                    outs = slot["out"][k] = (torch.empty(64, k, dtype=torch.int64, device=self.device),
-                                             torch.empty(64, dtype=torch.int32, device=self.device))
+                    outs = slot_out[k] = (torch.empty(64, k, dtype=torch.int64, device=self.device),
+                                          torch.empty(64, dtype=torch.int32, device=self.device))
             out_ids, out_ct = outs[0][:nq], outs[1][:nq]
         else:   # fresh outputs: ONE allocation, the counts behind the ids -- on the caller's stream (entering a stream
                 # context costs ~5 us: skipped when torch's current stream already is that stream)
@@ -197,7 +184,7 @@ class TechTokenIndex:
         rc = _native.load().crag_tech_lane_host(ptrs[0], ptrs[1], ptrs[2], ptrs[3], self.n, flat.buffer_info()[0],
                                                 lens.buffer_info()[0], nq, int(k),
                                                 None if row_mask is None else row_mask.data_ptr(), int(mask_stride),
-                                                slot["handle"], bitmap.data_ptr(), out_ids.data_ptr(), out_ct.data_ptr(),
+                                                handle, bitmap.data_ptr(), out_ids.data_ptr(), out_ct.data_ptr(),
                                                 ctypes.c_void_p(stream))
         if rc == self._E2BIG:
             return None

@@ -131,8 +131,8 @@ class NgramIndex(Bm25Index):
         self.text = np.empty(0, dtype=np.uint8)
         self.text_ptr = np.zeros(1, dtype=np.int64)
         self.ids = np.empty(0, dtype=np.int64)
-        self._slots = {}
-        self._scratch = {}
+        self._ring = _native.UploadRing(self.device)
+        self._buffers = {}
         self._append(rows_bytes, ids)
         self._build()
 
@@ -207,7 +207,7 @@ class NgramIndex(Bm25Index):
         self.d_keys, self.d_post_ptr, self.d_post_pos, self.d_post_tf = d_keys, d_post_ptr, d_post_pos, d_post_tf
         self.d_doc_len = d_doc_len
         self.d_ids = torch.from_numpy(self.ids if n else np.zeros(1, dtype=np.int64)).to(dev)
-        self._scratch = {}
+        self._buffers = {}
 
     def host_csr(self):
         """The device's inverted CSR as numpy arrays: post_ptr [V + 1] int64, post_pos [nnz] int32, post_tf [nnz] uint16."""

@@ -268,6 +268,53 @@ def test_random_corpus(random_case):
                 assert case.oracle.holds_phrase_rows(terms)[r] == holds_phrase(rows[r], terms)
 
 
+# ---- the frame the clause kernel shares with the any-of groups ----------------------------------------------------------
+def test_term_clauses_are_any_of_groups_of_one_term(gpu):
+    """REQ_TERM t == REQ_ANY {t}, EXC_TERM t == EXC_ANY {t}, MATCH_NOTHING == REQ_ANY {}: the same bytes from
+    crag_bm25_clause_masks_host and crag_bm25_group_masks_host, and the oracle's.  n = RANGE + 1 (the second range holds
+    one row), 8 bytes of stride padding, a per-query input mask with its last valid bit set and row RANGE - 1 cleared;
+    term 0 is held by every row, term 1 by rows RANGE - 1 and RANGE alone, term 2 by none."""
+    n = R + 1
+    rows = [np.array([0])] * (R - 1) + [np.array([0, 1])] * 2
+    case = Case(rows, 3)
+    try:
+        ix, lib = case.ix, _native.load()
+        stride = (n + 31) // 32 * 4 + 8
+        in_mask = np.ones((3, n), dtype=bool)
+        in_mask[:, R - 1] = False
+        in_mask[1, 7] = in_mask[2, R - 2] = False                       # (per query: the runs differ)
+        d_in = torch.from_numpy(np.ascontiguousarray(DenseIndex.pack_mask(in_mask))).to(DEV)
+        in_stride = d_in.shape[-1]
+        ptr, t_ptr1, t_ptr0 = np.arange(4, dtype=np.int32), np.arange(4, dtype=np.int32), np.zeros(4, dtype=np.int32)
+        terms = np.arange(3, dtype=np.int32)
+
+        def launch(entry, extra, kind, t_ptr):
+            kinds = np.full(3, kind, dtype=np.int32)
+            out = torch.full((3 * stride + GUARD,), 0xA5, dtype=torch.uint8, device=DEV)
+            rc = getattr(lib, entry)(ix.d_post_ptr.data_ptr(), ix.d_post_pos.data_ptr(), *extra, n, 3, ptr.ctypes.data,
+                                     kinds.ctypes.data, t_ptr.ctypes.data, terms.ctypes.data if t_ptr[-1] else None, 3,
+                                     d_in.data_ptr(), in_stride, case.slot, out.data_ptr(), stride, None)
+            assert rc == 0, _native.last_error()
+            got = out.cpu().numpy()
+            assert np.all(got[3 * stride:] == 0xA5), "the guard zone behind the runs was written"
+            return got[:3 * stride]
+
+        where = (ix.d_post_off.data_ptr(), ix.d_post_where.data_ptr())
+        for clause_kind, group_kind, t_ptr in [(RT, 0, t_ptr1), (XT, 1, t_ptr1), (NOTHING, 0, t_ptr0)]:
+            queries = [[(clause_kind, (t,) if t_ptr[-1] else ())] for t in range(3)]
+            want = packed(case.oracle.mask(queries, in_mask), stride)
+            by_clause = launch("crag_bm25_clause_masks_host", where, clause_kind, t_ptr)
+            by_group = launch("crag_bm25_group_masks_host", (), group_kind, t_ptr)
+            assert np.array_equal(by_clause, by_group) and np.array_equal(by_clause, want), (clause_kind, group_kind)
+            for got in (by_clause, by_group):                           # the stride padding is zero
+                assert not got.reshape(3, stride)[:, (n + 31) // 32 * 4:].any()
+        # what the shapes are for: the required rare term keeps row RANGE alone, the last valid bit of the second range
+        rare = case.oracle.mask([[(RT, (1,))]], in_mask[:1])[0]
+        assert rare[R] and rare.sum() == 1
+    finally:
+        case.close()
+
+
 # ---- refusals ---------------------------------------------------------------------------------------------------------
 def test_every_einval_leaves_the_buffer_untouched(gpu):
     rng = np.random.default_rng(11)
