@@ -13,14 +13,12 @@
 // id to entry number (ATTR_SLOTS = 1024 slots for at most 512 distinct keys: load <= 0.5, LDS compare-and-swap on the
 // slot, linear probing behind a multiplicative hash) and copies the entries' query sets [n_keys][NU] beside it, NU = the
 // number of clauses any query uses, rounded up to 1, 2, 4 or 8 (the kernel is instantiated per NU, so that have[] lives
-// in registers).  It then walks spans of ATTR_SPAN = 1024 consecutive row positions = 32 mask words of every query with a
-// grid stride; the spans cover the words [0, mask_stride / 4) of a run, so the zeros beyond n_rows and in the stride
-// padding come from the same code as the bits.  One lane per row: it reads its attr_ptr pair, walks its ids (neighbouring
-// lanes' lists are neighbours in memory), probes the table per id and ORs the hit's words into have[].  nq ballots, every
-// lane taking part, transpose the 64 x 64 bit matrix as in crag_filter.hip; the words meet in LDS ([query][33]) and leave
-// as 128 contiguous bytes per query and span.  The input mask is applied at the write-out, where a thread holds (query,
-// word): the same thread reads and writes a word, which is what makes the in-place form safe.  Plain stores only, no
-// global atomics: the output is a function of the input alone, whatever the launch geometry.
+// in registers).  It then walks the spans of crag_maskspan.h (1024 consecutive row positions = 32 mask words of every
+// query) with a grid stride; the spans cover the words [0, mask_stride / 4) of a run.  What is this file's own is the
+// middle: one lane per row reads its attr_ptr pair, walks its ids (neighbouring lanes' lists are neighbours in memory),
+// probes the table per id and ORs the hit's words into have[].  The transpose, the LDS staging and the write-out are the
+// header's; the input mask is applied at the write-out, where a thread holds (query, word): the same thread reads and
+// writes a word, which is what makes the in-place form safe.  Plain stores only, no global atomics.
 // Known weakness: a row with hundreds of attributes holds its wave for the length of its list.
 #include "crag_arch.h"
 #include <hip/hip_runtime.h>
@@ -28,24 +26,17 @@
 
 #include "../../include/crag_dense.h"
 #include "crag_host.h"
-
+#include "crag_maskspan.h"
 
 namespace crag {
 namespace {
 
-constexpr int ATTR_THREADS = 256;
-constexpr int ATTR_WAVES = ATTR_THREADS / 64;
-constexpr int ATTR_SPAN = 1024;                         // row positions per span
-constexpr int ATTR_SPAN_WORDS = ATTR_SPAN / 32;         // mask words per query and span
-constexpr int ATTR_GROUPS = ATTR_SPAN / 64 / ATTR_WAVES;   // 64-row groups per wave and span
-constexpr int ATTR_LDS_STRIDE = ATTR_SPAN_WORDS + 1;
 constexpr int ATTR_SLOTS = 1024;                        // of the key table: a power of two >= 2 * CRAG_ATTR_MAX_KEYS
 constexpr int ATTR_SLOT_BITS = 10;
 constexpr int32_t ATTR_EMPTY = -1;                      // no key is negative
 constexpr int ATTR_WGS_PER_CU = 2;                      // persistent grid = this many workgroups per CU, at most
 
-static_assert(ATTR_SPAN_WORDS == 32, "the write-out maps 32 consecutive threads to one query's words");
-static_assert(CRAG_ATTR_MAX_QUERIES == 64, "one ballot lane and one set bit per query");
+static_assert(CRAG_ATTR_MAX_QUERIES == MASK_MAX_QUERIES, "one ballot lane and one set bit per query");
 static_assert(ATTR_SLOTS == 1 << ATTR_SLOT_BITS && ATTR_SLOTS >= 2 * CRAG_ATTR_MAX_KEYS, "load <= 0.5");
 static_assert(CRAG_ATTR_MAX_CLAUSES == 8, "NU is one of 1, 2, 4, 8");
 
@@ -67,19 +58,19 @@ struct AttrParams {
 __device__ __forceinline__ uint32_t attr_hash(int32_t id) { return ((uint32_t)id * 0x9E3779B1u) >> (32 - ATTR_SLOT_BITS); }
 
 template <int NU>
-__global__ __launch_bounds__(ATTR_THREADS) void attr_masks_kernel(AttrParams p) {
+__global__ __launch_bounds__(MASK_THREADS) void attr_masks_kernel(AttrParams p) {
     __shared__ int32_t s_key[ATTR_SLOTS];
     __shared__ uint16_t s_ent[ATTR_SLOTS];
     __shared__ uint64_t s_sets[CRAG_ATTR_MAX_KEYS * NU];
-    __shared__ uint32_t s_words[CRAG_ATTR_MAX_QUERIES * ATTR_LDS_STRIDE];
+    __shared__ uint32_t s_words[MASK_LDS_WORDS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nq = p.nq, n_keys = p.n_keys;
 
     // the key table and the entries' query sets, once per workgroup
-    for (int s = tid; s < ATTR_SLOTS; s += ATTR_THREADS) s_key[s] = ATTR_EMPTY;
-    for (int e = tid; e < n_keys * NU; e += ATTR_THREADS) s_sets[e] = p.sets[e];
+    for (int s = tid; s < ATTR_SLOTS; s += MASK_THREADS) s_key[s] = ATTR_EMPTY;
+    for (int e = tid; e < n_keys * NU; e += MASK_THREADS) s_sets[e] = p.sets[e];
     __syncthreads();
-    for (int j = tid; j < n_keys; j += ATTR_THREADS) {
+    for (int j = tid; j < n_keys; j += MASK_THREADS) {
         const int32_t key = p.keys[j];
         uint32_t h = attr_hash(key);
         // keys are distinct and n_keys <= ATTR_SLOTS / 2: a free slot exists, the walk ends
@@ -93,11 +84,11 @@ __global__ __launch_bounds__(ATTR_THREADS) void attr_masks_kernel(AttrParams p) 
     }
     __syncthreads();
 
-    const int64_t n_spans = (p.stride_w + ATTR_SPAN_WORDS - 1) / ATTR_SPAN_WORDS;
+    const int64_t n_spans = (p.stride_w + MASK_SPAN_WORDS - 1) / MASK_SPAN_WORDS;
     for (int64_t span = blockIdx.x; span < n_spans; span += gridDim.x) {
-        const int64_t row0 = span * ATTR_SPAN;
-        for (int g = 0; g < ATTR_GROUPS; ++g) {
-            const int gl = wave * ATTR_GROUPS + g;            // the group's number inside the span
+        const int64_t row0 = span * MASK_SPAN;
+        for (int g = 0; g < MASK_GROUPS; ++g) {
+            const int gl = wave * MASK_GROUPS + g;            // the group's number inside the span
             const int64_t i = row0 + (int64_t)gl * 64 + lane;
             uint64_t bits = 0;
             if (i < p.n) {
@@ -126,46 +117,12 @@ __global__ __launch_bounds__(ATTR_THREADS) void attr_masks_kernel(AttrParams p) 
                 for (int c = 0; c < NU; ++c) bits &= have[c] | ~p.clause[c];
             }
             // every lane takes part in every ballot: the lanes beyond n_rows hold 0
-            const uint32_t blo = (uint32_t)bits, bhi = (uint32_t)(bits >> 32);
-            uint64_t mine = 0;
-            for (int q = 0; q < nq && q < 32; ++q) {
-                const uint64_t b = __ballot((blo >> q) & 1u);
-                if (lane == q) mine = b;
-            }
-            for (int q = 32; q < nq; ++q) {
-                const uint64_t b = __ballot((bhi >> (q - 32)) & 1u);
-                if (lane == q) mine = b;
-            }
-            if (lane < nq) {
-                s_words[lane * ATTR_LDS_STRIDE + 2 * gl] = (uint32_t)mine;
-                s_words[lane * ATTR_LDS_STRIDE + 2 * gl + 1] = (uint32_t)(mine >> 32);
-            }
+            stage_group(s_words, gl, lane, nq, ballot_transpose(bits, nq, lane));
         }
         __syncthreads();
-        // 32 consecutive threads write one query's 32 words; a word at or beyond the stride belongs to the next run.  An
-        // input run is read only where it is sure to exist (the words that hold rows); beyond them the word is 0 anyway.
-        const int w = tid & 31;
-        const int64_t gw = span * ATTR_SPAN_WORDS + w;
-        if (gw < p.stride_w)
-            for (int q = tid >> 5; q < nq; q += ATTR_THREADS / 32) {
-                uint32_t word = s_words[q * ATTR_LDS_STRIDE + w];
-                if (p.in && gw < p.n_words) word &= p.in[(int64_t)q * p.in_stride_w + gw];
-                p.out[(int64_t)q * p.stride_w + gw] = word;
-            }
+        store_span(s_words, span, p.stride_w, nq, p.out, p.in, p.in_stride_w, p.n_words);
         __syncthreads();   // the next span overwrites s_words
     }
-}
-
-int attr_cu_count() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-            n = v;
-        else
-            n = 256;
-    }
-    return n;
 }
 
 }  // namespace
@@ -180,17 +137,11 @@ extern "C" int crag_attr_masks_host(const int64_t *d_attr_ptr, const int32_t *d_
     if (n_rows < 0 || n_rows > INT32_MAX) return fail(CRAG_EINVAL, "attr_masks_host: n_rows must be in [0, 2^31)");
     if (n_attrs < 0) return fail(CRAG_EINVAL, "attr_masks_host: n_attrs must not be negative");
     if (n_keys < 0) return fail(CRAG_EINVAL, "attr_masks_host: n_keys must not be negative");
-    const int64_t min_stride = (n_rows + 31) / 32 * 4;
-    if (mask_stride < 0 || mask_stride % 4 != 0 || mask_stride < min_stride || mask_stride > ((int64_t)1 << 32))
-        return fail(CRAG_EINVAL, "attr_masks_host: mask_stride must be a multiple of 4 in [ceil(n_rows/32)*4, 2^32]");
-    if (d_in_mask && in_stride != 0 && (in_stride % 4 != 0 || in_stride < min_stride || in_stride > ((int64_t)1 << 32)))
-        return fail(CRAG_EINVAL, "attr_masks_host: in_stride must be 0 or a multiple of 4 in [ceil(n_rows/32)*4, 2^32]");
+    int rc = check_mask_strides("attr_masks_host", n_rows, d_in_mask, in_stride, d_out_mask, mask_stride);
+    if (rc != CRAG_OK) return rc;
     if (!h_clause_sets || !slot) return fail(CRAG_EINVAL, "attr_masks_host: NULL pointer argument");
     if (n_keys > 0 && (!h_keys || !h_key_sets)) return fail(CRAG_EINVAL, "attr_masks_host: NULL key pointer");
     if (n_rows > 0 && (!d_attr_ptr || !d_attr_ids)) return fail(CRAG_EINVAL, "attr_masks_host: NULL column pointer");
-    if (mask_stride > 0 && !d_out_mask) return fail(CRAG_EINVAL, "attr_masks_host: NULL output pointer");
-    if (((uintptr_t)d_out_mask & 3) != 0) return fail(CRAG_EINVAL, "attr_masks_host: the output must be 4-byte aligned");
-    if (((uintptr_t)d_in_mask & 3) != 0) return fail(CRAG_EINVAL, "attr_masks_host: the input mask must be 4-byte aligned");
     if (n_keys > CRAG_ATTR_MAX_KEYS)
         return fail(CRAG_E2BIG, "attr_masks_host: %d distinct keys, one call takes %d: split the batch", n_keys, CRAG_ATTR_MAX_KEYS);
     const uint64_t beyond = nq == 64 ? 0 : ~0ull << nq;   // the bits of queries the call does not have
@@ -210,27 +161,23 @@ extern "C" int crag_attr_masks_host(const int64_t *d_attr_ptr, const int32_t *d_
 
     const int nu = n_used <= 1 ? 1 : n_used <= 2 ? 2 : n_used <= 4 ? 4 : 8;
     // slot layout: sets [n_keys][nu] uint64 | keys [n_keys] int32 -- the clauses in use only, in clause order
-    const size_t set_bytes = (size_t)n_keys * nu * 8;
-    const size_t bytes = set_bytes + (size_t)n_keys * 4;
-    void *d = nullptr;
-    if (bytes > 0) {
-        void *h = nullptr;
-        int rc = crag_upload_slot_begin_(slot, bytes, &h, &d);
-        if (rc != CRAG_OK) return rc;
-        uint64_t *hs = (uint64_t *)h;
+    UploadPack up;
+    const int i_sets = up.add((const uint64_t *)nullptr, 0, (size_t)n_keys * nu * 8);   // repacked from [n_keys][8] below
+    const int i_keys = up.add(h_keys, (size_t)n_keys);
+    if (up.bytes > 0) {   // (a call without keys uploads nothing)
+        if ((rc = up.begin(slot)) != CRAG_OK) return rc;
+        uint64_t *hs = up.host<uint64_t>(i_sets);
         for (int j = 0; j < n_keys; ++j)
             for (int u = 0; u < nu; ++u)
                 hs[(size_t)j * nu + u] = u < n_used ? h_key_sets[(size_t)j * CRAG_ATTR_MAX_CLAUSES + used[u]] : 0;
-        memcpy((char *)h + set_bytes, h_keys, (size_t)n_keys * 4);
-        rc = crag_upload_slot_commit_(slot, bytes, stream);
-        if (rc != CRAG_OK) return rc;
+        if ((rc = up.commit(slot, stream)) != CRAG_OK) return rc;
     }
 
     crag::AttrParams p;
     p.attr_ptr = d_attr_ptr;
     p.attr_ids = d_attr_ids;
-    p.sets = (const uint64_t *)d;
-    p.keys = (const int32_t *)((const char *)d + set_bytes);
+    p.sets = up.dev<uint64_t>(i_sets);
+    p.keys = up.dev<int32_t>(i_keys);
     for (int u = 0; u < CRAG_ATTR_MAX_CLAUSES; ++u) p.clause[u] = u < n_used ? h_clause_sets[used[u]] : 0;
     p.n = n_rows;
     p.n_attrs = n_attrs;
@@ -241,9 +188,9 @@ extern "C" int crag_attr_masks_host(const int64_t *d_attr_ptr, const int32_t *d_
     p.nq = nq;
     p.in = (const uint32_t *)d_in_mask;
     p.out = (uint32_t *)d_out_mask;
-    const int64_t n_spans = (p.stride_w + crag::ATTR_SPAN_WORDS - 1) / crag::ATTR_SPAN_WORDS;
-    const int64_t cap = (int64_t)crag::attr_cu_count() * crag::ATTR_WGS_PER_CU;
-    const dim3 grid((unsigned)(n_spans < cap ? n_spans : cap)), block(crag::ATTR_THREADS);
+    const int64_t n_spans = (p.stride_w + crag::MASK_SPAN_WORDS - 1) / crag::MASK_SPAN_WORDS;
+    const int64_t cap = (int64_t)cu_count() * crag::ATTR_WGS_PER_CU;
+    const dim3 grid((unsigned)(n_spans < cap ? n_spans : cap)), block(crag::MASK_THREADS);
     switch (nu) {
     case 1: hipLaunchKernelGGL(crag::attr_masks_kernel<1>, grid, block, 0, (hipStream_t)stream, p); break;
     case 2: hipLaunchKernelGGL(crag::attr_masks_kernel<2>, grid, block, 0, (hipStream_t)stream, p); break;

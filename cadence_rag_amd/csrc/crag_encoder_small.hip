@@ -391,19 +391,6 @@ __global__ __launch_bounds__(256 * QB) void small_attn_kernel(SmallAttnParams p)
     }
 }
 
-int cu_count() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-            n = v;
-        else
-            n = 256;
-    }
-    return n;
-}
-
 }  // namespace
 
 extern "C" {

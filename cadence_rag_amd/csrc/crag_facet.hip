@@ -35,21 +35,18 @@
 
 #include "../../include/crag_dense.h"
 #include "crag_host.h"
-
+#include "crag_maskspan.h"
 
 namespace crag {
 namespace {
 
-constexpr int FACET_THREADS = 256;
-constexpr int FACET_WAVES = FACET_THREADS / 64;
-constexpr int FACET_SPAN = 1024;                           // row positions per transpose span
-constexpr int FACET_SPAN_GROUPS = FACET_SPAN / 64 / FACET_WAVES;   // 64-row groups per wave and span
+constexpr int FACET_THREADS = MASK_THREADS;                // the transpose walks the spans of crag_maskspan.h
 constexpr int FACET_CHUNK = 4096;                          // postings per workgroup chunk
 constexpr int FACET_BUF = 512;                             // keys of the selection buffer: top (<= 64) + pending
 constexpr int FACET_SELECT_LOADS = 8;                      // table entries a selection thread loads before it looks at any
 constexpr int FACET_WGS_PER_CU = 4;                        // persistent grids = this many workgroups per CU, at most
 
-static_assert(CRAG_FACET_MAX_QUERIES == 64, "one ballot lane and one set bit per query");
+static_assert(CRAG_FACET_MAX_QUERIES == MASK_MAX_QUERIES, "one ballot lane and one set bit per query");
 static_assert(CRAG_FACET_MAX_TOP + FACET_THREADS <= FACET_BUF, "a tile of candidates always fits behind the list");
 static_assert(CRAG_FACET_MAX_NAMESPACES <= 64, "one lane per range reads its posting bounds");
 
@@ -66,11 +63,11 @@ __global__ __launch_bounds__(FACET_THREADS) void facet_transpose_kernel(const ui
     if (tid < CRAG_FACET_MAX_QUERIES) s_rows[tid] = 0;
     __syncthreads();
     const int64_t n_groups = (n_rows + 63) / 64;
-    const int64_t n_spans = (n_rows + FACET_SPAN - 1) / FACET_SPAN;
+    const int64_t n_spans = (n_rows + MASK_SPAN - 1) / MASK_SPAN;
     uint32_t my_rows = 0;   // of query `lane`, over this wave's groups (n_rows < 2^31)
     for (int64_t span = blockIdx.x; span < n_spans; span += gridDim.x)
-        for (int k = 0; k < FACET_SPAN_GROUPS; ++k) {
-            const int64_t g = span * (FACET_SPAN / 64) + wave * FACET_SPAN_GROUPS + k;
+        for (int k = 0; k < MASK_GROUPS; ++k) {
+            const int64_t g = span * (MASK_SPAN / 64) + wave * MASK_GROUPS + k;
             if (g >= n_groups) break;   // (uniform in the wave)
             const int64_t base = g * 64, w0 = g * 2;
             uint64_t w = 0;
@@ -275,18 +272,6 @@ __global__ __launch_bounds__(FACET_THREADS) void facet_select_kernel(FacetSelect
     if (tid == 0) p.out_distinct[(int64_t)q * p.rg.n + r] = s_distinct;
 }
 
-int facet_cu_count() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-            n = v;
-        else
-            n = 256;
-    }
-    return n;
-}
-
 }  // namespace
 }  // namespace crag
 
@@ -326,11 +311,8 @@ extern "C" int crag_facet_counts_host(const int64_t *d_post_ptr, const int32_t *
         rg.col[r] = width;
         width += hi - lo;
     }
-    if (d_masks) {
-        if (((uintptr_t)d_masks & 3) != 0) return fail(CRAG_EINVAL, "facet_counts_host: the masks must be 4-byte aligned");
-        if (mask_stride < 0 || mask_stride % 4 != 0 || mask_stride < (n_rows + 31) / 32 * 4 || mask_stride > ((int64_t)1 << 32))
-            return fail(CRAG_EINVAL, "facet_counts_host: mask_stride must be a multiple of 4 in [ceil(n_rows/32)*4, 2^32]");
-    }
+    const int rc = check_mask_input("facet_counts_host", n_rows, d_masks, mask_stride);
+    if (rc != CRAG_OK) return rc;
     if (n_postings > 0 && (!d_post_ptr || !d_post_rows || !d_post_fid))
         return fail(CRAG_EINVAL, "facet_counts_host: NULL postings pointer");
     if (!d_out_rows || (n_ranges > 0 && (!d_out_ids || !d_out_counts || !d_out_distinct)))
@@ -347,11 +329,11 @@ extern "C" int crag_facet_counts_host(const int64_t *d_post_ptr, const int32_t *
     hipStream_t st = (hipStream_t)stream;
     uint64_t *qsets = masked ? (uint64_t *)d_workspace : nullptr;
     uint32_t *counts = (uint32_t *)((char *)d_workspace + (masked ? n_rows * 8 : 0));
-    const int64_t cap = (int64_t)crag::facet_cu_count() * crag::FACET_WGS_PER_CU;
+    const int64_t cap = (int64_t)cu_count() * crag::FACET_WGS_PER_CU;
     const dim3 block(crag::FACET_THREADS);
     if (d_masks) HIP_TRY(hipMemsetAsync(d_out_rows, 0, (size_t)nq * 8, st));   // (no rows: the zeros are the answer)
     if (masked) {
-        const int64_t n_spans = (n_rows + crag::FACET_SPAN - 1) / crag::FACET_SPAN;
+        const int64_t n_spans = (n_rows + crag::MASK_SPAN - 1) / crag::MASK_SPAN;
         hipLaunchKernelGGL(crag::facet_transpose_kernel, dim3((unsigned)(n_spans < cap ? n_spans : cap)), block, 0, st,
                            (const uint32_t *)d_masks, mask_stride / 4, n_rows, nq, qsets, (unsigned long long *)d_out_rows);
     }

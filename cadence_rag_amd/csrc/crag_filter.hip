@@ -7,35 +7,24 @@
 //              & (from[q] == INT64_MIN or started[i] != INT64_MIN and started[i] >= from[q])
 //              & (to[q]   == INT64_MAX or started[i] != INT64_MIN and started[i] <= to[q])
 //
-// One launch.  A workgroup of four waves owns FILTER_SPAN = 1024 consecutive row positions = 32 mask words of every
-// query; the grid covers the words [0, mask_stride / 4) of a run, so the zeros beyond n_rows and in the stride padding
-// come from the same code as the bits (rows at or beyond n_rows contribute 0 and load nothing).  A wave takes four
-// groups of 64 rows: every lane loads its row's timestamp and slot (coalesced), gathers qset[slot] (8 bytes; the table
-// stays in L2), clears the bits of the queries whose date range the row fails -- a wave-uniform loop over only the
-// queries that carry a bound -- and nq ballots transpose the 64 x 64 bit matrix: ballot q is the group's two mask words
-// of query q, kept by lane q.  The words meet in LDS ([query][33]: the odd stride keeps the column write and the row
-// read off each other's banks) and leave as 128 contiguous bytes per query and workgroup.  Stores only, no atomics: the
-// output is a function of the input alone, whatever the launch geometry, and a reused buffer keeps no stale bit.
+// One launch on the span frame of crag_maskspan.h: a workgroup owns one span of 1024 row positions, the grid covers the
+// words [0, mask_stride / 4) of a run (rows at or beyond n_rows contribute 0 and load nothing).  What is this file's own
+// is the middle: per 64-row group every lane loads its row's timestamp and slot (coalesced), gathers qset[slot] (8 bytes;
+// the table stays in L2) and clears the bits of the queries whose date range the row fails -- a wave-uniform loop over
+// only the queries that carry a bound.  The transpose, the LDS staging and the write-out are the header's; a reused
+// buffer keeps no stale bit.
 #include "crag_arch.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/crag_dense.h"
 #include "crag_host.h"
-
+#include "crag_maskspan.h"
 
 namespace crag {
 namespace {
 
-constexpr int FILTER_THREADS = 256;
-constexpr int FILTER_WAVES = FILTER_THREADS / 64;
-constexpr int FILTER_SPAN = 1024;                       // row positions per workgroup
-constexpr int FILTER_SPAN_WORDS = FILTER_SPAN / 32;     // mask words per query and workgroup
-constexpr int FILTER_GROUPS = FILTER_SPAN / 64 / FILTER_WAVES;   // 64-row groups per wave
-constexpr int FILTER_LDS_STRIDE = FILTER_SPAN_WORDS + 1;
-
-static_assert(FILTER_SPAN_WORDS == 32, "the write-out maps 32 consecutive threads to one query's words");
-static_assert(CRAG_FILTER_MAX_QUERIES == 64, "one ballot lane and one qset bit per query");
+static_assert(CRAG_FILTER_MAX_QUERIES == MASK_MAX_QUERIES, "one ballot lane and one qset bit per query");
 
 struct FilterParams {
     const int64_t *started;     // [n]
@@ -50,14 +39,13 @@ struct FilterParams {
     uint32_t *out;              // [nq][stride_w]
 };
 
-__global__ __launch_bounds__(FILTER_THREADS) void filter_masks_kernel(FilterParams p) {
-    __shared__ uint32_t s_words[CRAG_FILTER_MAX_QUERIES * FILTER_LDS_STRIDE];
+__global__ __launch_bounds__(MASK_THREADS) void filter_masks_kernel(FilterParams p) {
+    __shared__ uint32_t s_words[MASK_LDS_WORDS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t row0 = (int64_t)blockIdx.x * FILTER_SPAN;
-    const int nq = p.nq;
+    const int64_t row0 = (int64_t)blockIdx.x * MASK_SPAN;
 
-    for (int g = 0; g < FILTER_GROUPS; ++g) {
-        const int gl = wave * FILTER_GROUPS + g;          // the group's number inside the span
+    for (int g = 0; g < MASK_GROUPS; ++g) {
+        const int gl = wave * MASK_GROUPS + g;            // the group's number inside the span
         const int64_t i = row0 + (int64_t)gl * 64 + lane;
         uint64_t bits = 0;
         int64_t ts = INT64_MIN;
@@ -78,27 +66,10 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_masks_kernel(FilterPara
             if (!pass) bits &= ~(1ull << q);
         }
         // every lane takes part in every ballot: the lanes beyond n_rows hold 0
-        const uint32_t lo = (uint32_t)bits, hi = (uint32_t)(bits >> 32);
-        uint64_t mine = 0;
-        for (int q = 0; q < nq && q < 32; ++q) {
-            const uint64_t b = __ballot((lo >> q) & 1u);
-            if (lane == q) mine = b;
-        }
-        for (int q = 32; q < nq; ++q) {
-            const uint64_t b = __ballot((hi >> (q - 32)) & 1u);
-            if (lane == q) mine = b;
-        }
-        if (lane < nq) {
-            s_words[lane * FILTER_LDS_STRIDE + 2 * gl] = (uint32_t)mine;
-            s_words[lane * FILTER_LDS_STRIDE + 2 * gl + 1] = (uint32_t)(mine >> 32);
-        }
+        stage_group(s_words, gl, lane, p.nq, ballot_transpose(bits, p.nq, lane));
     }
     __syncthreads();
-    // 32 consecutive threads write one query's 32 words; a word at or beyond the stride belongs to the next run
-    const int w = tid & 31;
-    const int64_t gw = (int64_t)blockIdx.x * FILTER_SPAN_WORDS + w;
-    if (gw < p.stride_w)
-        for (int q = tid >> 5; q < nq; q += FILTER_THREADS / 32) p.out[(int64_t)q * p.stride_w + gw] = s_words[q * FILTER_LDS_STRIDE + w];
+    store_span(s_words, blockIdx.x, p.stride_w, p.nq, p.out, nullptr, 0, 0);
 }
 
 }  // namespace
@@ -112,32 +83,27 @@ extern "C" int crag_filter_masks_host(const int64_t *d_started_us, const int32_t
     if (nq < 1 || nq > CRAG_FILTER_MAX_QUERIES) return fail(CRAG_EINVAL, "filter_masks_host: need 1 <= nq <= 64");
     if (n_rows < 0 || n_rows > INT32_MAX) return fail(CRAG_EINVAL, "filter_masks_host: n_rows must be in [0, 2^31)");
     if (n_calls < 0) return fail(CRAG_EINVAL, "filter_masks_host: n_calls must not be negative");
-    if (mask_stride < 0 || mask_stride % 4 != 0 || mask_stride < (n_rows + 31) / 32 * 4 || mask_stride > ((int64_t)1 << 32))
-        return fail(CRAG_EINVAL, "filter_masks_host: mask_stride must be a multiple of 4 in [ceil(n_rows/32)*4, 2^32]");
+    int rc = check_mask_strides("filter_masks_host", n_rows, nullptr, 0, d_out_mask, mask_stride);
+    if (rc != CRAG_OK) return rc;
     if (!h_date_from || !h_date_to || !slot) return fail(CRAG_EINVAL, "filter_masks_host: NULL pointer argument");
     if (n_rows > 0 && (!d_started_us || !d_call_slot)) return fail(CRAG_EINVAL, "filter_masks_host: NULL column pointer");
-    if (mask_stride > 0 && !d_out_mask) return fail(CRAG_EINVAL, "filter_masks_host: NULL output pointer");
-    if (((uintptr_t)d_out_mask & 3) != 0) return fail(CRAG_EINVAL, "filter_masks_host: the output must be 4-byte aligned");
     if (mask_stride == 0) return CRAG_OK;   // (n_rows is 0: the runs are empty)
 
     // slot layout: from [64] int64 | to [64] int64 | qset [n_calls] uint64
     const size_t head = (size_t)CRAG_FILTER_MAX_QUERIES * 8;
-    const size_t bytes = 2 * head + (h_call_qset ? (size_t)n_calls * 8 : 0);
-    void *h = nullptr, *d = nullptr;
-    int rc = crag_upload_slot_begin_(slot, bytes, &h, &d);
-    if (rc != CRAG_OK) return rc;
-    memcpy(h, h_date_from, (size_t)nq * 8);
-    memcpy((char *)h + head, h_date_to, (size_t)nq * 8);
-    if (h_call_qset && n_calls > 0) memcpy((char *)h + 2 * head, h_call_qset, (size_t)n_calls * 8);
-    rc = crag_upload_slot_commit_(slot, bytes, stream);
-    if (rc != CRAG_OK) return rc;
+    UploadPack up;
+    const int i_from = up.add(h_date_from, (size_t)nq, head);
+    const int i_to = up.add(h_date_to, (size_t)nq, head);
+    const int i_qset = up.add(h_call_qset, h_call_qset ? (size_t)n_calls : 0);
+    if ((rc = up.begin(slot)) != CRAG_OK) return rc;
+    if ((rc = up.commit(slot, stream)) != CRAG_OK) return rc;
 
     crag::FilterParams p;
     p.started = d_started_us;
     p.slot = d_call_slot;
-    p.qset = h_call_qset ? (const uint64_t *)((const char *)d + 2 * head) : nullptr;
-    p.from = (const int64_t *)d;
-    p.to = (const int64_t *)((const char *)d + head);
+    p.qset = h_call_qset ? up.dev<uint64_t>(i_qset) : nullptr;
+    p.from = up.dev<int64_t>(i_from);
+    p.to = up.dev<int64_t>(i_to);
     p.dated = 0;
     for (int q = 0; q < nq; ++q)
         if (h_date_from[q] != INT64_MIN || h_date_to[q] != INT64_MAX) p.dated |= 1ull << q;
@@ -146,7 +112,7 @@ extern "C" int crag_filter_masks_host(const int64_t *d_started_us, const int32_t
     p.stride_w = mask_stride / 4;
     p.nq = nq;
     p.out = (uint32_t *)d_out_mask;
-    const int64_t blocks = (p.stride_w + crag::FILTER_SPAN_WORDS - 1) / crag::FILTER_SPAN_WORDS;
-    hipLaunchKernelGGL(crag::filter_masks_kernel, dim3((unsigned)blocks), dim3(crag::FILTER_THREADS), 0, (hipStream_t)stream, p);
+    const int64_t blocks = (p.stride_w + crag::MASK_SPAN_WORDS - 1) / crag::MASK_SPAN_WORDS;
+    hipLaunchKernelGGL(crag::filter_masks_kernel, dim3((unsigned)blocks), dim3(crag::MASK_THREADS), 0, (hipStream_t)stream, p);
     return launch_ok("filter_masks");
 }

@@ -1,6 +1,6 @@
 // crag_host.h — the host helpers shared by the translation units of the C ABI: error reporting, device selection,
-// grow-only device buffers, host-or-device inputs, the argument checks and the upload packer of the BM25 entries.  Host
-// code only; hidden visibility: nothing here is exported.
+// grow-only device buffers, host-or-device inputs, the CU count, the argument checks of the BM25 and row-mask entries and
+// their upload packer.  Host code only; hidden visibility: nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -76,17 +76,28 @@ inline int check_bm25_counts(const char *op, int nq, int nq_min, int64_t n_rows,
     if (n_terms < 0 || n_terms > INT32_MAX) return fail(CRAG_EINVAL, "%s: n_terms must be in [0, 2^31)", op);
     return CRAG_OK;
 }
-// the input and output runs of an entry that turns row masks into row masks
+// The runs of packed row masks an entry writes or reads (crag_filter.hip, crag_attr.hip, crag_facet.hip,
+// crag_bm25_clause.hip): a stride in bytes is a multiple of 4 in [ceil(n_rows/32)*4, 2^32]
+inline bool mask_stride_ok(int64_t n_rows, int64_t stride) {
+    return stride >= (n_rows + 31) / 32 * 4 && stride % 4 == 0 && stride <= ((int64_t)1 << 32);
+}
+// the input and output runs of an entry that writes row masks (d_in NULL: it reads none)
 inline int check_mask_strides(const char *op, int64_t n_rows, const void *d_in, int64_t in_stride, const void *d_out,
                               int64_t out_stride) {
-    const int64_t min_stride = (n_rows + 31) / 32 * 4;
-    if (out_stride < 0 || out_stride % 4 != 0 || out_stride < min_stride || out_stride > ((int64_t)1 << 32))
+    if (!mask_stride_ok(n_rows, out_stride))
         return fail(CRAG_EINVAL, "%s: mask_stride must be a multiple of 4 in [ceil(n_rows/32)*4, 2^32]", op);
-    if (d_in && in_stride != 0 && (in_stride % 4 != 0 || in_stride < min_stride || in_stride > ((int64_t)1 << 32)))
+    if (d_in && in_stride != 0 && !mask_stride_ok(n_rows, in_stride))
         return fail(CRAG_EINVAL, "%s: in_stride must be 0 or a multiple of 4 in [ceil(n_rows/32)*4, 2^32]", op);
     if (out_stride > 0 && !d_out) return fail(CRAG_EINVAL, "%s: NULL output pointer", op);
     if (((uintptr_t)d_out & 3) != 0) return fail(CRAG_EINVAL, "%s: the output must be 4-byte aligned", op);
     if (((uintptr_t)d_in & 3) != 0) return fail(CRAG_EINVAL, "%s: the input mask must be 4-byte aligned", op);
+    return CRAG_OK;
+}
+// the runs of an entry that only reads row masks, one run per query (d_masks NULL: every row passes, no stride to check)
+inline int check_mask_input(const char *op, int64_t n_rows, const void *d_masks, int64_t stride) {
+    if (((uintptr_t)d_masks & 3) != 0) return fail(CRAG_EINVAL, "%s: the masks must be 4-byte aligned", op);
+    if (d_masks && !mask_stride_ok(n_rows, stride))
+        return fail(CRAG_EINVAL, "%s: mask_stride must be a multiple of 4 in [ceil(n_rows/32)*4, 2^32]", op);
     return CRAG_OK;
 }
 
@@ -128,6 +139,20 @@ inline int launch_ok(const char *what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(CRAG_EHIP, "%s launch failed: %s", what, hipGetErrorString(e));
     return CRAG_OK;
+}
+
+// the compute units of the current device, asked once per process (256 when the runtime does not say): what the
+// persistent grids are sized by
+inline int cu_count() {
+    static int n = 0;
+    if (n == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
+            n = v;
+        else
+            n = 256;
+    }
+    return n;
 }
 
 inline bool is_device_ptr(const void *p) {

@@ -39,7 +39,56 @@ def mask_bytes(n_rows: int) -> int:
     return ((int(n_rows) + 31) // 32) * 4
 
 
-class FilterColumns:
+def _nonempty(a: np.ndarray) -> np.ndarray:
+    """`a`, or one zero of its dtype when `a` is empty: an upload or a pointer argument always has a valid address."""
+    return a if a.size else np.zeros(1, dtype=a.dtype)
+
+
+def _halve_on_e2big(call, q0: int, nq: int, too_big) -> None:
+    """Queries [q0, q0 + nq) through `call(q0, nq)`, which returns the entry's code after raising for every error but
+    CRAG_E2BIG: a batch that is too big for one call goes as its two halves, in order; a single query that is too big
+    raises `too_big(q0)`, the caller's ValueError."""
+    if call(q0, nq) != _native.CRAG_E2BIG:
+        return
+    if nq == 1:
+        raise too_big(q0)
+    half = nq // 2
+    _halve_on_e2big(call, q0, half, too_big)
+    _halve_on_e2big(call, q0 + half, nq - half, too_big)
+
+
+class _RingColumns:
+    """Device columns whose kernel takes host arguments: they go through one upload slot per stream of `_ring`."""
+
+    def _slot(self, stream: int):
+        return self._ring.slot(stream)
+
+    def close(self) -> None:
+        self._ring.close()
+
+
+def _mask_frame(cols, noun: str, nq: int, stride: Optional[int], out, stream: Optional[int]):
+    """What the two `masks` methods do before their kernel: the device check, the bounds of nq, the default stride
+    (minimal) and stream (torch's current one), `out` allocated on that stream or validated.  Returns (out, stride,
+    stream); stride == 0 is an empty table, whose runs are empty: the caller returns `out` as it is."""
+    import torch
+    if cols.device is None:
+        raise _native.NativeLibraryError(f"these {type(cols).__name__} were built without a device")
+    if not 1 <= nq <= MAX_QUERIES:
+        raise ValueError(f"{noun} batch holds 1 to {MAX_QUERIES} queries")
+    stride = mask_bytes(cols.n) if stride is None else int(stride)
+    if stream is None:
+        stream = torch.cuda.current_stream(cols.device).cuda_stream
+    if out is None:
+        from .fusion import _on_stream
+        with _on_stream(stream, cols.device):
+            out = torch.empty((nq, stride), dtype=torch.uint8, device=cols.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (nq, stride) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 [{nq}, {stride}] tensor")
+    return out, stride, stream
+
+
+class FilterColumns(_RingColumns):
     """The filter columns of one DenseTable: per row `started_us` (int64 microseconds since the epoch, NO_LOWER for
     NaT) and `call_slot` (int32: the dense number of the row's call in `slot_of`, numbered by first appearance), built in
     ONE host pass over the rows -- per table generation, not per request.  With a `device` the two arrays are uploaded
@@ -76,21 +125,10 @@ class FilterColumns:
         """Enqueue the kernel for compiled predicates on `stream` (default: torch's current stream): a uint8 CUDA
         tensor [nq, stride] (stride: a multiple of 4 >= mask_bytes(n), default minimal), every byte written.  `out`: a
         tensor of that shape to write into (it may hold anything).  No host synchronisation."""
-        import torch
-        if self.device is None:
-            raise _native.NativeLibraryError("these FilterColumns were built without a device")
         nq = int(date_from.size)
-        if not 1 <= nq <= MAX_QUERIES or int(date_to.size) != nq:
-            raise ValueError(f"a filter batch holds 1 to {MAX_QUERIES} queries")
-        stride = mask_bytes(self.n) if stride is None else int(stride)
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        if out is None:
-            from .fusion import _on_stream
-            with _on_stream(stream, self.device):
-                out = torch.empty((nq, stride), dtype=torch.uint8, device=self.device)
-        elif out.dtype != torch.uint8 or tuple(out.shape) != (nq, stride) or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous uint8 [{nq}, {stride}] tensor")
+        if int(date_to.size) != nq:
+            raise ValueError("date_from and date_to hold one bound per query each")
+        out, stride, stream = _mask_frame(self, "a filter", nq, stride, out, stream)
         if stride == 0:   # an empty table: the runs are empty
             return out
         date_from = np.ascontiguousarray(date_from, dtype=np.int64)
@@ -100,7 +138,8 @@ class FilterColumns:
             qset = np.ascontiguousarray(qset, dtype=np.uint64)
             if qset.size != self.n_calls:
                 raise ValueError("qset must have one word per call")
-            qptr = (qset if qset.size else np.zeros(1, dtype=np.uint64)).ctypes.data   # (scoped, no calls: a valid address)
+            qset = _nonempty(qset)   # (scoped, no calls)
+            qptr = qset.ctypes.data
         rc = _native.load().crag_filter_masks_host(
             self.d_started_us.data_ptr() if self.n else None, self.d_call_slot.data_ptr() if self.n else None, self.n,
             self.n_calls, qptr, date_from.ctypes.data, date_to.ctypes.data, nq, self._slot(stream), out.data_ptr(), stride,
@@ -233,7 +272,7 @@ def attr_clauses(filters) -> List[List[Attr]]:
     return clauses
 
 
-class AttributeColumns:
+class AttributeColumns(_RingColumns):
     """The attribute columns of one DenseTable: a dictionary `id_of` from (namespace, value) to an int32 id, numbered by
     first appearance (exact strings, no hashing: the BM25 vocabulary's idiom), and the rows' ids as a CSR by row position
     (`attr_ptr` int64 [n + 1], `attr_ids` int32; duplicates inside a row are kept), built in ONE host pass per table
@@ -261,11 +300,7 @@ class AttributeColumns:
         if device is not None:
             import torch
             self.d_attr_ptr = torch.from_numpy(self.attr_ptr).to(device)
-            # (never empty: a row list without attributes still hands the kernel a valid address)
-            self.d_attr_ids = torch.from_numpy(self.attr_ids if self.attr_ids.size else np.zeros(1, dtype=np.int32)).to(device)
-
-    _slot = FilterColumns._slot
-    close = FilterColumns.close
+            self.d_attr_ids = torch.from_numpy(_nonempty(self.attr_ids)).to(device)   # (a row list without attributes)
 
     def masks(self, compiled: Tuple[np.ndarray, np.ndarray, np.ndarray], in_mask=None, in_stride: int = 0,
               stride: Optional[int] = None, out=None, stream: Optional[int] = None, nq: Optional[int] = None):
@@ -275,52 +310,40 @@ class AttributeColumns:
         in_stride == stride (in place).  A batch that lists more than 512 distinct keys (CRAG_E2BIG) is split by queries
         into row slices of `out`; a single query above 512 keys is a ValueError.  `nq`: the number of queries, by default
         the rows of `out`, else the number up to the last query that has a clause.  No host synchronisation."""
-        import torch
-        if self.device is None:
-            raise _native.NativeLibraryError("these AttributeColumns were built without a device")
         keys, key_sets, clause_sets = compiled
         clause_sets = np.ascontiguousarray(clause_sets, dtype=np.uint64)
         if nq is None:
             nq = max(int(w).bit_length() for w in clause_sets) if out is None else int(out.shape[0])
-        nq = int(nq)
-        if not 1 <= nq <= MAX_QUERIES:
-            raise ValueError(f"an attribute batch holds 1 to {MAX_QUERIES} queries")
-        stride = mask_bytes(self.n) if stride is None else int(stride)
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        if out is None:
-            from .fusion import _on_stream
-            with _on_stream(stream, self.device):
-                out = torch.empty((nq, stride), dtype=torch.uint8, device=self.device)
-        elif out.dtype != torch.uint8 or tuple(out.shape) != (nq, stride) or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous uint8 [{nq}, {stride}] tensor")
+        out, stride, stream = _mask_frame(self, "an attribute", int(nq), stride, out, stream)
         if stride == 0:   # an empty table: the runs are empty
             return out
-        self._run(np.ascontiguousarray(keys, dtype=np.int32), np.ascontiguousarray(key_sets, dtype=np.uint64).reshape(-1, MAX_CLAUSES),
-                  clause_sets, 0, nq, None if in_mask is None else in_mask.data_ptr(), int(in_stride), out.data_ptr(), stride, stream)
-        return out
+        keys = np.ascontiguousarray(keys, dtype=np.int32)
+        key_sets = np.ascontiguousarray(key_sets, dtype=np.uint64).reshape(-1, MAX_CLAUSES)
+        in_ptr, in_stride = None if in_mask is None else in_mask.data_ptr(), int(in_stride)
+        out_ptr = out.data_ptr()
 
-    def _run(self, keys, key_sets, clause_sets, q0: int, nq: int, in_ptr, in_stride: int, out_ptr: int, stride: int,
-             stream: int) -> None:
-        """Queries [q0, q0 + nq) of the compiled batch into their rows of the output."""
-        span = np.uint64((1 << nq) - 1)
-        sets = (key_sets >> np.uint64(q0)) & span
-        listed = sets.any(axis=1)
-        k, s = np.ascontiguousarray(keys[listed]), np.ascontiguousarray(sets[listed])
-        c = np.ascontiguousarray((clause_sets >> np.uint64(q0)) & span)
-        rc = _native.load().crag_attr_masks_host(
-            self.d_attr_ptr.data_ptr() if self.n else None, self.d_attr_ids.data_ptr() if self.n else None, self.n,
-            self.n_attrs, k.ctypes.data if k.size else None, s.ctypes.data if k.size else None, int(k.size), c.ctypes.data,
-            nq, None if in_ptr is None else in_ptr + q0 * in_stride, in_stride, self._slot(stream), out_ptr + q0 * stride,
-            stride, ctypes.c_void_p(stream))
-        if rc != _native.CRAG_E2BIG:
-            _native.check(rc, "crag_attr_masks_host")
-            return
-        if nq == 1:
-            raise ValueError(f"one query lists {int(k.size)} distinct attribute keys, a call takes {MAX_KEYS}")
-        half = nq // 2
-        self._run(keys, key_sets, clause_sets, q0, half, in_ptr, in_stride, out_ptr, stride, stream)
-        self._run(keys, key_sets, clause_sets, q0 + half, nq - half, in_ptr, in_stride, out_ptr, stride, stream)
+        def listed(q0: int, n: int):
+            """The keys that queries [q0, q0 + n) list, and their sets as bits 0 .. n - 1."""
+            sets = (key_sets >> np.uint64(q0)) & np.uint64((1 << n) - 1)
+            some = sets.any(axis=1)
+            return np.ascontiguousarray(keys[some]), np.ascontiguousarray(sets[some])
+
+        def run(q0: int, n: int) -> int:
+            """Queries [q0, q0 + n) of the compiled batch into their rows of the output."""
+            k, s = listed(q0, n)
+            c = np.ascontiguousarray((clause_sets >> np.uint64(q0)) & np.uint64((1 << n) - 1))
+            rc = _native.load().crag_attr_masks_host(
+                self.d_attr_ptr.data_ptr() if self.n else None, self.d_attr_ids.data_ptr() if self.n else None, self.n,
+                self.n_attrs, k.ctypes.data if k.size else None, s.ctypes.data if k.size else None, int(k.size), c.ctypes.data,
+                n, None if in_ptr is None else in_ptr + q0 * in_stride, in_stride, self._slot(stream), out_ptr + q0 * stride,
+                stride, ctypes.c_void_p(stream))
+            if rc != _native.CRAG_E2BIG:
+                _native.check(rc, "crag_attr_masks_host")
+            return rc
+
+        _halve_on_e2big(run, 0, int(nq), lambda q: ValueError(
+            f"one query lists {int(listed(q, 1)[0].size)} distinct attribute keys, a call takes {MAX_KEYS}"))
+        return out
 
 
 def compile_attr_predicates(columns: AttributeColumns, batch: Sequence[Tuple[Any, Optional[Sequence[Any]]]]
@@ -429,10 +452,9 @@ class FacetColumns:
         self.d_post_ptr = self.d_post_rows = self.d_post_fid = None
         if device is not None:
             import torch
-            some = lambda a: a if a.size else np.zeros(1, dtype=a.dtype)   # (never empty: a valid address)
             self.d_post_ptr = torch.from_numpy(self.post_ptr).to(device)
-            self.d_post_rows = torch.from_numpy(some(self.post_rows)).to(device)
-            self.d_post_fid = torch.from_numpy(some(self.post_fid)).to(device)
+            self.d_post_rows = torch.from_numpy(_nonempty(self.post_rows)).to(device)
+            self.d_post_fid = torch.from_numpy(_nonempty(self.post_fid)).to(device)
 
     def requested(self, namespaces: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
         """The ranges of the requested namespaces, (lo, hi) int32 arrays; a namespace the table lacks is (0, 0)."""
@@ -488,7 +510,7 @@ class FacetColumns:
         if workspace.dtype != torch.uint8 or not workspace.is_contiguous():
             raise ValueError("workspace must be a contiguous uint8 tensor")
 
-        def run(q0: int, n: int) -> None:
+        def run(q0: int, n: int) -> int:
             rc = lib.crag_facet_counts_host(
                 self.d_post_ptr.data_ptr(), self.d_post_rows.data_ptr(), self.d_post_fid.data_ptr(), self.n_postings,
                 self.n, self.n_attrs, masks.data_ptr() + q0 * stride if stride else None, stride,
@@ -500,15 +522,14 @@ class FacetColumns:
                 ctypes.c_void_p(stream))
             if rc != _native.CRAG_E2BIG:
                 _native.check(rc, "crag_facet_counts_host")
-                return
-            if n == 1:
-                widths = {ns: int(h - l) for ns, l, h in zip(namespaces, lo, hi)}
-                raise ValueError(f"one query's count table ({4 * width} bytes + the query sets) does not fit a workspace "
-                                 f"of {int(workspace.numel())} bytes; namespace widths: {widths}")
-            run(q0, n // 2)
-            run(q0 + n // 2, n - n // 2)
+            return rc
 
-        run(0, nq)
+        def too_big(_q0: int) -> ValueError:
+            widths = {ns: int(h - l) for ns, l, h in zip(namespaces, lo, hi)}
+            return ValueError(f"one query's count table ({4 * width} bytes + the query sets) does not fit a workspace "
+                              f"of {int(workspace.numel())} bytes; namespace widths: {widths}")
+
+        _halve_on_e2big(run, 0, nq, too_big)
         return ids, counts, distinct, rows
 
     def lists(self, namespaces: Sequence[str], ids, counts, distinct, rows) -> List[Dict[str, Any]]:

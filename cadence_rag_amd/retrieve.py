@@ -157,10 +157,9 @@ class DenseTable:
         return len(self.index)
 
     def close(self) -> None:
-        if self._filter_cols is not None:
-            self._filter_cols.close()
-        if getattr(self, "_attr_cols", None) is not None:
-            self._attr_cols.close()
+        for cols in (self._filter_cols, self._attr_cols):
+            if cols is not None:
+                cols.close()
         self._filter_cols = self._attr_cols = self._facet_cols = self._mask_memo = None
         self.index.close()
 
@@ -446,56 +445,46 @@ class DenseTable:
         return pos
 
     # -- the same clause evaluated on the GPU (cadence_rag_amd.filters, crag_filter_masks_host) ----------
-    def filter_columns(self):
-        """The table's device filter columns (FilterColumns: call_started_at and the call number of every row in
-        HBM, 12 bytes per row), built in one host pass on first use and again when `generation` or the length
-        changed -- the way the exact-token and BM25 lanes follow the generation."""
+    def _device_columns(self, attr_name: str, build, close_old: bool = True):
+        """The column set kept in `attr_name`, rebuilt by `build(device, generation)` on first use and again when
+        `generation` or the length changed -- the way the exact-token and BM25 lanes follow the generation.  A kernel in
+        flight may still read the old columns: the device is synchronised before they go.  close_old: the set owns an
+        upload ring to close and feeds the masks, so the mask memo goes with it."""
         import torch
-
-        from .filters import FilterColumns
-        cols = self._filter_cols
+        cols = getattr(self, attr_name)
         if cols is None or cols.generation != self.generation or cols.n != len(self):
             if cols is not None:
-                torch.cuda.synchronize(self.index.device)   # a mask kernel in flight may still read the old columns
-                cols.close()
-            self._mask_memo = None
-            cols = self._filter_cols = FilterColumns(self.call_started_at, self.call_ids,
-                                                     device=torch.device("cuda", self.index.device),
-                                                     generation=self.generation)
+                torch.cuda.synchronize(self.index.device)
+                if close_old:
+                    cols.close()
+            if close_old:
+                self._mask_memo = None
+            cols = build(torch.device("cuda", self.index.device), self.generation)
+            setattr(self, attr_name, cols)
         return cols
+
+    def filter_columns(self):
+        """The table's device filter columns (FilterColumns: call_started_at and the call number of every row in
+        HBM, 12 bytes per row), built in one host pass per generation."""
+        from .filters import FilterColumns
+        return self._device_columns("_filter_cols", lambda device, generation: FilterColumns(
+            self.call_started_at, self.call_ids, device=device, generation=generation))
 
     def attribute_columns(self):
         """The table's device attribute columns (filters.AttributeColumns: the rows' speaker, kind and entities as a CSR
-        of dictionary ids in HBM, 8 bytes per row + 4 per attribute), built in one host pass on first use and again when
-        `generation` or the length changed, like `filter_columns`.  Only a request with an attribute clause builds
-        them."""
-        import torch
-
+        of dictionary ids in HBM, 8 bytes per row + 4 per attribute), built in one host pass per generation, like
+        `filter_columns`.  Only a request with an attribute clause builds them."""
         from .filters import AttributeColumns
-        cols = getattr(self, "_attr_cols", None)
-        if cols is None or cols.generation != self.generation or cols.n != len(self):
-            if cols is not None:
-                torch.cuda.synchronize(self.index.device)   # a mask kernel in flight may still read the old columns
-                cols.close()
-            self._mask_memo = None
-            cols = self._attr_cols = AttributeColumns(self._row_attrs(), device=torch.device("cuda", self.index.device),
-                                                      generation=self.generation)
-        return cols
+        return self._device_columns("_attr_cols", lambda device, generation: AttributeColumns(
+            self._row_attrs(), device=device, generation=generation))
 
     def facet_columns(self):
         """The table's device facet columns (filters.FacetColumns: the attributes renumbered by (namespace, value) and
-        stored as postings, 8 bytes per posting + 8 per attribute of HBM), built from `attribute_columns()` on first use
-        and again when `generation` or the length changed.  Only a request that asks for facets builds them."""
-        import torch
-
+        stored as postings, 8 bytes per posting + 8 per attribute of HBM), built from `attribute_columns()` per
+        generation.  Only a request that asks for facets builds them."""
         from .filters import FacetColumns
-        cols = getattr(self, "_facet_cols", None)
-        if cols is None or cols.generation != self.generation or cols.n != len(self):
-            if cols is not None:
-                torch.cuda.synchronize(self.index.device)   # a facet kernel in flight may still read the old columns
-            cols = self._facet_cols = FacetColumns(self.attribute_columns(), device=torch.device("cuda", self.index.device),
-                                                   generation=self.generation)
-        return cols
+        return self._device_columns("_facet_cols", lambda device, generation: FacetColumns(
+            self.attribute_columns(), device=device, generation=generation), close_old=False)
 
     def facets(self, batch: Sequence[Tuple[Optional[RetrieveFilters], Optional[Sequence[UUID]]]],
                namespaces: Sequence[str], top: int = 10) -> List[Dict[str, Any]]:
@@ -568,33 +557,18 @@ class DenseTable:
         kinds) also runs the attribute kernel (crag_attr_masks_host); one without them never builds the attribute columns."""
         import torch
 
-        from .filters import compile_attr_predicates, compile_predicates
-        by_attr = _has_attr_filters(filters)
-        by_call = bool(filters) and bool(filters.date_from or filters.date_to or call_ids is not None or filters.call_tags)
-        if not by_call and not by_attr:
+        if not self.filter_mask_applies(filters, call_ids):
             return None
         cols = self.filter_columns()
         key = (cols.generation, cols.n, filters.date_from, filters.date_to,
                None if call_ids is None else tuple(call_ids), tuple(filters.call_tags or ()))
-        if by_attr:
+        if _has_attr_filters(filters):
             key += (tuple((e.get("label"), e.get("value")) if isinstance(e, dict) else tuple(e)
                           for e in getattr(filters, "entity_filters", None) or ()),
                     tuple(getattr(filters, "speakers", None) or ()), tuple(getattr(filters, "kinds", None) or ()))
         if self._mask_memo is not None and self._mask_memo[0] == key:
             return self._mask_memo[1]
-        if by_attr:
-            # the attribute kernel runs in place behind the filter kernel on the same stream; without a call or date
-            # predicate it runs alone, with no input mask (one launch, not two)
-            acols = self.attribute_columns()
-            attrs = compile_attr_predicates(acols, [(filters, call_ids)])
-            if by_call:
-                run = cols.masks(*compile_predicates(cols, self.call_tags, [(filters, call_ids)]))
-                acols.masks(attrs, in_mask=run, in_stride=int(run.shape[1]), stride=int(run.shape[1]), out=run)
-            else:
-                run = acols.masks(attrs, nq=1)
-            mask = run[0]
-        else:
-            mask = cols.masks(*compile_predicates(cols, self.call_tags, [(filters, call_ids)]))[0]
+        mask = self.filter_masks_device([(filters, call_ids)])[0][0]   # one launch, or two with both kinds of predicate
         torch.cuda.current_stream(cols.device).synchronize()
         self._mask_memo = (key, mask)
         return mask

@@ -21,6 +21,7 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
 SIZES = [0, 1, 31, 32, 33, 63, 64, 65, 1023, 1024, 1025, 2049, 70001]
 NQS = [1, 2, 33, 64]
+HALF_NQS = [31, 32, 63]   # around the 32-bit halves of the ballot transpose, and one short of a full wave
 GUARD = 64
 N_ATTRS = 300
 LISTED = 290          # queries list keys below this; the ids [LISTED, N_ATTRS) are in the dictionary and in no query
@@ -63,7 +64,7 @@ _queries: dict = {}
 def shared_queries():
     if not _queries:
         q = make_queries(np.random.default_rng(4242))
-        _queries.update(lists=q, compiled={nq: attr_oracle.transpose(q[:nq]) for nq in NQS})
+        _queries.update(lists=q, compiled={nq: attr_oracle.transpose(q[:nq]) for nq in NQS + HALF_NQS})
     return _queries
 
 
@@ -158,6 +159,29 @@ def test_kernel_equals_the_rule_at_every_stride_and_input_mask(gpu, slot, n):
             assert np.array_equal(got, want & padded(d["in_per"][:, :mb], nq, stride)) and untouched(front, back), \
                 (n, nq, stride, "per query")
             before = rng.integers(0, 256, (nq, stride), dtype=np.uint8)                                # in place
+            got, front, back, _ = run(gpu, slot, d, compiled, nq, stride, in_place=before)
+            assert np.array_equal(got, want & before) and untouched(front, back), (n, nq, stride, "in place")
+
+
+@pytest.mark.parametrize("n", [97, 1025])
+def test_kernel_at_the_half_boundary_of_the_transpose(gpu, slot, n):
+    """nq around 32 and at 63, without an input mask, with one run per query and in place.  97 rows: one full and one
+    partial group; 1025 rows: one full span plus one row, and at the minimal stride the words behind that row's belong
+    to the next query's run."""
+    d = inputs(n)
+    mb = fl.mask_bytes(n)
+    rng = np.random.default_rng(n)
+    for nq in HALF_NQS:
+        compiled = shared_queries()["compiled"][nq]
+        for extra in (0, 4):
+            stride = mb + extra
+            want = padded(d["want"], nq, stride)
+            got, front, back, _ = run(gpu, slot, d, compiled, nq, stride)
+            assert np.array_equal(got, want) and untouched(front, back), (n, nq, stride, "null")
+            got, front, back, _ = run(gpu, slot, d, compiled, nq, stride, d["d_in_per"].data_ptr(), mb + 8)
+            assert np.array_equal(got, want & padded(d["in_per"][:, :mb], nq, stride)) and untouched(front, back), \
+                (n, nq, stride, "per query")
+            before = rng.integers(0, 256, (nq, stride), dtype=np.uint8)
             got, front, back, _ = run(gpu, slot, d, compiled, nq, stride, in_place=before)
             assert np.array_equal(got, want & before) and untouched(front, back), (n, nq, stride, "in place")
 
@@ -451,6 +475,32 @@ def test_table_masks_equal_the_host_masks_and_follow_edits(world):
         want = chunks.filter_mask(filters, call_ids)
         want = np.ones(len(chunks), dtype=bool) if want is None else want
         assert np.array_equal(masks[q].cpu().numpy(), DenseIndex.pack_mask(want)), q
+
+
+def test_the_single_form_is_row_0_of_the_batch_form(world):
+    """filter_mask_device(f, c) holds the bytes of filter_masks_device([(f, c)])[0], a second call returns the same
+    tensor (the memo), and the mask is None exactly when filter_mask returns None -- for a request with call and date
+    predicates only, with attribute clauses only, with both, and for the two that restrict nothing."""
+    F = rt.RetrieveFilters
+    at = T0 + timedelta(hours=55)
+    acme = {"label": "org", "value": "acme"}
+    requests = [(F(call_tags=["outage", "billing"], date_from=at - timedelta(hours=40)), CALLS[:6]),
+                (F(entity_filters=[acme], speakers=["alice", "bob"]), None),
+                (F(entity_filters=[acme], date_to=at + timedelta(hours=30)), CALLS[2:]),
+                (F(), None), (None, CALLS[:2])]
+    for table in (world["chunks"], world["arts"]):
+        for filters, call_ids in requests:
+            host = table.filter_mask(filters, call_ids)
+            single = table.filter_mask_device(filters, call_ids)
+            assert (single is None) == (host is None), (table.name, filters, call_ids)
+            if single is None:
+                continue
+            assert table.filter_mask_device(filters, call_ids) is single, (table.name, filters, call_ids)
+            batch, stride = table.filter_masks_device([(filters, call_ids)])
+            assert tuple(batch.shape) == (1, stride) and batch[0].data_ptr() != single.data_ptr()
+            assert np.array_equal(single.cpu().numpy(), batch[0].cpu().numpy()), (table.name, filters, call_ids)
+            assert np.array_equal(single.cpu().numpy(), DenseIndex.pack_mask(host)), (table.name, filters, call_ids)
+    assert world["chunks"].filter_mask(*requests[0]).any() and world["chunks"].filter_mask(*requests[2]).any()
 
 
 def host_route(table, filters, call_ids):

@@ -398,3 +398,42 @@ def test_argument_errors_are_codes_with_a_message(native_lib):
     assert b"attr_masks_host" in native_lib.crag_last_error()
     # an empty table with empty runs is nothing to do
     assert call(n_rows=0, stride=0, ptr=None, ids=None, out=None) == 0
+
+
+# ---- the batch splitter of AttributeColumns.masks and FacetColumns.counts ---------------------------------------
+@pytest.mark.parametrize("nq", [1, 2, 3, 64])
+def test_halving_on_e2big_tiles_the_batch_in_order(nq):
+    """A fake entry that answers CRAG_E2BIG above a width: the slices it accepts tile [0, nq) in order without overlap,
+    every refused slice is retried as its halves and never as itself, and a single query that is too big raises the
+    caller's ValueError at that query, behind the slices in front of it."""
+    def too_big(q):
+        return ValueError(f"query {q} is too big")
+
+    for width in (1, 2, 5, 64):
+        issued, accepted = [], []
+
+        def call(q0, n):
+            issued.append((q0, n))
+            if n > width:
+                return _native.CRAG_E2BIG
+            accepted.append((q0, n))
+            return 0
+
+        assert fl._halve_on_e2big(call, 0, nq, too_big) is None
+        at = 0
+        for q0, n in accepted:
+            assert q0 == at and 1 <= n <= width, (nq, width, accepted)
+            at += n
+        assert at == nq and issued[0] == (0, nq) and len(set(issued)) == len(issued), (nq, width, issued)
+    for heavy in sorted({0, nq // 2, nq - 1}):
+        accepted = []
+
+        def refusing(q0, n):
+            if q0 <= heavy < q0 + n:
+                return _native.CRAG_E2BIG
+            accepted.append((q0, n))
+            return 0
+
+        with pytest.raises(ValueError, match=f"query {heavy} is too big"):
+            fl._halve_on_e2big(refusing, 0, nq, too_big)
+        assert [q for q0, n in accepted for q in range(q0, q0 + n)] == list(range(heavy)), (nq, heavy, accepted)

@@ -102,6 +102,20 @@ def test_kernel_equals_the_rule_at_every_stride(gpu, slot, n):
             assert np.all(front == 0xAB) and np.all(back == 0xAB), (n, nq, stride)
 
 
+@pytest.mark.parametrize("n", [97, 1025])
+def test_kernel_at_the_half_boundary_of_the_transpose(gpu, slot, n):
+    """nq around 32, where the ballot transpose goes from the low half of a row's query set to the high one, and 63, one
+    short of a full wave.  97 rows: one full and one partial group; 1025 rows: one full span plus one row, and at the
+    minimal stride the words behind that row's belong to the next query's run."""
+    d = inputs(n)
+    for nq in (31, 32, 63):
+        for extra in (0, 4):
+            stride = fl.mask_bytes(n) + extra
+            got, front, back, _ = run(gpu, slot, d, d["qset"], d["lo"], d["hi"], nq, stride)
+            assert np.array_equal(got, padded(d["want"], nq, stride)), (n, nq, stride)
+            assert np.all(front == 0xAB) and np.all(back == 0xAB), (n, nq, stride)
+
+
 @pytest.mark.parametrize("n", [1, 33, 97, 4097])
 def test_kernel_without_a_call_table_and_without_any_filter(gpu, slot, n):
     d = inputs(n)
